@@ -3,7 +3,7 @@
 secp256k1 on MI355X, plus the second half of BASELINE.json's metric (range-proof verifies/s,
 config C5) and the inner-product-argument prover of config C3 as `extra`.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--logn 20] [--scaling weak|strong]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--logn 20] [--scaling weak|strong] [--full] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment: this process touches no GPU; it
 starts `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same args>`
@@ -19,16 +19,21 @@ all K results are complete inside the timed region.
   strong: ONE MSM of n pairs split N ways (n/N pairs per rank), north_star's "large MSMs
           shard across the GPUs of one node".
 
-Prints ONE JSON line on rank 0 (driver contract), with
+Prints ONE JSON line on rank 0 (driver contract).  A plain run sets up, warms up, times the K steps and prints the headline:
+metric, value (pairs/s), unit, higher_is_better, dtype, ms_per_step (one timed step, milliseconds), steps, warmup, config.
+--dump-outputs DIR writes the last timed step's 64-byte result as DIR/msm_result.npy (benchlib/headline.py dump_result).
+--full adds everything else, each with its own untimed work:
+  result_ok    -- the timed MSM's 64 bytes against the known answer (sum e_i k_i) * G;
   roofline     -- the dominant kernel (k_accum_l0) against the HBM roofline that north_star
                   prescribes: algorithmic bytes = 96 B/pair, duration from HIP events on the
                   launch stream inside the timed region;
   alu_roofline -- the honest utilisation figure for this integer path: multiply-add lane
                   operations per second against the raw v_mad_u64_u32 rate of the chip;
   cpu_baseline -- the plain-C oracle MSM ("port") on this host's cores, bounded sample;
-  result_ok    -- the timed MSM's 64 bytes against the known answer (sum e_i k_i) * G;
   extra        -- C5 batch verification (verifies/s) and C3 IPA prover (seconds), each with its
-                  own roofline object.
+                  own roofline object;
+  summary      -- every configuration in one compact object (the last key), after which the
+                  GPU is kept busy for --soak-seconds.
 """
 import os
 import sys

@@ -55,6 +55,14 @@ def summary_of(out):
             "result_ok_all": bool(ran) and all(ran), "checks": len(ran)}
 
 
+def dump_result(out_dir, result):
+    """--dump-outputs: the 64-byte result a caller of the timed path receives (affine x || y, 32 bytes little-endian each; the identity
+    is 64 zero bytes) as DIR/msm_result.npy, one float32 per byte in a (2, 32) array: exact, and equal bytes for equal results."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "msm_result.npy"), np.frombuffer(result, dtype=np.uint8).astype(np.float32).reshape(2, 32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -78,7 +86,14 @@ def main():
     ap.add_argument("--extra-scale", choices=("full", "small"), default="full",
                     help="small: the extras at test sizes (C5 2^8 proofs, C3 n = 2^12, C4 4 x 16 bits, the strong MSM at --logn): the N-rank "
                          "control flow with every extra in a minute (tests/test_gpu_dist.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the known-answer check, kernel events and the roofline objects, the per-stage "
+                         "breakdown, the extras, the CPU baseline and the soak (without it: set-up, warm-up, the timed steps, the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's result to DIR/msm_result.npy: float32 (2, 32), the bytes of the affine x and y, little-endian")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args, sys.argv[1:]))
@@ -166,13 +181,14 @@ def main():
     eng.sync()
     del d_G, d_k
     d_sc = torch.frombuffer(bytearray(eb), dtype=torch.uint8).to(dev)
+    c2_n = min(n, 1 << 16)
+    ns_strong = n // world                 # extra MSM_strong: this rank's share (its first n / N pairs) of ONE n-pair MSM
     # known answer of this rank's shard: sum e_i * P_i = (sum e_i k_i mod q) * G, one scalar multiplication
     # by a different kernel (k_ec_mul_batch: a double-and-add ladder, no buckets)
-    local_dlog = sum(e * k for e, k in zip(ev, kv)) % Q
-    c2_n = min(n, 1 << 16)
-    c2_dlog = sum(e * k for e, k in zip(ev[:c2_n], kv[:c2_n])) % Q
-    ns_strong = n // world                 # extra MSM_strong: this rank's share (its first n / N pairs) of ONE n-pair MSM
-    strong_dlog = sum(e * k for e, k in zip(ev[:ns_strong], kv[:ns_strong])) % Q
+    if args.full:
+        local_dlog = sum(e * k for e, k in zip(ev, kv)) % Q
+        c2_dlog = sum(e * k for e, k in zip(ev[:c2_n], kv[:c2_n])) % Q
+        strong_dlog = sum(e * k for e, k in zip(ev[:ns_strong], kv[:ns_strong])) % Q
     del kb, kv, eb, ev
     t_in = time.time() - t_in
 
@@ -247,7 +263,8 @@ def main():
     result = run_steps(args.warmup)
     sharded.exchange_us()
     host_t[:] = [0.0, 0.0, 0.0, 0.0, 0]
-    if not os.environ.get("BENCH_NO_KERNEL_EVENTS"):       # (experiments only: what the two events per step cost)
+    # the kernel events feed only the roofline objects of --full (their cost on the step: none measurable, tools/r06_event_cost.sh)
+    if args.full and not os.environ.get("BENCH_NO_KERNEL_EVENTS"):       # (experiments only: what the two events per step cost)
         eng.profile(2)          # HIP events around the dominant kernel only: each recorded event is a ~10 us bubble
     eng.profile_reset()
     barrier()
@@ -261,17 +278,19 @@ def main():
     exchange_us = sharded.exchange_us()
     host_ms = {"enqueue": host_t[0], "finish_wait_and_tail": host_t[1], "combine_wait": host_t[2], "combine_begin": host_t[3]}
     host_ms = {k_: round(v / max(host_t[4], 1) * 1e3, 4) for k_, v in host_ms.items()}
-    ev_ms = ev0.elapsed_time(ev1)
-    prof = eng.profile_read()
-    # per-stage breakdown: a few extra, UNTIMED synchronous steps with events around every stage
-    eng.profile(1)
-    eng.profile_reset()
-    for _ in range(min(5, args.steps)):
-        sharded.multiexp_local_dev(d_pts, d_sc, n)
-    prof_all = eng.profile_read()
-    eng.profile(False)
+    if rank == 0 and args.dump_outputs:
+        dump_result(args.dump_outputs, result)
+    if args.full:
+        ev_ms = ev0.elapsed_time(ev1)
+        prof = eng.profile_read()
+        # per-stage breakdown: a few extra, UNTIMED synchronous steps with events around every stage
+        eng.profile(1)
+        eng.profile_reset()
+        for _ in range(min(5, args.steps)):
+            sharded.multiexp_local_dev(d_pts, d_sc, n)
+        prof_all = eng.profile_read()
+        eng.profile(False)
 
-    n_ranks_seen = 1
     ms_by_rank = [elapsed / args.steps * 1e3]
     if use_dist:
         cpu_side = dist.get_backend() != "nccl"
@@ -281,28 +300,7 @@ def main():
         ms_by_rank = [float(t.item()) / args.steps * 1e3 for t in every]
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
-        ones = torch.ones(1, dtype=torch.int64, device="cpu" if cpu_side else dev)
-        dist.all_reduce(ones)
-        n_ranks_seen = int(ones.item())
-        dl = [None] * world
-        dist.all_gather_object(dl, local_dlog)
-        global_dlog = sum(dl) % Q
-    else:
-        global_dlog = local_dlog
-    expect = eng.ec_mul_batch_bytes(G64, global_dlog.to_bytes(32, "little"), 1)
-    result_ok = bool(result == expect)
-
     pairs_per_s = world * n * args.steps / elapsed
-    acc_ms, acc_calls = prof["msm_accumulate"]
-    acc_avg_s = acc_ms / max(acc_calls, 1) / 1e3
-    achieved_gbs = ALGO_BYTES_PER_PAIR * n / acc_avg_s / 1e9 if acc_avg_s > 0 else 0.0
-    stages = {k: round(v[0] / max(v[1], 1), 4) for k, v in prof_all.items() if v[1]}
-    geom = eng.msm_geometry(n, pipelined=not args.no_pipeline)      # the engine's own answer (csrc/msm_host.hpp msm_pick_geometry), not a constant
-    windows = geom["windows"] * geom["slices"] * geom["pairs_per_slice"] / n      # bucket additions per pair
-    isa = isa_counts()
-    traffic, traffic_corrected, traffic_src = committed_traffic(args.logn if args.scaling == "weak" or world == 1 else -1)
-
-    madds_per_launch = n * windows
     out = {
         "metric": "Pippenger MSM scalar-point pairs/sec at n=2^20",
         "value": pairs_per_s,
@@ -322,8 +320,40 @@ def main():
                                "64-byte result to host every step",
                    "pairs_per_gpu": n, "sharding": "pairs across ranks, one all_gather of 64 B partials per step",
                    "pipeline": "synchronous" if args.no_pipeline else "%d MSMs in flight (bpmi_msm_dev_enqueue / bpmi_msm_finish)" % args.depth},
-        "n_ranks_seen": n_ranks_seen,
         "dist_backend": backend,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if use_dist:
+            dist.destroy_process_group()
+        return
+
+    n_ranks_seen = 1
+    if use_dist:
+        ones = torch.ones(1, dtype=torch.int64, device="cpu" if cpu_side else dev)
+        dist.all_reduce(ones)
+        n_ranks_seen = int(ones.item())
+        dl = [None] * world
+        dist.all_gather_object(dl, local_dlog)
+        global_dlog = sum(dl) % Q
+    else:
+        global_dlog = local_dlog
+    expect = eng.ec_mul_batch_bytes(G64, global_dlog.to_bytes(32, "little"), 1)
+    result_ok = bool(result == expect)
+
+    acc_ms, acc_calls = prof["msm_accumulate"]
+    acc_avg_s = acc_ms / max(acc_calls, 1) / 1e3
+    achieved_gbs = ALGO_BYTES_PER_PAIR * n / acc_avg_s / 1e9 if acc_avg_s > 0 else 0.0
+    stages = {k: round(v[0] / max(v[1], 1), 4) for k, v in prof_all.items() if v[1]}
+    geom = eng.msm_geometry(n, pipelined=not args.no_pipeline)      # the engine's own answer (csrc/msm_host.hpp msm_pick_geometry), not a constant
+    windows = geom["windows"] * geom["slices"] * geom["pairs_per_slice"] / n      # bucket additions per pair
+    isa = isa_counts()
+    traffic, traffic_corrected, traffic_src = committed_traffic(args.logn if args.scaling == "weak" or world == 1 else -1)
+
+    madds_per_launch = n * windows
+    out.update({
+        "n_ranks_seen": n_ranks_seen,
         "result_ok": result_ok,
         "result_check": "timed MSM result == (sum e_i k_i mod q) * G computed by k_ec_mul_batch (different kernel), outside the timed region",
         "roofline": {"bound": "hbm", "achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -353,7 +383,7 @@ def main():
         "exchange_us": None if exchange_us is None else round(exchange_us, 1),      # device time of one RCCL exchange (copy up, all_gather of 64 B, fold kernel, copy down); None without a process group
         "input_setup_s": round(t_in, 2),
         "result_x_lo": result[:8].hex(),
-    }
+    })
     if isa and acc_avg_s > 0:
         mads = isa["v_mad_u64_u32_per_madd"]
         lane_mads = madds_per_launch * mads / acc_avg_s / 1e12

@@ -28,7 +28,7 @@ def test_bench_self_launches_its_ranks():
     env = dict(os.environ, BENCH_DIST_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--logn", "16",
-           "--no-extra", "--soak-seconds", "0"]
+           "--full", "--no-extra", "--soak-seconds", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -67,7 +67,7 @@ def test_bench_eight_ranks_time_sharing_this_gpu_with_every_extra():
     env = dict(os.environ, BENCH_DIST_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "8", "--steps", "4", "--warmup", "1", "--logn", "14", "--preheat-ms", "0",
-           "--soak-seconds", "0", "--no-cpu-baseline", "--extra-scale", "small"]
+           "--full", "--soak-seconds", "0", "--no-cpu-baseline", "--extra-scale", "small"]
     out = _bench_line(cmd, env, 1500)
     assert out["n_gpus"] == 8 and out["n_ranks_seen"] == 8 and out["result_ok"] is True and out["scaling"] == "weak"
     assert len(out["ms_per_step_by_rank"]) == 8 and all(v > 0 for v in out["ms_per_step_by_rank"])
@@ -105,7 +105,7 @@ def test_an_extra_failing_on_one_rank_costs_neither_the_line_nor_the_other_extra
     env = dict(os.environ, BENCH_DIST_BACKEND="gloo", BENCH_INJECT_FAILURE="C3_ipa_prover:5")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "8", "--steps", "4", "--warmup", "1", "--logn", "14", "--preheat-ms", "0",
-           "--soak-seconds", "0", "--no-cpu-baseline", "--extra-scale", "small"]
+           "--full", "--soak-seconds", "0", "--no-cpu-baseline", "--extra-scale", "small"]
     out = _bench_line(cmd, env, 1500)
     assert out["n_ranks_seen"] == 8 and out["result_ok"] is True and out["value"] > 0
     c3 = out["extra"]["C3_ipa_prover"]
@@ -120,7 +120,7 @@ def test_bench_collectives_on_rccl_with_one_rank():
     env = dict(os.environ, BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29541", os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--logn", "18",
-           "--soak-seconds", "0", "--no-cpu-baseline"]
+           "--full", "--soak-seconds", "0", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
@@ -140,7 +140,7 @@ def test_bench_two_gpus_on_rccl_when_the_box_has_them():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     env.pop("BENCH_DIST_BACKEND", None)
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--soak-seconds", "0", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--full", "--soak-seconds", "0", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1800)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])

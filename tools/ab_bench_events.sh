@@ -1,7 +1,7 @@
 #!/bin/bash
 # What do the two HIP events per step around k_accum_l0 (bench.py's live kernel timing) cost the pipelined step, and how much
 # do the fill and the drain of the two-deep pipeline weigh at 20 steps?  Run on the GPU box from the repo root.
-B="python3 bench.py --no-extra --no-cpu-baseline --soak-seconds 0"
+B="python3 bench.py --full --no-extra --no-cpu-baseline --soak-seconds 0"
 show() { python3 -c "
 import json,sys
 d=json.loads(open('gpurun_out/bench_k.json').read().strip().split('\n')[-1])

@@ -1,6 +1,6 @@
 #!/bin/bash
 # chunk length of the two-lane pipeline x the live kernel events of bench.py (do the events change which L wins?)
-B="python3 bench.py --no-extra --no-cpu-baseline --soak-seconds 0 --steps 200 --warmup 10"
+B="python3 bench.py --full --no-extra --no-cpu-baseline --soak-seconds 0 --steps 200 --warmup 10"
 for rep in 1 2; do for ev in "" 1; do for L in 86 128; do
   BENCH_NO_KERNEL_EVENTS=$ev timeout 300 $B --opt chunk=$L > gpurun_out/bench_s.json 2>/dev/null
   python3 -c "

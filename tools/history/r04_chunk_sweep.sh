@@ -3,7 +3,7 @@
 out=${1:-gpurun_out/r04_chunk}
 mkdir -p "$out"
 for L in 86 64 72 80 96 104 112 128 86 96; do
-  line=$(python bench.py --steps 200 --warmup 10 --no-extra --no-cpu-baseline --soak-seconds 0 --opt chunk=$L 2>>"$out/stderr.txt" | tail -1)
+  line=$(python bench.py --full --steps 200 --warmup 10 --no-extra --no-cpu-baseline --soak-seconds 0 --opt chunk=$L 2>>"$out/stderr.txt" | tail -1)
   python - "$L" "$line" <<'PY'
 import json, sys
 d = json.loads(sys.argv[2])

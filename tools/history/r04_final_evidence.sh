@@ -4,7 +4,7 @@
 out=${1:-gpurun_out/r04z}
 mkdir -p "$out"
 timeout 1500 python -m pytest tests -q -m gpu 2>&1 | tail -12 > "$out/pytest_gpu.txt"; tail -3 "$out/pytest_gpu.txt"
-for k in 1 2 3; do timeout 600 python bench.py > "$out/bench_$k.json" 2> "$out/bench_$k.err"; done
+for k in 1 2 3; do timeout 600 python bench.py --full > "$out/bench_$k.json" 2> "$out/bench_$k.err"; done
 python3 - "$out" <<'PY'
 import json, sys
 out = sys.argv[1]

@@ -6,7 +6,7 @@ out=${1:-gpurun_out/r04_ab}
 mkdir -p "$out"
 run() {   # label, extra args
   label=$1; shift
-  line=$(python bench.py --steps 200 --warmup 10 --no-extra --no-cpu-baseline --soak-seconds 0 "$@" 2>>"$out/stderr.txt" | tail -1)
+  line=$(python bench.py --full --steps 200 --warmup 10 --no-extra --no-cpu-baseline --soak-seconds 0 "$@" 2>>"$out/stderr.txt" | tail -1)
   echo "$line" > "$out/bench_$label.json"
   python - "$label" "$line" <<'PY'
 import json, sys

@@ -1,11 +1,11 @@
-mkdir -p gpurun_out/r05_exp10
-timeout 2400 python -m pytest tests -m gpu -x -q > gpurun_out/r05_exp10/pytest_gpu_all.txt 2>&1
-tail -8 gpurun_out/r05_exp10/pytest_gpu_all.txt
-timeout 900 python bench.py --steps 20 --warmup 5 > gpurun_out/r05_exp10/bench_default.json 2> gpurun_out/r05_exp10/bench_default.err
-tail -3 gpurun_out/r05_exp10/bench_default.err
+mkdir -p out/r05_exp10
+timeout 2400 python -m pytest tests -m gpu -x -q > out/r05_exp10/pytest_gpu_all.txt 2>&1
+tail -8 out/r05_exp10/pytest_gpu_all.txt
+timeout 900 python bench.py --full --steps 20 --warmup 5 > out/r05_exp10/bench_default.json 2> out/r05_exp10/bench_default.err
+tail -3 out/r05_exp10/bench_default.err
 python - <<'PY'
 import json
-d=json.loads(open('gpurun_out/r05_exp10/bench_default.json').read().strip().splitlines()[-1])
+d=json.loads(open('out/r05_exp10/bench_default.json').read().strip().splitlines()[-1])
 e=d['extra']
 print('headline', d['value'], d['ms_per_step'])
 c2=e['C2_msm_2e16']; print('C2', c2['ms_per_msm_one_at_a_time'], c2['ms_per_msm_two_in_flight'])

@@ -3,8 +3,8 @@
 out=${1:-gpurun_out/r05z}
 mkdir -p "$out"
 timeout 2400 python -m pytest tests -q -m gpu 2>&1 | tail -12 > "$out/pytest_gpu.txt"; tail -3 "$out/pytest_gpu.txt"
-for k in 1 2 3; do timeout 900 python bench.py --steps 20 --warmup 5 > "$out/bench_$k.json" 2> "$out/bench_$k.err"; done
-timeout 600 python bench.py --steps 200 --warmup 10 --no-extra --no-cpu-baseline > "$out/bench_200steps.json" 2> "$out/bench_200steps.err"
+for k in 1 2 3; do timeout 900 python bench.py --full --steps 20 --warmup 5 > "$out/bench_$k.json" 2> "$out/bench_$k.err"; done
+timeout 600 python bench.py --full --steps 200 --warmup 10 --no-extra --no-cpu-baseline > "$out/bench_200steps.json" 2> "$out/bench_200steps.err"
 python3 - "$out" <<'PY'
 import json, sys
 out = sys.argv[1]

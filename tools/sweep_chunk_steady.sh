@@ -1,6 +1,6 @@
 #!/bin/bash
 # chunk length L of the accumulate kernel x the two-lane pipeline at n = 2^20, at steady clocks (bench.py's preheat), one call
-B="python3 bench.py --no-extra --no-cpu-baseline --soak-seconds 0 --steps 200 --warmup 10"
+B="python3 bench.py --full --no-extra --no-cpu-baseline --soak-seconds 0 --steps 200 --warmup 10"
 for L in ${LS:-64 76 86 96 108 128}; do
   timeout 300 $B --opt chunk=$L > gpurun_out/bench_s.json 2>/dev/null
   python3 -c "
