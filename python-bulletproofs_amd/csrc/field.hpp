@@ -165,12 +165,12 @@ BPMI_HD void fe_carry(fe &r, const fe &a) {
 // The reduction (fe_mac_c below is its definition; csrc/field_gen.hpp is the same thing as chained v_mad_u64_u32):
 //   columns 9..16  s = 8 hi32(previous s) + products; the limb th = lo32(s) stays a DIRTY 32-bit value, which is all
 //                  the fold needs:  2^261 == 2^37 + 31264 (mod p), 2^37 = 2^8 2^29, so th[j] adds 31264 th[j] to
-//                  column j and 256 th[j] to column j + 1 (t17, the carry out of column 16, sits at column
-//                  17 = 8 + 9: 31264 t17 to column 8; its 256 t17 part, column 9, folds once more into columns 0, 1)
-//   column 8       raw sum; the bits above 2^24 (w, < 2^40) are units of 2^256 == 2^32 + 977 and are folded into
-//                  columns 0, 1, 2 BEFORE the low chain runs
+//                  column j and 256 th[j] to column j + 1 (hp, the carry out of column 16, is 8 hp at column
+//                  17 = 8 + 9: 31264 * 8 hp to column 8; its 256 * 8 hp part, column 9, folds once more into columns 0, 1)
+//   column 8       raw sum; its high 32 bits h8 are units of 2^264 == 2^40 + 250112 and are folded into columns 0, 1
+//                  BEFORE the low chain runs; its low 32 bits s8m are kept as they are (no mask, no shift)
 //   columns 0..7   s = carry + products + addend + fold terms; limb = s & M29, carry = s >> 29
-//   end            limb 8 keeps 24 bits of (column 8's 24 bits + the last carry); the < 2^12 above them go to limbs
+//   end            limb 8 keeps 24 bits of (s8m + the last carry, < 2^35 + 2^32); the < 2^12 above them go to limbs
 //                  0 and 1 WITHOUT a carry ripple.
 // Output ("loose"): limb 0 < 2^29 + 2^22, limb 1 < 2^29 + 2^15, limbs 2..7 < 2^29, limb 8 < 2^24; value < 2^256 + 2^45.
 // A loose value is a fine operand everywhere a tight one is (the biases below dominate its limbs, its magnitude is
@@ -194,19 +194,17 @@ BPMI_HD void fe_cols_reduce(fe &r, const fe_dcols &q) {
     th[k - 9] = (u32)s;
     hp = (u32)(s >> 32);
   }
-  const u32 t17 = hp << 3;
-  s = q.c[8] + (u64)t17 * 31264u + (u64)th[7] * 256u;
-  const u32 s8m = (u32)s & M24;
-  const u64 w = s >> 24;
-  const u32 wl = (u32)w & M29, wh = (u32)(w >> 29);
+  // hp: the carry out of column 16, weight 2^(29*16+32) = 2^496 == 250112 * 2^232 + 64028672 + 524288 * 2^29
+  s = q.c[8] + (u64)hp * 250112u + (u64)th[7] * 256u;
+  // column 8's high half h8 has weight 2^264 == 250112 + 2048 * 2^29; its low half s8m waits for the last carry
+  const u32 s8m = (u32)s, h8 = (u32)(s >> 32);
   s = 0;
 #pragma unroll
   for (int k = 0; k < 8; k++) {
     s += q.c[k] + (u64)th[k] * 31264u;
     if (k >= 1) s += (u64)th[k - 1] * 256u;
-    if (k == 0) s += (u64)t17 * (31264u * 256u) + (u64)wl * 977u;
-    if (k == 1) s += (u64)t17 * 65536u + ((u64)wl << 3) + (u64)wh * 977u;
-    if (k == 2) s += (u64)wh << 3;
+    if (k == 0) s += (u64)hp * 64028672u + (u64)h8 * 250112u;
+    if (k == 1) s += (u64)hp * 524288u + (u64)h8 * 2048u;
     t[k] = (u32)s & M29;
     s >>= 29;
   }

@@ -18,10 +18,11 @@ tests of the C body and a GPU test that compares both bit for bit pin the asm:
   columns 9..16 (high half)   s = 8 * hi32(previous s) + products;  limb th = lo32(s) is kept DIRTY (32 bits):
                               it only feeds the fold multiply-adds, and hi32(s) is a register, so the high
                               half needs no `and` and no shift at all (one extra multiply-add by 8 instead)
-  column 8                    raw sum + fold terms; everything above bit 24 (w, < 2^40) is folded into columns
-                              0..2 as w * (2^32 + 977) BEFORE the low chain runs, so no second carry pass
+  column 8                    raw sum + fold terms; its high 32 bits h8 (units of 2^264 == 2^40 + 250112) are
+                              folded into columns 0 and 1 BEFORE the low chain runs, so no second carry pass; its
+                              low 32 bits wait for the last carry as they are (no extraction at all)
   columns 0..7                s = carry + products + addend + fold terms;  limb = s & M29, carry = s >> 29
-  end                         column 8 keeps 24 bits; the < 2^12 that the last carry pushes above them goes
+  end                         column 8 keeps 24 bits of (low 32 bits + last carry); the < 2^12 above them go
                               to limbs 0 and 1 uncarried ("loose" output, see field.hpp)
 """
 import os
@@ -85,7 +86,7 @@ def body(prods, addend, add_kind="v1"):
     """prods: list of (kind, A, B).  addend: name of an fe whose limbs (times 1, or 8 with add_kind "v8") are added to
     columns 0..8, or None."""
     L = []
-    L.append("  const u32 k31264 = 31264u, k256 = 256u, k65536 = 65536u, kf = 31264u * 256u, k977 = 977u;\n")
+    L.append("  const u32 k31264 = 31264u, k256 = 256u, k250112 = 250112u, k2048 = 2048u, k17a = 64028672u, k17b = 524288u;\n")
     L.append("  u64 s, sink_;\n  u32 th[8], t[8], hp;\n")
     for kind, A, B in prods:
         if kind == "sqr":
@@ -101,10 +102,10 @@ def body(prods, addend, add_kind="v1"):
             for x, y in products(k, kind, A, B):
                 st.add(x, y)
         L.append(st.emit())
-        L.append("  th[%d] = (u32)s; hp = (u32)(s >> 32);\n" % (k - 9) if k < 16 else "  th[7] = (u32)s; const u32 t17 = (u32)(s >> 32) << 3;\n")
-    # ---- column 8, raw
+        L.append("  th[%d] = (u32)s; hp = (u32)(s >> 32);\n" % (k - 9))
+    # ---- column 8, raw (hp is now the carry out of column 16, 8 hp the top column 17)
     st = Stmt(True)
-    st.add("t17", "k31264", "vs")
+    st.add("hp", "k250112", "vs")
     st.add("th[7]", "k256", "vs")
     for kind, A, B in prods:
         for x, y in products(8, kind, A, B):
@@ -112,19 +113,16 @@ def body(prods, addend, add_kind="v1"):
     if addend:
         st.add("%s.v[8]" % addend, None, add_kind)
     L.append(st.emit())
-    L.append("  const u32 s8m = (u32)s & M24;\n  const u64 w = s >> 24;\n  const u32 wl = (u32)w & M29, wh = (u32)(w >> 29);\n")
+    L.append("  const u32 s8m = (u32)s, h8 = (u32)(s >> 32);\n")
     # ---- low chain: columns 0..7
     for k in range(8):
         st = Stmt(k == 0)
         if k == 0:
-            st.add("t17", "kf", "vs")
-            st.add("wl", "k977", "vs")
+            st.add("hp", "k17a", "vs")
+            st.add("h8", "k250112", "vs")
         if k == 1:
-            st.add("t17", "k65536", "vs")
-            st.add("wl", None, "v8")
-            st.add("wh", "k977", "vs")
-        if k == 2:
-            st.add("wh", None, "v8")
+            st.add("hp", "k17b", "vs")
+            st.add("h8", "k2048", "vs")
         st.add("th[%d]" % k, "k31264", "vs")
         if k >= 1:
             st.add("th[%d]" % (k - 1), "k256", "vs")
