@@ -432,7 +432,8 @@ int bpmi_host_free(bpmi_ctx *ctx, void *p);
 /* ---- self-test hook (not part of the drop-in surface) ---------------------------------------------------
  * Runs one member of the device's field-multiplication family on n operand tuples given as RAW 9 x 29-bit
  * limb vectors (9 uint32 each, any lazy magnitude the routine allows) and returns the raw result limbs:
- * op 0 a*b, 1 a^2, 2 a*b + c, 3 a^2 + c, 4 a*b + c*d, 5 carry(a), 6 canonical(a).  tests/test_gpu_field.py
+ * op 0 a*b, 1 a^2, 2 a*b + c, 3 a^2 + c, 4 a*b + c*d, 5 carry(a), 6 canonical(a), 7 3 a^2, 8 a*b + 8 c,
+ * 9 the limbs of the first 8 uint32 of a read as 32-byte little-endian words (fe_from_words).  tests/test_gpu_field.py
  * compares them with the host build of the same header, limb for limb -- the arithmetic under every
  * `Point + Point` of the reference (src/pippenger/group.py:31-32) is pinned at its worst-case bounds.
  * op 10..15: the mod-q limb arithmetic of the batch-preparation kernel (csrc/scalar.hpp "sq"): 10 a*b, 11 a+b, 12 a-b,
@@ -442,6 +443,12 @@ int bpmi_debug_fe_op(bpmi_ctx *ctx, int op, const uint32_t *a, const uint32_t *b
 /* self-test hook: out[i] = a[i] + b[i] on 144-byte XYZZ records (4 x 9 limbs of 29 bits: X, Y, ZZ, ZZZ; all zero = identity) with the
  * four-lane point addition of the bucket reduction (csrc/msm_kernels.hpp quad_add) */
 int bpmi_debug_quad_add(bpmi_ctx *ctx, const uint32_t *a, const uint32_t *b, uint64_t n, uint32_t *out);
+/* self-test hook: one member of the group law of csrc/curve.hpp on n raw 144-byte records, limb forms as given (36 uint32 each: XYZZ =
+ * X, Y, ZZ, ZZZ; Jacobian = X, Y, Z in the first 27; an affine addend = x, y in the first 18 of b).  Results in the same layout, unused
+ * words 0: op 0 xyzz_add(a, b), 1 xyzz_dbl(a), 2 xyzz_madd(a, b.x, b.y), 3 xyzz_dbl_affine(b.x, b.y), 4 jac_dbl(a) (Jacobian),
+ * 5 jac_madd(a, b.x, b.y) (Jacobian), 6 xyzz_to_affine(a) (x, y), 7 jac_to_affine(a) (x, y), 8 xyzz_add(r, r, b) with r = a,
+ * 9 xyzz_dbl(r, r) with r = a.  tests/test_point_forms.py compares them with the host build of the same header. */
+int bpmi_debug_point_op(bpmi_ctx *ctx, int op, const uint32_t *a, const uint32_t *b, uint64_t n, uint32_t *out);
 
 /* ---- per-stage device timing (HIP events on the ctx's stream) --------------------------
  * After bpmi_profile(ctx, 1) every MSM records HIP events around each kernel

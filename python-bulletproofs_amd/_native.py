@@ -72,6 +72,7 @@ SIGNATURES = {
     "bpmi_ipa_prove_rounds": (_i, [_vp, _cp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, ctypes.c_uint32, _vp]),
     "bpmi_debug_fe_op": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _u64, _vp]),
     "bpmi_debug_quad_add": (_i, [_vp, _vp, _vp, _u64, _vp]),
+    "bpmi_debug_point_op": (_i, [_vp, _i, _vp, _vp, _u64, _vp]),
     "bpmi_profile": (_i, [_vp, _i]),
     "bpmi_profile_reset": (_i, [_vp]),
     "bpmi_profile_read": (_i, [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_u64)]),

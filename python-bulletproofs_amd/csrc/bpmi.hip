@@ -1832,6 +1832,27 @@ int bpmi_debug_quad_add(bpmi_ctx *ctx, const uint32_t *a, const uint32_t *b, uin
   return BPMI_OK;
 }
 
+// the group law of curve.hpp (k_debug_point_op, point_kernels.hpp) on n raw 144-byte records; ops: include/bpmi.h
+int bpmi_debug_point_op(bpmi_ctx *ctx, int op, const uint32_t *a, const uint32_t *b, uint64_t n, uint32_t *out) {
+  if (!ctx || !a || !b || !out) return ctx ? fail(ctx, BPMI_E_ARG, "null argument") : BPMI_E_ARG;
+  if (op < 0 || op > 9) return fail(ctx, BPMI_E_ARG, "unknown op");
+  if (n == 0) return BPMI_OK;
+  if (n > (1u << 20)) return fail(ctx, BPMI_E_ARG, "n too large");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t bytes = 4 * XYZZ_WORDS * n, stride = align_up(bytes, 256);
+  int rc = ensure_stage_in(ctx, 3 * stride + 512);
+  if (rc) return rc;
+  char *base = (char *)ctx->stage_in;
+  HIPCHK(ctx, h2d(ctx, base, a, bytes, ctx->stream));
+  HIPCHK(ctx, h2d(ctx, base + stride, b, bytes, ctx->stream));
+  hipLaunchKernelGGL(k_debug_point_op, dim3((u32)((n + 255) / 256)), dim3(256), 0, ctx->stream, op, (const u32 *)base, (const u32 *)(base + stride), (u32)n,
+                     (u32 *)(base + 2 * stride));
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipMemcpyAsync(out, base + 2 * stride, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return BPMI_OK;
+}
+
 // ---- profiling -----------------------------------------------------------------------------------
 static void prof_drain(bpmi_ctx *ctx) {
   (void)hipStreamSynchronize(ctx->stream);

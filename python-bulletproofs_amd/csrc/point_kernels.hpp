@@ -796,3 +796,50 @@ __global__ void __launch_bounds__(256) k_ec_sum(const u32 *__restrict__ pts, u32
     for (int k = 0; k < 16; k++) out[k] = w16[k];
   }
 }
+
+// Self-test hook (bpmi_debug_point_op): one member of the group law of curve.hpp per thread on raw 36-u32 records, so that a test
+// can hand in every limb form the formulas admit and compare the limbs with the host build of the same header
+// (tests/csrc_host/host_shim.cpp t_point_op, the same switch).  a: XYZZ (X, Y, ZZ, ZZZ) or Jacobian (X, Y, Z: the first 27 u32);
+// b: XYZZ, or an affine addend (x, y: the first 18 u32).  Ops: include/bpmi.h.
+__global__ void __launch_bounds__(256) k_debug_point_op(int op, const u32 *__restrict__ a, const u32 *__restrict__ b, u32 n, u32 *__restrict__ out) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const u32 *ra = a + 36ull * i, *rb = b + 36ull * i;
+  u32 *ro = out + 36ull * i;
+  xyzz A, R;
+  jac J, JR;
+  affine B, AF;
+  xyzz_load(A, ra);
+#pragma unroll
+  for (int k = 0; k < 9; k++) { J.X.v[k] = ra[k]; J.Y.v[k] = ra[9 + k]; J.Z.v[k] = ra[18 + k]; B.x.v[k] = rb[k]; B.y.v[k] = rb[9 + k]; }
+  xyzz_set_inf(R);
+  jac_set_inf(JR);
+  fe_set_zero(AF.x); fe_set_zero(AF.y);
+  switch (op) {
+    case 0: { xyzz Bx; xyzz_load(Bx, rb); xyzz_add(R, A, Bx); break; }
+    case 1: xyzz_dbl(R, A); break;
+    case 2: R = A; xyzz_madd(R, B.x, B.y); break;
+    case 3: xyzz_dbl_affine(R, B.x, B.y); break;
+    case 4: jac_dbl(JR, J); break;
+    case 5: JR = J; jac_madd(JR, B.x, B.y); break;
+    case 6: xyzz_to_affine(AF, A); break;
+    case 7: jac_to_affine(AF, J); break;
+    case 8: { xyzz Bx; xyzz_load(Bx, rb); R = A; xyzz_add(R, R, Bx); break; }      // the aliased forms the kernels call
+    case 9: R = A; xyzz_dbl(R, R); break;
+    default: break;
+  }
+  u32 w[36];
+#pragma unroll
+  for (int k = 0; k < 36; k++) w[k] = 0;
+  if (op == 4 || op == 5) {
+#pragma unroll
+    for (int k = 0; k < 9; k++) { w[k] = JR.X.v[k]; w[9 + k] = JR.Y.v[k]; w[18 + k] = JR.Z.v[k]; }
+  } else if (op == 6 || op == 7) {
+#pragma unroll
+    for (int k = 0; k < 9; k++) { w[k] = AF.x.v[k]; w[9 + k] = AF.y.v[k]; }
+  } else if (op >= 0 && op <= 9) {
+    xyzz_store(w, R);
+  }
+#pragma unroll
+  for (int k = 0; k < 36; k++) ro[k] = w[k];
+}

@@ -242,7 +242,8 @@ __global__ void __launch_bounds__(256) k_sc_svector(const u32 *__restrict__ tab,
 
 // Self-test hook: the DEVICE bodies of the multiplication family (csrc/field_gen.hpp) on raw limbs, so that a
 // test can feed lazy magnitudes and compare the limbs with the host build of the same header (tests/test_gpu_field.py).
-// op 0 mul(a,b), 1 sqr(a), 2 mul_add(a,b,c), 3 sqr_add(a,c), 4 mul2(a,b,c,d), 5 carry(a), 6 canon(a); 10..15: mod-q limb arithmetic (below)
+// op 0 mul(a,b), 1 sqr(a), 2 mul_add(a,b,c), 3 sqr_add(a,c), 4 mul2(a,b,c,d), 5 carry(a), 6 canon(a), 7 sqr3(a), 8 mul_add8(a,b,c),
+// 9 fe_from_words(the first 8 u32 of a, as words: the device's alignbit path); 10..15: mod-q limb arithmetic (below)
 __global__ void __launch_bounds__(256) k_debug_fe_op(int op, const u32 *__restrict__ a, const u32 *__restrict__ b, const u32 *__restrict__ c,
                                                      const u32 *__restrict__ d, u32 n, u32 *__restrict__ out) {
   const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -258,6 +259,9 @@ __global__ void __launch_bounds__(256) k_debug_fe_op(int op, const u32 *__restri
     case 4: fe_mul2(r, A, B, C, D); break;
     case 5: fe_carry(r, A); break;
     case 6: fe_canon(r, A); break;
+    case 7: fe_sqr3(r, A); break;
+    case 8: fe_mul_add8(r, A, B, C); break;
+    case 9: fe_from_words(r, A.v); break;
     default: fe_set_zero(r);
   }
   if (op >= 10) {

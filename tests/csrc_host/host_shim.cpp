@@ -41,7 +41,8 @@ void t_fe_op(int op, const uint8_t *a, const uint8_t *b, uint8_t *out) {
   store_fe(out, r);
 }
 // the multiplication family on RAW limbs (any lazy magnitude the caller wants to try), raw loose limbs out:
-// op 0 mul(a,b), 1 sqr(a), 2 mul_add(a,b,add=c), 3 sqr_add(a,add=c), 4 mul2(a,b,c,d), 5 carry(a), 6 canon(a)
+// op 0 mul(a,b), 1 sqr(a), 2 mul_add(a,b,add=c), 3 sqr_add(a,add=c), 4 mul2(a,b,c,d), 5 carry(a), 6 canon(a), 7 sqr3(a),
+// 8 mul_add8(a,b,add=c), 9 fe_from_words(the first 8 u32 of a, as words)
 void t_fe_raw(int op, const u32 *a, const u32 *b, const u32 *c, const u32 *d, u32 *out) {
   fe A, B, C, D, r;
   for (int k = 0; k < 9; k++) { A.v[k] = a[k]; B.v[k] = b[k]; C.v[k] = c[k]; D.v[k] = d[k]; }
@@ -53,9 +54,50 @@ void t_fe_raw(int op, const u32 *a, const u32 *b, const u32 *c, const u32 *d, u3
     case 4: fe_mul2(r, A, B, C, D); break;
     case 5: fe_carry(r, A); break;
     case 6: fe_canon(r, A); break;
+    case 7: fe_sqr3(r, A); break;
+    case 8: fe_mul_add8(r, A, B, C); break;
+    case 9: fe_from_words(r, a); break;
     default: fe_set_zero(r);
   }
   for (int k = 0; k < 9; k++) out[k] = r.v[k];
+}
+// t_fe_raw on n cases at once (9 u32 per operand and result)
+void t_fe_raw_n(int op, const u32 *a, const u32 *b, const u32 *c, const u32 *d, u32 n, u32 *out) {
+  for (u32 i = 0; i < n; i++) t_fe_raw(op, a + 9ull * i, b + 9ull * i, c + 9ull * i, d + 9ull * i, out + 9ull * i);
+}
+// the host twin of bpmi_debug_point_op (the group law of curve.hpp on raw 36-u32 records; see include/bpmi.h for the ops), looped here
+// so that a test makes one call for a whole case list
+void t_point_op(int op, const u32 *a, const u32 *b, u32 n, u32 *out) {
+  for (u32 i = 0; i < n; i++) {
+    const u32 *ra = a + 36ull * i, *rb = b + 36ull * i;
+    u32 *ro = out + 36ull * i;
+    xyzz A, R;
+    jac J, JR;
+    affine B, AF;
+    xyzz_load(A, ra);
+    for (int k = 0; k < 9; k++) { J.X.v[k] = ra[k]; J.Y.v[k] = ra[9 + k]; J.Z.v[k] = ra[18 + k]; B.x.v[k] = rb[k]; B.y.v[k] = rb[9 + k]; }
+    xyzz_set_inf(R);
+    for (int k = 0; k < 36; k++) ro[k] = 0;
+    switch (op) {
+      case 0: { xyzz Bx; xyzz_load(Bx, rb); xyzz_add(R, A, Bx); break; }
+      case 1: xyzz_dbl(R, A); break;
+      case 2: R = A; xyzz_madd(R, B.x, B.y); break;
+      case 3: xyzz_dbl_affine(R, B.x, B.y); break;
+      case 4: jac_dbl(JR, J); break;
+      case 5: JR = J; jac_madd(JR, B.x, B.y); break;
+      case 6: xyzz_to_affine(AF, A); break;
+      case 7: jac_to_affine(AF, J); break;
+      case 8: { xyzz Bx; xyzz_load(Bx, rb); R = A; xyzz_add(R, R, Bx); break; }
+      case 9: R = A; xyzz_dbl(R, R); break;
+      default: break;
+    }
+    if (op == 4 || op == 5)
+      for (int k = 0; k < 9; k++) { ro[k] = JR.X.v[k]; ro[9 + k] = JR.Y.v[k]; ro[18 + k] = JR.Z.v[k]; }
+    else if (op == 6 || op == 7)
+      for (int k = 0; k < 9; k++) { ro[k] = AF.x.v[k]; ro[9 + k] = AF.y.v[k]; }
+    else if (op >= 0 && op <= 9)
+      xyzz_store(ro, R);
+  }
 }
 // GLV: k (32 bytes LE, < q) -> |k1|, |k2| (16 bytes LE each) and their signs; beta * x for a field element
 void t_glv_split(const uint8_t *k, uint8_t *k1, uint8_t *k2, int *signs) {

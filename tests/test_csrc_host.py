@@ -300,12 +300,145 @@ def mul_family_cases(rnd, count):
             cases.append((3, lazy(rnd.randrange(1, 3)), None, [rnd.randrange(1 << 32) for _ in range(9)], None))
         else:
             cases.append((4, lazy(1), lazy(rnd.randrange(1, 4)), lazy(rnd.randrange(1, 3)), lazy(1)))
+    # ---- fe_sqr3 (7) and fe_mul_add8 (8): their contract maxima, then the reduction's corners (below) of all seven ops
+    for op in (7, 8):
+        cases += mul_family_maxima(op)
+    for x in (LOOSE_MAX, TIGHT_MAX, zero, one, plimbs):
+        cases.append((7, x, None, None, None))
+    neg_loose = [bb - v for bb, v in zip(bias2, LOOSE_MAX)]                     # fe_neg of the largest loose value
+    for add in (bias2, neg_loose, full):
+        cases.append((8, TIGHT_MAX, DBL_SUB_MAX, add, None))                       # jac_dbl: E tight, D - X3 + 2p, 2p - C
+        cases.append((8, LOOSE_MAX, DBL_SUB_MAX, add, None))
+        cases.append((8, DBL_SUB_MAX, TIGHT_MAX, add, None))
+    for x in (zero, one, plimbs):
+        cases += [(8, x, LOOSE_MAX, bias2, None), (8, TIGHT_MAX, x, x, None), (8, zero, zero, x, None)]
+    for op, seeds in sorted(CORNER_SEEDS.items()):
+        cases += [mul_family_corner(op, s) for s in seeds]
+    # random draws after the existing ones, so that the sequence above stays as it was
+    for _ in range(count // 4):
+        op = 7 + rnd.randrange(2)
+        if op == 7:
+            loose = rnd.randrange(2)
+            top = LOOSE_MAX if loose else TIGHT_MAX
+            cases.append((7, [rnd.randrange(v + 1) for v in top], None, None, None))
+        else:
+            ma = rnd.randrange(1, 8)
+            a = [rnd.randrange(ma * (1 << 29)) for _ in range(8)] + [rnd.randrange(ma * ((1 << 24) + (1 << 20)))]
+            mb = max(1, 7 // ma)
+            b = [rnd.randrange(mb * (1 << 29)) for _ in range(8)] + [rnd.randrange(mb * ((1 << 24) + (1 << 20)))]
+            cases.append((8, a, b, [rnd.randrange(1 << 32) for _ in range(9)], None))
     return cases
 
 
 def mul_family_expected(op, a, b, c, d):
     va, vb, vc, vd = (limbs_value(x) if x is not None else 0 for x in (a, b, c, d))
-    return {0: va * vb, 1: va * va, 2: va * vb + vc, 3: va * va + vc, 4: va * vb + vc * vd}[op] % P
+    return {0: va * vb, 1: va * va, 2: va * vb + vc, 3: va * va + vc, 4: va * vb + vc * vd, 7: 3 * va * va, 8: va * vb + 8 * vc}[op] % P
+
+
+# ---- fe_cols_reduce (field.hpp) restated in Python: the model only chooses and measures cases --------------------------------
+MUL_OPS = (0, 1, 2, 3, 4, 7, 8)
+M32 = (1 << 32) - 1
+BIAS2 = [0x3FFFF85E, 0x3FFFFFEE] + [0x3FFFFFFE] * 6 + [0x01FFFFFE]
+DBL_SUB_MAX = [2 * v + bb for v, bb in zip(LOOSE_MAX, BIAS2)]          # fe_dbl_sub(a, b) of two loose values at its largest (b = 0)
+SQR3_EDGE = [M32 // 6] * 9                                              # fe_sqr3's domain edge: 6 x limb must fit 32 bits
+# seeds of mul_family_corner found by a search on the model (the first seed whose output has limb 0, resp. limb 1, >= 2^29)
+CORNER_SEEDS = {0: (1034, 6190), 1: (627, 55129), 2: (105, 15371), 3: (26, 64215), 4: (458, 39195), 7: (5, 7423), 8: (864, 30272)}
+
+
+def mul_family_maxima(op):
+    """the all-limbs-maximal admissible inputs of op (9 x the sum of mag mag over its products <= 63; the largest addend)"""
+    full = [M32] * 9
+    out = []
+    if op in (0, 2, 8):
+        for ma, mb in ((1, 7), (7, 1), (2, 3), (3, 2)):
+            for pat in (LOOSE_MAX, TIGHT_MAX):
+                out.append((op, scaled(pat, ma, pat[8] * ma), scaled(pat, mb, pat[8] * mb), None if op == 0 else full, None))
+        if op == 8:
+            out.append((8, TIGHT_MAX, DBL_SUB_MAX, full, None))
+    elif op in (1, 3):
+        for pat in (LOOSE_MAX, TIGHT_MAX):
+            out.append((op, scaled(pat, 2, pat[8] * 2), None, full if op == 3 else None, None))
+    elif op == 7:
+        out.append((7, SQR3_EDGE, None, None, None))
+    elif op == 4:
+        for ms in ((1, 3, 2, 1), (1, 4, 1, 3), (2, 2, 1, 3), (1, 7, 0, 0), (1, 1, 1, 1)):
+            for pat in (LOOSE_MAX, TIGHT_MAX):
+                out.append((4,) + tuple(scaled(pat, m, pat[8] * m) for m in ms))
+    return out
+
+
+def mul_family_corner(op, seed):
+    """one of op's maximal inputs with every limb lowered by a random 0 .. 6 % (Random(seed))"""
+    rnd = random.Random(seed)
+    base = rnd.choice(mul_family_maxima(op))
+    return (op,) + tuple(None if x is None else [v - rnd.randrange((v >> 4) + 1) for v in x] for x in base[1:])
+
+
+def mul_family_columns(op, a, b, c, d):
+    """the 17 columns fe_mac_c builds for op (the op numbers of t_fe_raw)"""
+    col = [0] * 17
+
+    def prod(x, y, times=1):
+        for i in range(9):
+            xi = (x[i] * times) & M32                                   # the C body scales a limb in 32 bits
+            for j in range(9):
+                col[i + j] += xi * y[j]
+    if op in (0, 2, 8):
+        prod(a, b)
+    elif op in (1, 3):
+        prod(a, a)
+    elif op == 7:
+        prod(a, a, 3)
+    else:
+        prod(a, b)
+        prod(c, d)
+    if op in (2, 3, 8):
+        for k in range(9):
+            col[k] += c[k] * (8 if op == 8 else 1)
+    return col
+
+
+def cols_reduce_model(col):
+    """fe_cols_reduce step for step: (limbs, h8, hp, v2); every 64-bit sum is asserted not to overflow"""
+    assert all(v >> 64 == 0 for v in col)
+    th = [0] * 8
+    s = col[9]
+    th[0], hp = s & M32, s >> 32
+    for k in range(10, 17):
+        s = col[k] + (hp << 3)
+        assert s >> 64 == 0
+        th[k - 9], hp = s & M32, s >> 32
+    s = col[8] + hp * 250112 + th[7] * 256
+    assert s >> 64 == 0
+    s8m, h8 = s & M32, s >> 32
+    s, t = 0, [0] * 8
+    for k in range(8):
+        s += col[k] + th[k] * 31264
+        if k >= 1:
+            s += th[k - 1] * 256
+        if k == 0:
+            s += hp * 64028672 + h8 * 250112
+        if k == 1:
+            s += hp * 524288 + h8 * 2048
+        assert s >> 64 == 0
+        t[k], s = s & M29, s >> 29
+    s += s8m
+    v2 = s >> 24
+    out = [t[0] + v2 * 977, t[1] + (v2 << 3)] + t[2:] + [s & ((1 << 24) - 1)]
+    assert all(v <= M32 for v in out)
+    return out, h8, hp, v2
+
+
+def fe_raw_batch(L, op, cases):
+    """t_fe_raw_n: the host C body on every (op, a, b, c, d) of `cases` in one call; the raw result limbs per case"""
+    n = len(cases)
+    z = [0] * 9
+    flat = lambda idx: (ctypes.c_uint32 * (9 * n))(*[v for case in cases for v in (case[idx] if case[idx] is not None else z)])
+    out = (ctypes.c_uint32 * (9 * n))()
+    L.t_fe_raw_n.argtypes = [ctypes.c_int] + [ctypes.POINTER(ctypes.c_uint32)] * 4 + [ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
+    L.t_fe_raw_n(op, flat(1), flat(2), flat(3), flat(4), n, out)
+    got = list(out)
+    return [got[9 * i: 9 * i + 9] for i in range(n)]
 
 
 def test_multiplication_family_raw_limbs(shim):
@@ -325,6 +458,53 @@ def test_multiplication_family_raw_limbs(shim):
         assert limbs_value(t) % P == limbs_value(l) % P and all(v < (1 << 29) for v in t[:8]) and t[8] <= (1 << 24) + (1 << 20)
         cn = fe_raw(shim, 6, l)
         assert limbs_value(cn) == limbs_value(l) % P
+
+
+def test_multiplication_family_cases_reach_the_reduction_corners(shim):
+    """The case set of the multiplication family reaches every corner of fe_cols_reduce, for each of the seven ops: the high half
+    h8 of column 8 and the carry hp out of column 16 at >= 90 % of their value at the op's all-limbs-maximal input, the final carry
+    v2 at >= half of it, and outputs whose limb 0, and whose limb 1, is >= 2^29 (the non-canonical loose forms every later zero
+    test must handle).  The Python model that measures this is pinned to the C body limb for limb on every case."""
+    cases = mul_family_cases(random.Random(77), 4000)
+    by_op = {}
+    for case in cases:
+        by_op.setdefault(case[0], []).append(case)
+    assert sorted(by_op) == list(MUL_OPS)
+    for op in MUL_OPS:
+        lst = by_op[op]
+        host = fe_raw_batch(shim, op, lst)
+        reached = [0, 0, 0]
+        high = [0, 0]
+        for case, got in zip(lst, host):
+            out, h8, hp, v2 = cols_reduce_model(mul_family_columns(*case))
+            assert out == got, case
+            reached = [max(r, x) for r, x in zip(reached, (h8, hp, v2))]
+            high = [high[0] + (out[0] >= 1 << 29), high[1] + (out[1] >= 1 << 29)]
+        ref = [max(x) for x in zip(*(cols_reduce_model(mul_family_columns(*m))[1:] for m in mul_family_maxima(op)))]
+        assert reached[0] >= 0.9 * ref[0] and reached[1] >= 0.9 * ref[1], (op, reached, ref)
+        assert reached[2] >= ref[2] / 2, (op, reached, ref)
+        assert high[0] >= 1 and high[1] >= 1, (op, high)
+
+
+def test_sqr3_and_mul_add8_at_their_contract_edges(shim):
+    """fe_sqr3 up to its documented domain edge (every limb (2^32 - 1) // 6) and fe_mul_add8 at jac_dbl's call site (E tight, D - X3
+    + 2p of magnitude about 4, the addend 2p - C at BIAS2 and at 2^32 - 1 in every limb), exactly against Python integers."""
+    for case in [(7, SQR3_EDGE, None, None, None)] + mul_family_maxima(8):
+        out = fe_raw(shim, *case)
+        assert_loose(out)
+        assert limbs_value(out) % P == mul_family_expected(*case)
+        assert out == cols_reduce_model(mul_family_columns(*case))[0]
+
+
+def test_limbs_from_words(shim):
+    """fe_from_words (op 9) on the host's 64-bit-shift path: the 29-bit limbs of the 256-bit little-endian value, also for values >= p
+    (the loader does not reduce) and for every single-bit and all-ones word pattern."""
+    rnd = random.Random(9)
+    vals = [0, 1, P - 1, P, 2**256 - 1, 2**255, (1 << 29) - 1, 1 << 29, 1 << 232, (1 << 232) - 1] + [1 << k for k in range(256)]
+    vals += [((1 << 32) - 1) << (32 * i) for i in range(8)] + [rnd.randrange(2**256) for _ in range(500)]
+    cases = [(9, [(v >> (32 * i)) & M32 for i in range(8)] + [0], None, None, None) for v in vals]
+    for v, got in zip(vals, fe_raw_batch(shim, 9, cases)):
+        assert got == [(v >> (29 * k)) & M29 for k in range(9)], hex(v)
 
 
 def test_generated_device_bodies_are_current():

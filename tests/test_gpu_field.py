@@ -1,14 +1,15 @@
 """The DEVICE bodies of the field-multiplication family (csrc/field_gen.hpp: generated v_mad_u64_u32 chains) against
 the HOST build of the same header (the C body fe_mac_c, itself checked against Python integers in
 tests/test_csrc_host.py): identical limbs on adversarial limb patterns -- every variant at the largest
-magnitudes it allows, the largest addends, loose and tight maxima, zero / one / p -- and on random lazy values.
+magnitudes it allows, the largest addends, loose and tight maxima, zero / one / p, the cases that reach the reduction's
+corners (test_csrc_host.py::test_multiplication_family_cases_reach_the_reduction_corners) -- and on random lazy values.
 This is the arithmetic under every `Point + Point` of the reference (/root/reference/src/pippenger/group.py:31-32)."""
 import ctypes
 import random
 
 import pytest
 
-from test_csrc_host import P, assert_loose, fe_raw, limbs_value, mul_family_cases, mul_family_expected, shim  # noqa: F401
+from test_csrc_host import M29, P, assert_loose, fe_raw, fe_raw_batch, limbs_value, mul_family_cases, mul_family_expected, shim  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -30,14 +31,15 @@ def test_device_multiplication_family_equals_host_limb_for_limb(shim):  # noqa: 
         out = (ctypes.c_uint32 * (9 * n))()
         eng._ck(eng.lib.bpmi_debug_fe_op(eng.ctx, op, flat(1), flat(2), flat(3), flat(4), n, out))
         got = list(out)
+        host = fe_raw_batch(shim, op, lst)
         for i, (_, a, b, c, d) in enumerate(lst):
             dev = got[9 * i: 9 * i + 9]
-            if i < 3000:                    # the host shim call is the slow part; every case is still checked against Python below
-                assert dev == fe_raw(shim, op, a, b, c, d), (op, a, b, c, d)
+            assert dev == host[i], (op, a, b, c, d)
             assert_loose(dev)
             assert limbs_value(dev) % P == mul_family_expected(op, a, b, c, d), (op, a, b, c, d)
         total += n
     assert total >= 60000
+    assert sorted(by_op) == [0, 1, 2, 3, 4, 7, 8]
     # carry / canonical form of lazy and loose inputs
     pats = [[0xFFFFFFFF] * 9, [0] * 9, [0x1FFFFC2F, 0x1FFFFFF7] + [0x1FFFFFFF] * 6 + [0x00FFFFFF]] + \
            [[rnd.randrange(1 << 32) for _ in range(9)] for _ in range(500)]
@@ -48,6 +50,25 @@ def test_device_multiplication_family_equals_host_limb_for_limb(shim):  # noqa: 
         eng._ck(eng.lib.bpmi_debug_fe_op(eng.ctx, op, arr, arr, arr, arr, n, out))
         for i, p in enumerate(pats):
             assert list(out)[9 * i: 9 * i + 9] == fe_raw(shim, op, p)
+
+
+def test_device_limbs_from_words_equal_host(shim):  # noqa: F811
+    """fe_from_words (op 9): the device's one-alignbit-per-limb path against the host's 64-bit shifts and Python, on single bits,
+    all-ones words, values >= p and random words."""
+    import gpu_common
+    eng = gpu_common.engine()
+    rnd = random.Random(99)
+    vals = [0, 1, P - 1, P, 2**256 - 1, 2**255, 1 << 232] + [1 << k for k in range(256)] + \
+           [((1 << 32) - 1) << (32 * i) for i in range(8)] + [rnd.randrange(2**256) for _ in range(4000)]
+    cases = [(9, [(v >> (32 * i)) & 0xFFFFFFFF for i in range(8)] + [0], None, None, None) for v in vals]
+    n = len(cases)
+    arr = (ctypes.c_uint32 * (9 * n))(*[w for c in cases for w in c[1]])
+    out = (ctypes.c_uint32 * (9 * n))()
+    eng._ck(eng.lib.bpmi_debug_fe_op(eng.ctx, 9, arr, arr, arr, arr, n, out))
+    got = list(out)
+    host = fe_raw_batch(shim, 9, cases)
+    for i, v in enumerate(vals):
+        assert got[9 * i: 9 * i + 9] == host[i] == [(v >> (29 * k)) & M29 for k in range(9)], hex(v)
 
 
 def test_device_mod_q_limb_arithmetic_equals_host(shim):  # noqa: F811
