@@ -392,6 +392,22 @@ int bpmi_rp_batch_prepare_dev(bpmi_ctx *ctx, uint32_t n_gens, uint32_t values_pe
 int bpmi_rp_batch_verify_dev(bpmi_ctx *ctx, uint32_t n_gens, uint32_t values_per_proof, uint64_t n_proofs, const uint8_t *blobs, uint64_t blobs_len,
                              const uint64_t *blob_off, const uint8_t *weights, const uint8_t *seed, const uint8_t *v_points, const void *d_gens, void *d_points,
                              void *d_scalars, uint8_t out[64], int64_t *first_bad);
+/* Which proofs of a rejected batch are invalid (replaces what a loop of RangeVerifier.verify gives by construction, a verdict per proof:
+ * /root/reference/src/rangeproofs/rangeproof_verifier.py:55-99, /root/reference/src/rangeproofs/rangeproof_aggreg_verifier.py:55-108).
+ * The call of bpmi_rp_batch_verify_dev with the batch cut into GROUPS of `group` consecutive proofs (group >= 1; the last group may be
+ * short): one preparation, then every group's own combination over [g h u gs hs | the group's commitments | the group's proof points],
+ * all groups in one launch.  Arguments as for bpmi_rp_batch_verify_dev (weights: 4 per proof by batch index, or derived from the seed by
+ * batch index).
+ *   values  HOST  ceil(n_proofs / group) x 64 B: values[t] = the value of group t's combination over its UNFLAGGED proofs; 64 zero
+ *                 bytes exactly when every one of them verifies (up to the 1/q soundness error)
+ *   status  HOST  n_proofs B: bit 0 = the proof failed a byte-level check (parsing, a transcript, a scalar's range), bit 1 = one of
+ *                 its point encodings is invalid (wire format 3: a wrong y).  A flagged proof contributes to no group.
+ * A well-formed proof of another wire format at the smallest flagged index is BPMI_E_ARG ("mixed wire formats"), as in the calls above;
+ * under option "rp_only_role" >= 0 every status is non-zero.  Same limits as bpmi_rp_batch_verify_dev, and ceil(n_proofs / group) x
+ * (3 + 2 n_gens) <= 2^26.  One call at a time per ctx. */
+int bpmi_rp_batch_group_values_dev(bpmi_ctx *ctx, uint32_t n_gens, uint32_t values_per_proof, uint64_t n_proofs, const uint8_t *blobs, uint64_t blobs_len,
+                                   const uint64_t *blob_off, const uint8_t *weights, const uint8_t *seed, const uint8_t *v_points, const void *d_gens,
+                                   void *d_points, void *d_scalars, uint64_t group, uint8_t *values, uint8_t *status);
 /* ---- a BATCH of single-value range proofs, proved on the device in one call (csrc/rp_prove_kernels.hpp, rp_prove_host.hpp) -------------
  * Replaces a LOOP of NIRangeProver(v, n, g, h, gs, hs, gamma, u, group, seed).prove() (/root/reference/src/rangeproofs/
  * rangeproof_prover.py:35-91) with NIProver.prove / FastNIProver2.prove inside (/root/reference/src/innerproduct/

@@ -1512,6 +1512,14 @@ int bpmi_rp_batch_prepare(uint32_t n_gens, uint32_t values_per_proof, uint64_t n
 // hashes and checks them, the weighted scalars are written straight into the caller's device scalar arrays, the proofs' points
 // are decoded where they lie in the blobs into d_points, and only the (5 + 2n) shared coefficients and the verdict come back.
 struct RpQueued { u32 *d_shared; unsigned long long *d_bad; u32 ncols; };
+// bpmi_rp_batch_group_values_dev: the preparation sums the cells per GROUP of `group` proofs instead of per batch and leaves one verdict
+// byte per proof (k_rp_verdict, k_rp_group_colsum); the arrays live behind the preparation's own in ctx->rp_buf
+struct RpGroups {
+  u32 group, ngroups;        // in
+  u32 *d_gsum, *d_gfin;      // out: ngroups x (5 + 2n) raw column sums; room for the ngroups x (3 + 2n) scalars of the groups' MSMs
+  uint8_t *d_verdict, *d_ptflag;
+  u32 *d_E, *d_vals;         // room for the window sums (37 per group) and the 64-byte values
+};
 #define RP_UPLOAD_SLICES 4
 // A batch is read in the wire format of its FIRST proof.  A well-formed proof of the OTHER format inside it is not a forged proof: the
 // device paths report it as an argument error ("mixed wire formats"), not as a verdict -- a verifier must be able to tell a
@@ -1535,7 +1543,8 @@ static int rp_mixed_formats(bpmi_ctx *ctx, const uint8_t *blobs, uint64_t blobs_
 // queues everything on the ctx's two lanes and returns without waiting; the results stay on the device (d_shared: 5 + 2n
 // scalars of 8 words, *d_bad behind them).  The caller waits for both lanes whatever this returns.
 static int rp_prepare_enqueue(bpmi_ctx *ctx, uint32_t n_gens, uint32_t m, uint64_t n_proofs, const uint8_t *blobs, uint64_t blobs_len, const uint64_t *blob_off,
-                              const uint8_t *weights, const uint8_t *seed, void *d_v_scalars, void *d_pt_scalars, void *d_points, RpQueued &Q) {
+                              const uint8_t *weights, const uint8_t *seed, void *d_v_scalars, void *d_pt_scalars, void *d_points, RpQueued &Q,
+                              RpGroups *G = nullptr) {
   if (n_gens < 2 || (n_gens & (n_gens - 1)) || n_gens > 65536) return fail(ctx, BPMI_E_ARG, "n_gens must be a power of two in [2, 65536]");
   if (m < 1 || n_gens % m) return fail(ctx, BPMI_E_ARG, "values_per_proof must divide n_gens");
   if (n_proofs == 0 || n_proofs > (1ull << 22)) return fail(ctx, BPMI_E_ARG, "n_proofs must be in [1, 2^22]");
@@ -1591,7 +1600,15 @@ static int rp_prepare_enqueue(bpmi_ctx *ctx, uint32_t n_gens, uint32_t m, uint64
   const size_t o_ctx = align_up(36 * (size_t)ncols * rows, 256), o_shared = o_ctx + align_up(36 * (size_t)nslots * rows, 256),
                o_T = o_shared + align_up(2 * out_row + 256, 256), T_bytes = 8 * (size_t)W * P,      // summed columns | verdict | MSM scalars of the shared generators
                o_lens = o_T + align_up(T_bytes, 256);                                               // format 2: lengths of the expanded proofs
-  const size_t need = o_lens + 4 * (size_t)P + 256;
+  size_t need = o_lens + 4 * (size_t)P + 256;
+  size_t o_gsum = 0, o_gfin = 0, o_verdict = 0, o_ptflag = 0, o_E = 0, o_vals = 0;
+  if (G) {
+    const size_t ng = G->ngroups;
+    o_gsum = align_up(need, 256); o_gfin = o_gsum + align_up(32 * (size_t)ncols * ng, 256);
+    o_verdict = o_gfin + align_up(32 * (size_t)(ncols - 2) * ng, 256); o_ptflag = o_verdict + align_up(P, 256);
+    o_E = o_ptflag + align_up(P, 256); o_vals = o_E + align_up(4ull * XYZZ_WORDS * (255u / MID_C + 1u) * ng, 256);
+    need = o_vals + 64 * ng + 256;
+  }
   if (need > ctx->rp_buf_bytes) {
     if (ctx->rp_buf) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(ctx->rp_buf)); ctx->rp_buf = nullptr; ctx->rp_buf_bytes = 0; }
     HIPCHK(ctx, hipMalloc(&ctx->rp_buf, need));
@@ -1605,6 +1622,13 @@ static int rp_prepare_enqueue(bpmi_ctx *ctx, uint32_t n_gens, uint32_t m, uint64
   if (weights) HIPCHK(ctx, h2d(ctx, din + o_w, weights, 128 * (size_t)P, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(d_shared, 0, out_row, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(d_bad, 0xFF, 8, ctx->stream));
+  if (G) {
+    char *b = (char *)ctx->rp_buf;
+    G->d_gsum = (u32 *)(b + o_gsum); G->d_gfin = (u32 *)(b + o_gfin); G->d_verdict = (uint8_t *)(b + o_verdict); G->d_ptflag = (uint8_t *)(b + o_ptflag);
+    G->d_E = (u32 *)(b + o_E); G->d_vals = (u32 *)(b + o_vals);
+    HIPCHK(ctx, hipMemsetAsync(G->d_gsum, 0, 32 * (size_t)ncols * G->ngroups, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(G->d_ptflag, 0, P, ctx->stream));            // (before the slices' events: the second lane's decoding sets flags)
+  }
   // Upload in slices of whole proofs; the point decoding of a slice (second lane; it reads only the wire bytes) starts as soon as the
   // slice has arrived and runs beside the upload of the next one and, for the last slice, beside the preparation kernels.
   // Option rp_overlap = 0 (measurements only): one decoding launch BEHIND the preparation kernels on the same stream, so that
@@ -1613,7 +1637,7 @@ static int rp_prepare_enqueue(bpmi_ctx *ctx, uint32_t n_gens, uint32_t m, uint64
     StageTimer t(ctx, ST_DECOMP, st);
     const u64 npts = (u64)(g1 - g0) * per;
     hipLaunchKernelGGL(k_ec_decompress_wire, dim3((u32)((npts + 255) / 256)), dim3(256), 0, st, (const uint8_t *)din, (const u64 *)(din + o_off) + g0,
-                       k, g1 - g0, (u64)g0, (u32)RP_MAX_PROOF_BYTES, (u32 *)d_points + 16ull * per * g0, d_bad);
+                       k, g1 - g0, (u64)g0, (u32)RP_MAX_PROOF_BYTES, (u32 *)d_points + 16ull * per * g0, d_bad, G ? G->d_ptflag + g0 : (uint8_t *)nullptr);
   };
   // (format 3's points are checked, not computed: 0.02 ms for 2^14 proofs -- nothing to hide behind an upload, and four uploads with their
   // events cost more than one: a batch alone 1.63 ms against 1.72; the one check still runs on the second lane, beside the expander)
@@ -1656,6 +1680,8 @@ static int rp_prepare_enqueue(bpmi_ctx *ctx, uint32_t n_gens, uint32_t m, uint64
   rpd::ElemGeom eg;
   eg.el_log = std::min<u32>(3u, lb);
   eg.ranges = n_gens >> eg.el_log;
+  // groups: the per-proof verdict needs the point flags, so the decoding comes first (no overlap: queued here; else the join below)
+  if (G && !ctx->opt_rp_overlap) decode(ctx->stream, 0, P);
   for (u32 base = 0; base < P; base += rows) {
     const u32 cnt = std::min(rows, P - base);
     u32 lanes = (u32)ctx->opt_rp_lanes;
@@ -1674,10 +1700,25 @@ static int rp_prepare_enqueue(bpmi_ctx *ctx, uint32_t n_gens, uint32_t m, uint64
     {
       StageTimer t(ctx, ST_RPELEM);
       hipLaunchKernelGGL(rpd::k_rp_elements, dim3(2 * eg.ranges * ((cnt + 63) / 64)), dim3(64), 0, ctx->stream, q, eg);
-      hipLaunchKernelGGL(rpd::k_rp_colsum, dim3(ncols), dim3(256), 0, ctx->stream, (const u32 *)d_contrib, cnt, d_shared);
+      if (!G) hipLaunchKernelGGL(rpd::k_rp_colsum, dim3(ncols), dim3(256), 0, ctx->stream, (const u32 *)d_contrib, cnt, d_shared);
+    }
+    if (G) {
+      if (base == 0 && ctx->opt_rp_overlap) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));      // the two lanes join: every point flag is set
+      StageTimer t(ctx, ST_RPELEM);
+      rpd::VerdictArgs va;
+      va.role_status = (const uint8_t *)(din + o_st); va.pt_flag = G->d_ptflag; va.verdict = G->d_verdict;
+      va.Pall = P; va.first = base; va.cnt = cnt; va.m = m; va.per = per; va.only_role = ctx->opt_rp_only_role;
+      va.v_scalars = (u32 *)d_v_scalars; va.pt_scalars = (u32 *)d_pt_scalars; va.points = (u32 *)d_points;
+      hipLaunchKernelGGL(rpd::k_rp_verdict, dim3((u32)(((uint64_t)cnt * (m + per) + 255) / 256)), dim3(256), 0, ctx->stream, va);
+      const u32 t0 = base / G->group, nt = (base + cnt - 1) / G->group - t0 + 1;                  // the groups with proofs in this chunk
+      u32 lpg = 1;
+      while (lpg < 64u && lpg < G->group) lpg <<= 1;
+      const u32 gpb = 64u / lpg, nblk = (nt + gpb - 1) / gpb;
+      hipLaunchKernelGGL(rpd::k_rp_group_colsum, dim3(ncols * nblk), dim3(64), 0, ctx->stream, (const u32 *)d_contrib, cnt, base, (const uint8_t *)G->d_verdict,
+                         G->group, t0, nt, lpg, ncols, G->d_gsum);
     }
   }
-  if (!ctx->opt_rp_overlap) decode(ctx->stream, 0, P);
+  if (!ctx->opt_rp_overlap && !G) decode(ctx->stream, 0, P);
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
   return BPMI_OK;
@@ -1774,6 +1815,102 @@ int bpmi_rp_batch_verify_dev(bpmi_ctx *ctx, uint32_t n_gens, uint32_t values_per
   rc = rp_mixed_formats(ctx, blobs, blobs_len, blob_off, *first_bad);
   if (rc) { memset(out, 0xFF, 64); return rc; }
   if (ctx->opt_rp_only_role >= 0) *first_bad = 0;
+  return BPMI_OK;
+}
+// Which proofs of a rejected batch are the bad ones (replaces what a caller of the reference gets from verifying one proof at a time:
+// src/rangeproofs/rangeproof_verifier.py:55-99, rangeproof_aggreg_verifier.py:55-108): the preparation of bpmi_rp_batch_verify_dev, but the
+// cells are summed per GROUP of `group` consecutive proofs, the groups' MSMs over [shared generators | the group's commitments | the
+// group's proof points] run as ONE launch over (group, window) (k_msm_group) with a device tail (k_group_tail), and every proof gets a
+// verdict byte for its byte-level checks.  values[t] = the 64-byte value of group t's combination over its UNFLAGGED proofs (64 zero
+// bytes: all of them verify); status[i] = bit 0: a byte-level check failed (parse, transcript, scalar range) | bit 1: an invalid point
+// encoding.  A flagged proof contributes to no group.  A group whose MSM does not fit the one-launch kernel (3 + 2n + group (m + 6 + 2k) >
+// MID_NMAX pairs) goes through msm_run, group by group: the same 64 bytes.
+int bpmi_rp_batch_group_values_dev(bpmi_ctx *ctx, uint32_t n_gens, uint32_t values_per_proof, uint64_t n_proofs, const uint8_t *blobs, uint64_t blobs_len,
+                                   const uint64_t *blob_off, const uint8_t *weights, const uint8_t *seed, const uint8_t *v_points, const void *d_gens,
+                                   void *d_points, void *d_scalars, uint64_t group, uint8_t *values, uint8_t *status) {
+  if (!ctx) return BPMI_E_ARG;
+  if (!blobs || !blob_off || (!weights && !seed) || !v_points || !d_gens || !d_points || !d_scalars || !values || !status) return fail(ctx, BPMI_E_ARG, "null argument");
+  if (group < 1) return fail(ctx, BPMI_E_ARG, "group must be at least 1");
+  if (n_proofs == 0 || n_proofs > (1ull << 22)) return fail(ctx, BPMI_E_ARG, "n_proofs must be in [1, 2^22]");
+  uint32_t k = 0;
+  while ((1u << k) < n_gens) k++;
+  const uint32_t m = values_per_proof, per = 6 + 2 * k, nshared = 3 + 2 * n_gens;
+  const uint64_t nv = n_proofs * m, npts = n_proofs * per;
+  if (nshared + nv + npts > (1ull << 23)) return fail(ctx, BPMI_E_ARG, "at most 2^23 points in the batch's MSM");
+  RpGroups G;
+  memset(&G, 0, sizeof(G));
+  G.group = (u32)std::min<uint64_t>(group, n_proofs);
+  G.ngroups = (u32)((n_proofs + G.group - 1) / G.group);
+  if ((uint64_t)G.ngroups * nshared > (1ull << 26)) return fail(ctx, BPMI_E_ARG, "too many groups: n_groups x (3 + 2 n_gens) must not exceed 2^26");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t vals_bytes = 64 * (size_t)G.ngroups;
+  int rc = ensure_pin(ctx, std::max<size_t>(32 * (size_t)(5 + 2 * n_gens) + 64, vals_bytes + n_proofs + 64));
+  if (rc) return rc;
+  HIPCHK(ctx, h2d(ctx, d_points, v_points, 64 * nv, ctx->stream));
+  const bool check = ctx->opt_validate >= 1;
+  if (check) {
+    int vrc = validate_begin(ctx, ctx->stream);
+    if (vrc) return vrc;
+    validate_enqueue(ctx, d_points, nv, 0, ctx->stream);
+    if (ctx->opt_validate >= 2) validate_enqueue(ctx, d_gens, nshared, 1, ctx->stream);
+    vrc = validate_fetch(ctx, ctx->stream);
+    if (vrc) return vrc;
+  }
+  RpQueued Q;
+  rc = rp_prepare_enqueue(ctx, n_gens, m, n_proofs, blobs, blobs_len, blob_off, weights, seed, d_scalars, (char *)d_scalars + 32 * nv, (char *)d_points + 64 * nv, Q, &G);
+  if (rc) return rp_wait_lanes(ctx, rc);
+  {
+    StageTimer t(ctx, ST_RPELEM);
+    hipLaunchKernelGGL(rpd::k_rp_group_scalars, dim3((u32)(((uint64_t)G.ngroups * nshared + 255) / 256)), dim3(256), 0, ctx->stream, (const u32 *)G.d_gsum, n_gens,
+                       G.ngroups, G.d_gfin);
+  }
+  const uint64_t pairs = nshared + (uint64_t)G.group * (m + per);          // of a full group
+  const u32 W = 255u / MID_C + 1u;
+  if (pairs <= MID_NMAX) {
+    GroupMsm J;
+    J.gens = (const u32 *)d_gens; J.gsc = G.d_gfin;
+    J.v_pts = (const u32 *)d_points; J.v_sc = (const u32 *)d_scalars;
+    J.p_pts = (const u32 *)d_points + 16 * nv; J.p_sc = (const u32 *)d_scalars + 8 * nv;
+    J.nshared = nshared; J.m = m; J.per = per; J.group = G.group; J.P = (u32)n_proofs; J.W = W; J.E = G.d_E;
+    {
+      StageTimer t(ctx, ST_ACCUM);
+      if (pairs <= GROUP_LIGHT_NMAX) hipLaunchKernelGGL((k_msm_group<GROUP_LIGHT_THREADS, GROUP_LIGHT_NMAX>), dim3(G.ngroups * W), dim3(GROUP_LIGHT_THREADS), 0, ctx->stream, J);
+      else hipLaunchKernelGGL((k_msm_group<MID_THREADS, MID_NMAX>), dim3(G.ngroups * W), dim3(MID_THREADS), 0, ctx->stream, J);
+      hipLaunchKernelGGL(k_group_tail, dim3((G.ngroups + 63) / 64), dim3(64), 0, ctx->stream, (const u32 *)G.d_E, W, (u32)MID_C, G.ngroups, G.d_vals);
+    }
+    if (hipGetLastError() != hipSuccess) rc = fail(ctx, BPMI_E_HIP, "launch of the group MSMs failed");
+    if (!rc && hipMemcpyAsync(ctx->pin, G.d_vals, vals_bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = fail(ctx, BPMI_E_HIP, "copy of the group values failed");
+  }
+  if (!rc && hipMemcpyAsync((char *)ctx->pin + vals_bytes, G.d_verdict, n_proofs, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+    rc = fail(ctx, BPMI_E_HIP, "copy of the verdicts failed");
+  rc = rp_wait_lanes(ctx, rc);
+  if (rc) return rc;
+  memcpy(status, (char *)ctx->pin + vals_bytes, n_proofs);
+  if (pairs <= MID_NMAX) {
+    memcpy(values, ctx->pin, vals_bytes);
+  } else {
+    // groups beyond the one-launch kernel's capacity: one MSM each on the three segments
+    for (u32 t = 0; t < G.ngroups && !rc; t++) {
+      const uint64_t g0 = (uint64_t)t * G.group, cnt = std::min<uint64_t>(G.group, n_proofs - g0);
+      Segs s = segs_init();
+      s.pts[0] = (const u32 *)d_gens; s.sc[0] = G.d_gfin + 8 * (size_t)nshared * t; s.n[0] = nshared;
+      s.pts[1] = (const u32 *)d_points + 16 * m * g0; s.sc[1] = (const u32 *)d_scalars + 8 * m * g0; s.n[1] = (u32)(cnt * m);
+      s.pts[2] = (const u32 *)d_points + 16 * (nv + per * g0); s.sc[2] = (const u32 *)d_scalars + 8 * (nv + per * g0); s.n[2] = (u32)(cnt * per);
+      s.total = s.n[0] + s.n[1] + s.n[2];
+      rc = msm_run(ctx, s, values + 64 * (size_t)t);
+    }
+    rc = rp_wait_lanes(ctx, rc);
+    if (rc) { memset(values, 0xFF, vals_bytes); return rc; }
+  }
+  if (check) {
+    static const char *const names[] = {"v_points", "d_gens"};
+    rc = validate_end(ctx, "bpmi_rp_batch_group_values_dev", names);
+    if (rc) { memset(values, 0xFF, vals_bytes); return rc; }
+  }
+  int64_t first_flagged = -1;
+  for (uint64_t i = 0; i < n_proofs && first_flagged < 0; i++) if (status[i]) first_flagged = (int64_t)i;
+  rc = rp_mixed_formats(ctx, blobs, blobs_len, blob_off, first_flagged);
+  if (rc) { memset(values, 0xFF, vals_bytes); return rc; }
   return BPMI_OK;
 }
 // page-locked host memory for buffers that are handed to the library again and again (e.g. the receive buffer of wire proofs:

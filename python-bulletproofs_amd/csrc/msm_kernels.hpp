@@ -1611,6 +1611,204 @@ __global__ void __launch_bounds__(MID_THREADS) k_msm_mid(MidPair p) {
   }
 }
 
+// ---- many independent MSMs of one shape in ONE launch: the groups of a batch of range proofs (bpmi_rp_batch_group_values_dev) ------
+// Group t of a batch holds the proofs [t group, min((t + 1) group, P)); its MSM runs over [g h u gs hs | the group's commitments | the
+// group's proof points] -- three segments that follow from t, so the jobs need no table: block (t, w) = blockIdx.x builds group t's Segs
+// in registers and runs window w of it with the body of k_msm_mid.  Two shapes: <MID_THREADS, MID_NMAX> (the shape of k_msm_mid, one
+// block per CU) and <GROUP_LIGHT_THREADS, GROUP_LIGHT_NMAX> for small groups (one proof of 64 bits is 151 pairs): 52 KB of LDS, three
+// blocks per CU.
+// The body of k_msm_mid once more, as a function of the block shape: k_msm_mid itself stays as it is -- sharing this function with it
+// moved its register allocation (152 VGPRs against 154 built from the text above, three ways of passing the arguments tried), and
+// C2 / C3 run on that kernel.  Window w of the MSM over `segs` (g.n pairs,
+// g.W windows), pairs [n part / parts, n (part + 1) / parts); the window sum goes to Eout[w][part].  THREADS >= 4 MID_B (step 5 runs on
+// 64 quads of lanes); a part holds at most NMAX pairs.  Keep the two texts in step.
+template <u32 THREADS, u32 NMAX>
+__device__ __forceinline__ void msm_mid_block(const Segs &segs, const MsmGeom &g, const u32 w, const u32 parts, const u32 part, u32 *const &Eout) {
+  __shared__ u32 s_cnt[MID_B + 2], s_off[MID_B + 2], s_cur[MID_B + 2], s_lane0[MID_B + 2];
+  __shared__ unsigned short s_dig[NMAX];
+  __shared__ u32 s_ent[NMAX];
+  __shared__ u32 s_key[THREADS];
+  __shared__ u32 s_val[THREADS * LDS_STRIDE];
+  __shared__ u32 s_bkt[MID_B * XYZZ_WORDS];
+  const u32 tid = threadIdx.x;
+  const u32 n = g.n;
+  // round 5: a window's pairs may be split over gridDim.z blocks (`parts`): block z runs the whole method on pairs [i0, i1) and leaves its
+  // own window sum -- sum_b b X[b] is linear in the buckets -- in E[w][z]; the host tail adds the parts of a window at the same bit offset.
+  // 74 blocks of a pair of 8 193-pair MSMs used 74 of 256 CUs with 19 additions per lane; three parts: 222 blocks, 7 per lane
+  const u32 i0 = (u32)((u64)n * part / parts), i1 = (u32)((u64)n * (part + 1u) / parts);
+  if (tid < MID_B + 2) s_cnt[tid] = 0;
+  for (u32 i = tid; i < MID_B * XYZZ_WORDS; i += THREADS) s_bkt[i] = 0;          // empty buckets are the identity
+  __syncthreads();
+  // 1. digits of window w.  The carry chain of the signed recoding (for_each_digit: 37 dependent steps per scalar, and every one
+  // of the 37 blocks of an MSM would walk it for every scalar) is replaced by its closed form: with K = 64 sum_{j < 36} 2^(7 j),
+  // the 7-bit field j of s + K is d_j + 64 for digits d_j in [-64, 63] that represent the same s (the top field, bits 252 .. 255,
+  // stays as it is: s < 2^255 and K < 2^252, so it is at most 9) -- one 256-bit addition and a bit-field extraction per scalar.
+  for (u32 i = i0 + tid; i < i1; i += THREADS) {
+    sc v;
+    const bool neg = load_digit_source(v, segs, i);       // s or q - s (< 2^255), and whether the point is negated
+    {
+      // K = 0x0408102040810204081020408102040810204081020408102040810204081020 40 (bit 6 + 7 j set, j < 36)
+      u64 cy = 0;
+#pragma unroll
+      for (int k = 0; k < 8; k++) {
+        u32 kw = 0;
+#pragma unroll
+        for (int j = 0; j < 36; j++) { const int bit = 6 + 7 * j; if ((bit >> 5) == k) kw |= 1u << (bit & 31); }
+        cy += (u64)v.v[k] + kw;
+        v.v[k] = (u32)cy;
+        cy >>= 32;
+      }
+    }
+    const u32 pos = MID_C * w, wi = pos >> 5, sh = pos & 31u;
+    u32 lo_w = 0, hi_w = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++) { if ((u32)k == wi) lo_w = v.v[k]; if ((u32)k == wi + 1u) hi_w = v.v[k]; }
+    const u32 field = (u32)((((u64)hi_w << 32) | lo_w) >> sh) & ((1u << MID_C) - 1u);
+    int d = (int)field - (w + 1u < g.W ? (int)MID_B : 0);
+    const u32 b = (u32)(d < 0 ? -d : d);
+    const u32 sign = (d < 0 ? 1u : 0u) ^ (neg ? 1u : 0u);
+    s_dig[i - i0] = (unsigned short)(b | ((b ? sign : 0u) << 15));
+    if (b) atomicAdd(&s_cnt[b], 1u);
+  }
+  __syncthreads();
+  // 2. offsets and lanes (65 values: one thread)
+  if (tid == 0) {
+    u32 E = 0;
+    for (u32 b = 1; b <= MID_B; b++) { s_off[b] = E; s_cur[b] = E; E += s_cnt[b]; }
+    s_off[MID_B + 1] = E;
+    const u32 q = (E + (THREADS - MID_B) - 1) / (THREADS - MID_B);                 // entries per lane (0 when E = 0)
+    u32 L = 0;
+    for (u32 b = 1; b <= MID_B; b++) { s_lane0[b] = L; L += q ? (s_cnt[b] + q - 1) / q : 0u; }
+    s_lane0[MID_B + 1] = L;                                                            // <= E / q + 64 <= 512
+  }
+  __syncthreads();
+  // 3. counting sort, then every lane adds its share of its bucket
+  for (u32 i = i0 + tid; i < i1; i += THREADS) {
+    const u32 d = s_dig[i - i0], b = d & 0x7FFFu;
+    if (b) s_ent[atomicAdd(&s_cur[b], 1u)] = i | ((d >> 15) << 31);
+  }
+  __syncthreads();
+  const u32 TL = s_lane0[MID_B + 1];
+  u32 key = 0xFFFFFFFFu;
+  xyzz acc;
+  xyzz_set_inf(acc);
+  if (tid < TL) {
+    u32 lo = 1, hi = MID_B;                                     // largest b with s_lane0[b] <= tid (buckets without lanes share their successor's start)
+    while (lo < hi) { const u32 mid = (lo + hi + 1) >> 1; if (s_lane0[mid] <= tid) lo = mid; else hi = mid - 1; }
+    // several empty buckets may start at the same lane: the one that owns it is the last of them (the only one with lanes)
+    const u32 b = lo;
+    key = b;
+    const u32 lanes = s_lane0[b + 1] - s_lane0[b], j = tid - s_lane0[b];
+    const u32 beg = s_off[b], end = s_off[b + 1];
+    u32 pos = beg + j;
+    u32 w_next[16];
+    u32 e_next = 0;
+    if (pos < end) { e_next = s_ent[pos]; load_entry_point<false>(w_next, segs, e_next & 0x7FFFFFFFu); }
+    while (pos < end) {
+      const u32 e = e_next;
+      affine P;
+      affine_from_words(P, w_next);
+      pos += lanes;
+      if (pos < end) { e_next = s_ent[pos]; load_entry_point<false>(w_next, segs, e_next & 0x7FFFFFFFu); }
+      xyzz_madd_signed(acc, P, (e >> 31) != 0);
+    }
+  }
+  // 4. segmented scan over the lanes (keys ascending); the last lane of a bucket leaves its sum in LDS
+  s_key[tid] = key;
+  __syncthreads();
+  for (u32 d = 1; d < THREADS; d <<= 1) {
+    const bool act = tid >= d && key != 0xFFFFFFFFu && s_key[tid - d] == key;
+    if (!__syncthreads_or(act)) break;
+    xyzz_store(s_val + tid * LDS_STRIDE, acc);
+    __syncthreads();
+    if (act) {
+      xyzz other;
+      xyzz_load(other, s_val + (tid - d) * LDS_STRIDE);
+      xyzz_add(acc, other, acc);
+    }
+    __syncthreads();
+  }
+  if (key != 0xFFFFFFFFu && (tid + 1 == THREADS || s_key[tid + 1] != key)) xyzz_store(s_bkt + (key - 1u) * XYZZ_WORDS, acc);
+  __syncthreads();
+  // 5. sum_b b X[b] over the 64 buckets: bucket b = rec + 1 on the quad of lanes 4 rec .. 4 rec + 3 -- the first four waves; the
+  // other four only keep the block's barriers company (`live` is wave-uniform: a barrier that part of the block never reaches is
+  // undefined behaviour in the programming model, whatever today's hardware makes of ended waves)
+  const bool live = tid < 4 * MID_B;
+  const u32 rec = tid >> 2, q4 = tid & 3u;
+  fe a;
+  fe_set_zero(a);
+  if (live) {
+#pragma unroll
+    for (int k = 0; k < 9; k++) a.v[k] = s_bkt[rec * XYZZ_WORDS + q4 * 9u + k];
+  }
+  u32 *mine = s_val + (live ? rec : 0u) * XYZZ_WORDS + q4 * 9u;                // (s_val is free again)
+#pragma unroll 1
+  for (u32 d = 1; d < MID_B; d <<= 1) {                           // inclusive suffix scan
+    if (live) {
+#pragma unroll
+      for (int k = 0; k < 9; k++) mine[k] = a.v[k];
+    }
+    __syncthreads();
+    fe b;
+    fe_set_zero(b);
+    if (live) {
+#pragma unroll
+      for (int k = 0; k < 9; k++) b.v[k] = (rec + d < MID_B) ? mine[d * XYZZ_WORDS + k] : 0u;
+    }
+    __syncthreads();
+    if (live) quad_add(a, b, q4);
+  }
+#pragma unroll 1
+  for (u32 d = MID_B >> 1; d > 0; d >>= 1) {                      // sum of all suffixes: records [0, 2d) -> [0, d)
+    if (live) {
+#pragma unroll
+      for (int k = 0; k < 9; k++) mine[k] = a.v[k];
+    }
+    __syncthreads();
+    fe b;
+    fe_set_zero(b);
+    if (live) {
+#pragma unroll
+      for (int k = 0; k < 9; k++) b.v[k] = (rec < d) ? mine[d * XYZZ_WORDS + k] : 0u;
+    }
+    __syncthreads();
+    if (live) quad_add(a, b, q4);
+  }
+  if (!live) return;
+  if (rec == 0) {
+#pragma unroll
+    for (int k = 0; k < 9; k++) Eout[((u64)w * parts + part) * XYZZ_WORDS + q4 * 9u + k] = a.v[k];
+  }
+}
+
+#define GROUP_LIGHT_THREADS 256
+#define GROUP_LIGHT_NMAX 512
+struct GroupMsm {
+  const u32 *gens, *gsc;              // the 3 + 2n shared generators; their scalars, one row of `nshared` per group
+  const u32 *v_pts, *v_sc;            // commitments and their scalars, m per proof, proof-major
+  const u32 *p_pts, *p_sc;            // proof points and their scalars, `per` per proof
+  u32 nshared, m, per, group, P, W;
+  u32 *E;                             // [t][w]: W window sums per group
+};
+template <u32 THREADS, u32 NMAX> __global__ void __launch_bounds__(THREADS) k_msm_group(GroupMsm J) {
+  const u32 t = blockIdx.x / J.W, w = blockIdx.x - t * J.W;
+  const u32 g0 = t * J.group, cnt = min(J.group, J.P - g0);
+  Segs s;
+  s.pts[0] = J.gens; s.sc[0] = J.gsc + 8ull * J.nshared * t; s.n[0] = J.nshared;
+  s.pts[1] = J.v_pts + 16ull * J.m * g0; s.sc[1] = J.v_sc + 8ull * J.m * g0; s.n[1] = cnt * J.m;
+  s.pts[2] = J.p_pts + 16ull * J.per * g0; s.sc[2] = J.p_sc + 8ull * J.per * g0; s.n[2] = cnt * J.per;
+  s.total = s.n[0] + s.n[1] + s.n[2];
+  s.hlog[0] = s.hlog[1] = s.hlog[2] = 0xFFu;
+  s.phase[0] = s.phase[1] = s.phase[2] = 0;
+  s.glv_sub = nullptr; s.glv_neg = nullptr; s.glv_bx = nullptr;
+  MsmGeom g = {};                                  // (the body reads n and W only)
+  g.n = s.total; g.c = MID_C; g.W = J.W; g.B = MID_B;
+  u32 *const Et = J.E + (u64)t * J.W * XYZZ_WORDS;
+  msm_mid_block<THREADS, NMAX>(s, g, w, 1u, 0u, Et);
+}
+template __global__ void k_msm_group<MID_THREADS, MID_NMAX>(GroupMsm);
+template __global__ void k_msm_group<GROUP_LIGHT_THREADS, GROUP_LIGHT_NMAX>(GroupMsm);
+
 // ---- tail: result = sum_w 2^(c w) sum_v 2^(off[v]) E[w][v], to canonical affine -------------
 BPMI_HD void msm_tail_combine(u32 out_words[16], const u32 *E, u32 W, u32 c, const TailOffs &to) {
   // ONE Horner chain over bit positions: E[w][v] carries weight 2^(start of window w + off[v]), so walking from the top bit down
@@ -1646,6 +1844,18 @@ __global__ void __launch_bounds__(64) k_tail(const u32 *__restrict__ E, u32 W, u
 #pragma unroll
     for (int i = 0; i < 16; i++) out[i] = w16[i];
   }
+}
+
+// the tails of many MSMs of one shape (k_msm_group: nv = 1, no wide windows): ONE LANE per group -- k_tail is one lane of a wave, and 64
+// chains of dependent additions in the lanes of one wave take the time of one
+__global__ void __launch_bounds__(64) k_group_tail(const u32 *__restrict__ E, u32 W, u32 c, u32 ngroups, u32 *__restrict__ out) {
+  const u32 t = blockIdx.x * 64u + threadIdx.x;
+  if (t >= ngroups) return;
+  TailOffs to;
+  to.nv = 1; to.off[0] = to.off[1] = to.off[2] = to.off[3] = 0;
+  u32 w16[16];
+  msm_tail_combine(w16, E + (u64)t * W * XYZZ_WORDS, W, c, to);
+  store_words16(out + 16ull * t, w16);
 }
 
 #if defined(BPMI_ISA_PROBE)

@@ -739,9 +739,10 @@ __global__ void __launch_bounds__(256, 3) k_ec_decompress(const uint8_t *__restr
 // 6-byte header and the 5 + k scalars).  It needs nothing from the preparation kernel -- it checks by itself that the blob
 // is long enough to hold the encodings and carries the header of a k-round proof -- so it runs beside it on the second
 // lane; a blob that fails that check is left to the preparation's verdict (its points are zero), an invalid encoding
-// records its proof in *bad (atomicMin; `first` = batch index of proof 0 of this launch)
+// records its proof in *bad (atomicMin; `first` = batch index of proof 0 of this launch) and, when `flag` is given (one byte per
+// proof of this launch, zeroed by the caller: bpmi_rp_batch_group_values_dev), sets the proof's own flag
 __global__ void __launch_bounds__(256, 3) k_ec_decompress_wire(const uint8_t *__restrict__ blobs, const u64 *__restrict__ off, u32 k, u32 n_proofs, u64 first,
-                                                               u32 max_len, u32 *__restrict__ out, unsigned long long *bad) {
+                                                               u32 max_len, u32 *__restrict__ out, unsigned long long *bad, uint8_t *flag) {
   const u32 per = 6 + 2 * k;
   const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_proofs * per) return;
@@ -757,10 +758,10 @@ __global__ void __launch_bounds__(256, 3) k_ec_decompress_wire(const uint8_t *__
   if (len >= pts_at + 33ull * per + 2 && len <= max_len && blob[0] == 'B' && blob[1] == 'P' && blob[2] == 'R' && blob[3] == 'P' && blob[5] == k) {
     if (blob[4] == '1' || blob[4] == '2') {
       const bool valid = ec_decompress_one(blob + pts_at + 33 * t, w16);
-      if (!valid) atomicMin(bad, (unsigned long long)(first + g));
+      if (!valid) { atomicMin(bad, (unsigned long long)(first + g)); if (flag) flag[g] = 1; }
     } else if (blob[4] == '3' && len >= pts_at + 33ull * per + 132 + 32ull * per) {
       const bool valid = ec_hinted_one(blob + pts_at + 33 * t, blob + (len - 32ull * per) + 32 * t, w16);
-      if (!valid) atomicMin(bad, (unsigned long long)(first + g));
+      if (!valid) { atomicMin(bad, (unsigned long long)(first + g)); if (flag) flag[g] = 1; }
     }
   }
   store_words16(out + 16ull * i, w16);

@@ -1144,4 +1144,99 @@ __global__ void __launch_bounds__(256) k_rp_shared_scalars(const u32 *__restrict
   ::store_words8(out + 8ull * i, v.v);
 }
 
+// ---- per-proof verdicts and per-GROUP sums (bpmi_rp_batch_group_values_dev) -----------------------------------------------------------
+// After the two lanes have joined: verdict[g] = bit 0: a role of k_rp_roles failed | bit 1: a point encoding is invalid (`pt_flag`,
+// k_ec_decompress_wire).  A flagged proof takes part in no group: the scalars of its V_j and of its points are zeroed here, its decoded
+// points overwritten with the identity (64 zero bytes), and k_rp_group_colsum skips its cells -- by the verdict, not by content: a proof
+// whose role 0 or 1 failed has cells like any other.  One thread per (proof, item), items = the m commitments and the 6 + 2k points; all
+// pointers are the whole batch's, [first, first + cnt) are the proofs of this row chunk.
+struct VerdictArgs {
+  const uint8_t *role_status;      // [role * Pall + g]
+  const uint8_t *pt_flag;          // [g]
+  uint8_t *verdict;                // [g]
+  u32 Pall, first, cnt, m, per;
+  int only_role;                   // >= 0: a profiling run -- the roles that did not run report success, so every proof is flagged
+  u32 *v_scalars, *pt_scalars, *points;
+};
+__global__ void __launch_bounds__(256) k_rp_verdict(VerdictArgs a) {
+  const u32 items = a.m + a.per;
+  const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+  if (i >= (u64)a.cnt * items) return;
+  const u32 g = a.first + (u32)(i / items), j = (u32)(i % items);
+  u32 passed = 1;
+#pragma unroll
+  for (int r = 0; r < RP_ROLES; r++) passed &= a.role_status[(size_t)r * a.Pall + g];
+  const u32 v = ((passed && a.only_role < 0) ? 0u : 1u) | (a.pt_flag[g] ? 2u : 0u);
+  if (j == 0) a.verdict[g] = (uint8_t)v;
+  if (!v) return;
+  const uint4 z = make_uint4(0, 0, 0, 0);
+  if (j < a.m) {
+    uint4 *p = reinterpret_cast<uint4 *>(a.v_scalars + 8 * ((size_t)g * a.m + j));
+    p[0] = z; p[1] = z;
+  } else {
+    const size_t t = (size_t)g * a.per + (j - a.m);
+    uint4 *p = reinterpret_cast<uint4 *>(a.pt_scalars + 8 * t), *q = reinterpret_cast<uint4 *>(a.points + 16 * t);
+    p[0] = z; p[1] = z;
+    q[0] = z; q[1] = z; q[2] = z; q[3] = z;
+  }
+}
+
+// gsum[t][col] += sum of cell (col, g) over the unflagged proofs g of group t inside this row chunk (proofs [first, first + cnt) of the
+// batch; group t = proofs [t group, (t + 1) group), so a group may straddle two chunks: the sums accumulate as k_rp_colsum's do).  `lpg`
+// lanes (a power of two <= 64) share a group; a wave covers 64 / lpg groups [t0 + ..) of one column.  Limb rows are summed as plain
+// 64-bit integers and reduced once, as in k_rp_colsum.
+__global__ void __launch_bounds__(64) k_rp_group_colsum(const u32 *__restrict__ contrib, u32 cnt, u32 first, const uint8_t *__restrict__ verdict, u32 group,
+                                                        u32 t0, u32 nt, u32 lpg, u32 ncols, u32 *__restrict__ gsum) {
+  const u32 gpb = 64u / lpg, nblk = (nt + gpb - 1u) / gpb;
+  const u32 col = blockIdx.x / nblk, tl = (blockIdx.x % nblk) * gpb + threadIdx.x / lpg, sub = threadIdx.x % lpg;
+  const u32 t = t0 + tl;
+  u64 acc[9];
+#pragma unroll
+  for (int w = 0; w < 9; w++) acc[w] = 0;
+  if (tl < nt) {
+    const u64 lo64 = (u64)t * group, hi64 = lo64 + group;
+    const u32 lo = (u32)(lo64 > first ? lo64 : first), hi = (u32)(hi64 < (u64)first + cnt ? hi64 : (u64)first + cnt);
+    const u32 *base = contrib + (size_t)col * 9 * cnt;
+    for (u32 g = lo + sub; g < hi; g += lpg) {
+      if (verdict[g]) continue;
+#pragma unroll
+      for (int w = 0; w < 9; w++) acc[w] += base[(size_t)w * cnt + (g - first)];
+    }
+  }
+  for (u32 d = 1; d < lpg; d <<= 1) {
+#pragma unroll
+    for (int w = 0; w < 9; w++) acc[w] += __shfl_xor(acc[w], (int)d);
+  }
+  if (tl < nt && sub == 0) {
+    sq total;
+    bpmi::sq_norm_cols(total, acc);
+    sc sum, cur;
+    bpmi::sq_to_sc(sum, total);
+    u32 *dst = gsum + 8 * ((size_t)t * ncols + col);
+    ::load_words8(cur.v, dst);
+    bpmi::sc_add(cur, cur, sum);
+    ::store_words8(dst, cur.v);
+  }
+}
+
+// out[t][0 .. 3 + 2n): the scalars of g, h, u, gs_i, hs_i of group t's MSM from its 5 + 2n summed columns (k_rp_shared_scalars per group)
+__global__ void __launch_bounds__(256) k_rp_group_scalars(const u32 *__restrict__ gsum, u32 n, u32 ngroups, u32 *__restrict__ out) {
+  const u32 ns = 3 + 2 * n;
+  const u64 idx = (u64)blockIdx.x * 256u + threadIdx.x;
+  if (idx >= (u64)ngroups * ns) return;
+  const u32 t = (u32)(idx / ns), i = (u32)(idx % ns);
+  const u32 *row = gsum + 8 * (size_t)t * (5 + 2 * n);
+  sc v;
+  if (i < 3) {
+    ::load_words8(v.v, row + 8ull * i);
+  } else {
+    const u32 j = i - 3, side = j >= n ? 1u : 0u;
+    sc a, b;
+    ::load_words8(a.v, row + 8ull * (5 + j));
+    ::load_words8(b.v, row + 8ull * (3 + side));
+    bpmi::sc_add(v, a, b);
+  }
+  ::store_words8(out + 8 * idx, v.v);
+}
+
 }  // namespace rpd

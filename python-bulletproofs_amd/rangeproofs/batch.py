@@ -429,20 +429,14 @@ class BatchRangeVerifier:
         self._dev_chunks.append((d_pts, d_scs, nv + npts))
         self._absorb_shared(shared.raw, count)
 
-    def partial_wire(self, Vs, blobs, offsets=None):
-        """The 64-byte value of ONE batch of wire proofs, everything in one native call (bpmi_rp_batch_verify_dev): upload in
-        slices with the point decoding beside it, GPU preparation, the shared coefficients folded on the device, one MSM -- no
-        host round trip between the preparation and the MSM and no Python loop over anything.  Stand-alone: nothing is added to
-        this verifier's accumulators (a verifier that also holds proofs added otherwise folds the two values with ec_sum).
-        Vs / blobs / offsets as for add_wire_native (commitments packed -- bytes or a page-locked HostBuffer --, or Points / lists of
-        Points).  Raises
-        Exception("Proof invalid") when a proof fails its byte-level checks or has an invalid point; the MSM's verdict is the
-        returned value (64 zero bytes = valid)."""
+    def _wire_call(self, what, Vs, blobs, offsets):
+        """The arguments partial_wire and group_values_wire hand to their native call, from every form of Vs / blobs / offsets they
+        take: (eng, count, m, src, nbytes, offs, weights, seed, vbytes, d_points, d_scalars), or None for an empty batch."""
         import ctypes
         import os
         from itertools import accumulate
         if self._msm is not None:
-            raise ValueError("partial_wire needs the default engine (no custom msm)")
+            raise ValueError("%s needs the default engine (no custom msm)" % what)
         if offsets is None:
             count = len(blobs)
             offsets = [0, *accumulate(map(len, blobs))]
@@ -454,7 +448,7 @@ class BatchRangeVerifier:
             if count < 0 or offsets[0] < 0 or (count > 0 and not (0 <= offsets[count] <= total)):
                 raise ValueError("offsets must be non-decreasing positions inside the %d-byte proof buffer" % total)
         if not count:
-            return _ZERO64
+            return None
         k = self.n.bit_length() - 1
         if hasattr(Vs, "ptr") and hasattr(Vs, "nbytes"):           # a page-locked HostBuffer (engine.host_alloc): uploaded without a staging copy
             vbytes, vlen = Vs.ptr, Vs.nbytes
@@ -502,13 +496,100 @@ class BatchRangeVerifier:
                 src = ctypes.addressof((ctypes.c_char * nbytes).from_buffer(joined))
             except TypeError:
                 src = bytes(joined)
+        return eng, count, m, src, nbytes, offs, weights, seed, vbytes, bufs[1], bufs[2]
+
+    def partial_wire(self, Vs, blobs, offsets=None):
+        """The 64-byte value of ONE batch of wire proofs, everything in one native call (bpmi_rp_batch_verify_dev): upload in
+        slices with the point decoding beside it, GPU preparation, the shared coefficients folded on the device, one MSM -- no
+        host round trip between the preparation and the MSM and no Python loop over anything.  Stand-alone: nothing is added to
+        this verifier's accumulators (a verifier that also holds proofs added otherwise folds the two values with ec_sum).
+        Vs / blobs / offsets as for add_wire_native (commitments packed -- bytes or a page-locked HostBuffer --, or Points / lists of
+        Points).  Raises
+        Exception("Proof invalid") when a proof fails its byte-level checks or has an invalid point; the MSM's verdict is the
+        returned value (64 zero bytes = valid)."""
+        import ctypes
+        args = self._wire_call("partial_wire", Vs, blobs, offsets)
+        if args is None:
+            return _ZERO64
+        eng, count, m, src, nbytes, offs, weights, seed, vbytes, d_pts, d_scs = args
         out = ctypes.create_string_buffer(64)
         bad = ctypes.c_int64(-1)
         eng._ck(eng.lib.bpmi_rp_batch_verify_dev(eng.ctx, self.n, m, count, src, nbytes, ctypes.cast(offs, ctypes.c_void_p), weights, seed, vbytes,
-                                                 self._d_shared_pts.ptr, bufs[1].ptr, bufs[2].ptr, out, ctypes.cast(ctypes.pointer(bad), ctypes.c_void_p)))
+                                                 self._d_shared_pts.ptr, d_pts.ptr, d_scs.ptr, out, ctypes.cast(ctypes.pointer(bad), ctypes.c_void_p)))
         if bad.value >= 0:
             raise Exception("Proof invalid")
         return out.raw
+
+    def group_values_wire(self, Vs, blobs, offsets=None, group=1):
+        """partial_wire per GROUP of `group` consecutive proofs, in one native call (bpmi_rp_batch_group_values_dev: one
+        preparation, the groups' MSMs in one launch): (values, status) -- values[t] = the 64-byte value of the combination of
+        the proofs [t * group, (t + 1) * group) that are not flagged (64 zero bytes = all of them verify), status[i] = bit 0: proof i
+        fails a byte-level check, bit 1: it has an invalid point encoding (a flagged proof takes part in no group).  Never raises
+        "Proof invalid": the verdicts are the result.  Vs / blobs / offsets as for partial_wire; stand-alone like it."""
+        import ctypes
+        group = int(group)
+        if group < 0:
+            raise ValueError("group must be at least 1")
+        args = self._wire_call("group_values_wire", Vs, blobs, offsets)
+        if args is None:
+            return [], b""
+        eng, count, m, src, nbytes, offs, weights, seed, vbytes, d_pts, d_scs = args
+        per = max(1, min(group, count))              # (group = 0 is the native call's argument error)
+        ngroups = (count + per - 1) // per
+        values = ctypes.create_string_buffer(64 * ngroups)
+        status = ctypes.create_string_buffer(count)
+        eng._ck(eng.lib.bpmi_rp_batch_group_values_dev(eng.ctx, self.n, m, count, src, nbytes, ctypes.cast(offs, ctypes.c_void_p), weights, seed, vbytes,
+                                                       self._d_shared_pts.ptr, d_pts.ptr, d_scs.ptr, group, ctypes.cast(values, ctypes.c_void_p),
+                                                       ctypes.cast(status, ctypes.c_void_p)))
+        raw = values.raw
+        return [raw[64 * t: 64 * t + 64] for t in range(ngroups)], status.raw
+
+    def default_group(self, m=1):
+        """The group size locate_wire starts with: the largest power of two for which a group's MSM fits the one-launch kernel,
+        3 + 2 n + group * (m + 6 + 2 log2 n) <= 8448 pairs (MID_NMAX, csrc/msm_kernels.hpp) -- 256 for 64-bit single proofs."""
+        per_proof = m + 6 + 2 * (self.n.bit_length() - 1)
+        fit = (LOCATE_MAX_PAIRS - 3 - 2 * self.n) // per_proof
+        return 1 << (fit.bit_length() - 1) if fit >= 1 else 1
+
+    def locate_wire(self, Vs, blobs, offsets=None, group=None):
+        """The sorted indices of every invalid proof of a batch of wire proofs, [] for a valid batch; never raises "Proof invalid".
+        Level 1: one group_values_wire call with `group` (default: default_group(m) -- the largest power of two with
+        3 + 2 n + group * (m + 6 + 2 log2 n) <= 8448, the pairs one launch of the group kernel holds).  Level 2: one call with
+        group = 1 over the unflagged proofs of the groups whose value is not the identity.  Result: the proofs flagged at level 1 and
+        the proofs with a non-identity value at level 2 (locate_plan).  Vs / blobs / offsets as for partial_wire."""
+        count = len(blobs) if offsets is None else len(offsets) - 1
+        if count <= 0:
+            return []
+        if hasattr(Vs, "ptr") and hasattr(Vs, "nbytes"):
+            packed = Vs.view
+        elif isinstance(Vs, (bytes, bytearray, memoryview)):
+            packed = Vs
+        else:
+            packed = None
+        if packed is not None:
+            m = len(packed) // (64 * count)
+            if m < 1 or len(packed) != 64 * count * m or self.n % m:
+                raise Exception("Proof invalid")
+        else:
+            m = len(Vs[0]) if isinstance(Vs[0], (list, tuple)) else 1
+
+        def commitments(i):
+            if packed is not None:
+                return bytes(packed[64 * m * i: 64 * m * (i + 1)])
+            return b"".join(V.to_le64() for V in Vs[i]) if isinstance(Vs[i], (list, tuple)) else Vs[i].to_le64()
+
+        def proof(i):
+            if offsets is None:
+                return bytes(blobs[i])
+            buf = blobs.view if hasattr(blobs, "ptr") else blobs
+            return bytes(buf[offsets[i]: offsets[i + 1]])
+
+        def group_values(indices, grp):
+            if indices is None:
+                return self.group_values_wire(Vs, blobs, offsets, group=grp)
+            return self.group_values_wire(b"".join(commitments(i) for i in indices), [proof(i) for i in indices], group=grp)
+
+        return locate_plan(count, self.default_group(m) if group is None else int(group), group_values)
 
     def verify_wire(self, Vs, blobs, offsets=None, sharded=None):
         """True if every proof of this batch of wire proofs is valid; raises Exception("Proof invalid") otherwise (partial_wire +
@@ -595,6 +676,35 @@ class BatchRangeVerifier:
         if part != _ZERO64:
             raise Exception("Proof invalid")
         return True
+
+
+LOCATE_MAX_PAIRS = 8448          # MID_NMAX (csrc/msm_kernels.hpp): the pairs of one group's MSM in the one-launch group kernel
+
+
+def locate_plan(count, group, group_values):
+    """The two levels of BatchRangeVerifier.locate_wire, free of any GPU: group_values(indices, group) -> (values, status) is
+    group_values_wire over the sub-batch `indices` (a list of batch indices in ascending order; None = the whole batch).
+    Level 1 is group_values(None, group); level 2 -- only when some group's value is not the identity -- is ONE call
+    group_values(sub, 1) over the unflagged proofs of those groups (a flagged proof is already located and takes part in no value).
+    Returns the sorted indices of the proofs flagged at level 1 or with a non-identity value at level 2."""
+    if count <= 0:
+        return []
+    if group < 1:
+        raise ValueError("group must be at least 1")
+    group = min(group, count)
+    values, status = group_values(None, group)
+    if len(status) != count or len(values) != (count + group - 1) // group:
+        raise ValueError("group_values returned %d values and %d status bytes for %d proofs in groups of %d" % (len(values), len(status), count, group))
+    bad = [i for i in range(count) if status[i]]
+    sub = [i for t, v in enumerate(values) if v != _ZERO64 for i in range(t * group, min((t + 1) * group, count)) if not status[i]]
+    if sub and group == 1:                 # level 1 was already one proof per group
+        bad += sub
+    elif sub:
+        values2, status2 = group_values(sub, 1)
+        if len(values2) != len(sub) or len(status2) != len(sub):
+            raise ValueError("group_values returned %d values for a sub-batch of %d proofs" % (len(values2), len(sub)))
+        bad += [i for i, v, st in zip(sub, values2, status2) if v != _ZERO64 or st]
+    return sorted(bad)
 
 
 def batch_verify(Vs, proofs, g, h, gs, hs, u, **kw):
