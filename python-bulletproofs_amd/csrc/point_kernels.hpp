@@ -133,27 +133,7 @@ struct Sc2 { u32 k1[8]; u32 k2[8]; };
 // Non-adjacent forms of the two shared scalars, computed once on the host: bit i of nz*
 // says digit i is non-zero, bit i of sg* says it is -1.  257 positions each.
 struct NafPair { u32 nz1[9], sg1[9], nz2[9], sg2[9]; int top; };
-static void host_naf(const uint8_t k32[32], u32 nz[9], u32 sg[9], int &top) {
-  u32 w[9];
-  memcpy(w, k32, 32);
-  w[8] = 0;
-  for (int i = 0; i < 9; i++) nz[i] = sg[i] = 0;
-  for (int pos = 0; pos < 257; pos++) {
-    if (w[0] & 1u) {
-      const bool minus = (w[0] & 3u) == 3u;          // k mod 4 == 3 -> digit -1, k += 1
-      nz[pos >> 5] |= 1u << (pos & 31);
-      if (minus) {
-        sg[pos >> 5] |= 1u << (pos & 31);
-        for (int i = 0; i < 9; i++) { if (++w[i] != 0) break; }
-      } else {
-        w[0] &= ~1u;
-      }
-      if (pos > top) top = pos;
-    }
-    for (int i = 0; i < 8; i++) w[i] = (w[i] >> 1) | (w[i + 1] << 31);
-    w[8] >>= 1;
-  }
-}
+// (host_naf, which fills them: fold_ops_host.hpp)
 
 // out[i] = k1 * P1_i + k2 * P2_i with k1, k2 shared by all i (the generator fold,
 // inner_product_prover.py:107-108).  Jacobian ladder driven by the NAF digits: every
@@ -348,9 +328,7 @@ __global__ void __launch_bounds__(256) k_ec_sum_strided(const u32 *__restrict__ 
 // + ~172 mixed additions, against 126 + 88 PER TERM on the per-lane product path (k_ec_mul_batch_glv) -- and leaves an XYZZ
 // partial; k_ec_sum_partials adds the K / 2 partials of an output and makes it affine.
 //   2 x 2^16 bases -> 2 x 4 096 generators: 0.9 ms against 1.5 (profiles/r04_C3_product_fold_shared_scalars.txt)
-#define GLVF_MAXK 32
-#define GLVF_TERMS 2
-struct GlvFoldK { u32 nz[2][2 * GLVF_MAXK][5]; u32 sg[2][2 * GLVF_MAXK][5]; int top; };      // [side][2 t + half][160 bits]
+// (GlvFoldK, GLVF_MAXK, GLVF_TERMS and the table's builder: fold_ops_host.hpp)
 __global__ void __launch_bounds__(256, 2) k_ec_fold_glv(const u32 *__restrict__ base_a, const u32 *__restrict__ base_b, u32 m, u32 K,
                                                         const GlvFoldK *__restrict__ dk, u32 *__restrict__ partial) {
   const u32 G = K / GLVF_TERMS;
@@ -410,8 +388,7 @@ __global__ void __launch_bounds__(256) k_ec_sum_partials(const u32 *__restrict__
 
 // materialise 2^d-way folded generators: out[i] = sum_t coef[t] * G[i + t*m], i < m, as an
 // interleaved NAF ladder (shared scalars -> wave-uniform branches); two jobs (g and h) per launch
-#define MULTIFOLD_MAXK 16
-struct NafK { u32 nz[MULTIFOLD_MAXK][9]; u32 sg[MULTIFOLD_MAXK][9]; int top; };
+// (NafK, MULTIFOLD_MAXK and the table's builder: fold_ops_host.hpp)
 struct MultifoldJob { const u32 *base; u32 *out; };
 __global__ void __launch_bounds__(256, 3) k_ec_multifold(MultifoldJob ja, MultifoldJob jb, const NafK *__restrict__ nfa, const NafK *__restrict__ nfb,
                                                          u32 m, u32 K) {
@@ -532,8 +509,7 @@ template <int PER> __global__ void __launch_bounds__(256, 3) k_ec_odd_multiples(
     }
   }
 }
-// digits of the K (<= 16) shared scalars, width-4 NAF: dg[t][pos] in {0, +-1, +-3, +-5, +-7}, pos <= top
-struct WnafK { signed char dg[MULTIFOLD_MAXK][264]; int top; };
+// the width-4 NAF digits of the K (<= 16) shared scalars come in a WnafK (fold_ops_host.hpp, with its builder)
 __global__ void __launch_bounds__(256, 3) k_ec_multifold_w4(MultifoldJob ja, MultifoldJob jb, const u32 *__restrict__ tab_a, const u32 *__restrict__ tab_b,
                                                             const WnafK *__restrict__ wa, const WnafK *__restrict__ wb, u32 m, u32 K) {
   u32 i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -583,7 +559,7 @@ __global__ void __launch_bounds__(256, 3) k_ec_multifold_w4(MultifoldJob ja, Mul
 // add (-)(j-th odd multiple) of (lambda?) point row / 2".  The kernel fetches the point of operation q + 1 before it computes
 // operation q: 2^17 outputs are 2 048 waves -- two per SIMD, too few to hide a load behind the other waves' arithmetic.
 //   op = n_dbl | row << 8 | j << 13 | neg << 16          tail = doublings after the last addition
-// (WnafG and its builder: fold_ops_host.hpp)
+// (WnafG and its builder, like the tables of the other fold kernels: fold_ops_host.hpp)
 __device__ __forceinline__ void multifold_fetch(affine &P, u32 op, u32 i, u32 m, u32 npts, const u32 *base, const u32 *tab, const u32 *tabx) {
   const u32 r = (op >> 8) & 31u, j = (op >> 13) & 7u, k = i + (r >> 1) * m;      // j = 0: P, 1: 3P, 2: 5P, 3: 7P
   const bool lam = (r & 1u) != 0u;                                               // wave-uniform: the half that multiplies lambda (jP)

@@ -120,6 +120,43 @@ int t_glv_fold_ops(const uint8_t *coef, uint32_t K, uint32_t *ops, uint32_t *tai
   *tail = hw.tail;
   return (int)hw.nops;
 }
+// The digit tables of the other fold kernels for K coefficients (32 bytes LE each, < q), handed back as flat arrays.  Each builder
+// writes into ONE table that lives across calls, so it holds the previous call's digits; fill >= 0 sets every byte of it to `fill` first.
+static bool load_coefs(sc *c, const uint8_t *coef, uint32_t K, uint32_t maxk) {
+  if (K > maxk) return false;
+  for (uint32_t t = 0; t < K; t++) memcpy(c[t].v, coef + 32 * t, 32);
+  return true;
+}
+// nz, sg: u32[MULTIFOLD_MAXK][9]; returns top, -2 for K above the maximum
+int t_naf_fold_table(const uint8_t *coef, uint32_t K, int fill, uint32_t *nz, uint32_t *sg) {
+  static NafK nf;
+  sc c[MULTIFOLD_MAXK];
+  if (!load_coefs(c, coef, K, MULTIFOLD_MAXK)) return -2;
+  if (fill >= 0) memset(&nf, fill, sizeof(nf));
+  naf_fold_table(nf, c, K);
+  memcpy(nz, nf.nz, sizeof(nf.nz)); memcpy(sg, nf.sg, sizeof(nf.sg));
+  return nf.top;
+}
+// dg: int8[MULTIFOLD_MAXK][264]
+int t_wnaf_fold_table(const uint8_t *coef, uint32_t K, int fill, signed char *dg) {
+  static WnafK w;
+  sc c[MULTIFOLD_MAXK];
+  if (!load_coefs(c, coef, K, MULTIFOLD_MAXK)) return -2;
+  if (fill >= 0) memset(&w, fill, sizeof(w));
+  wnaf_fold_table(w, c, K);
+  memcpy(dg, w.dg, sizeof(w.dg));
+  return w.top;
+}
+// nz, sg: u32[2][2 * GLVF_MAXK][5], side 0 from coef_g, side 1 from coef_h
+int t_glv_fold_table(const uint8_t *coef_g, const uint8_t *coef_h, uint32_t K, int fill, uint32_t *nz, uint32_t *sg) {
+  static GlvFoldK hk;
+  sc cg[GLVF_MAXK], ch[GLVF_MAXK];
+  if (!load_coefs(cg, coef_g, K, GLVF_MAXK) || !load_coefs(ch, coef_h, K, GLVF_MAXK)) return -2;
+  if (fill >= 0) memset(&hk, fill, sizeof(hk));
+  glv_fold_table(hk, cg, ch, K);
+  memcpy(nz, hk.nz, sizeof(hk.nz)); memcpy(sg, hk.sg, sizeof(hk.sg));
+  return hk.top;
+}
 // SHA-256 compression of one block from the given state: which = 0 the portable code, 1 the CPU's SHA extensions (returns 0 and
 // leaves the state alone when the CPU has none), 2 whatever the library dispatches to
 int t_sha_block(int which, uint32_t *state, const uint8_t *block) {

@@ -589,6 +589,126 @@ def test_glv_fold_operation_list_spells_the_coefficients(shim):
     assert shim.t_glv_fold_ops(bytes(32 * 17), 17, (ctypes.c_uint32 * 2048)(), ctypes.byref(ctypes.c_uint32())) == -1
 
 
+LAMBDA = 0x5363AD4CC05C30E0A5261C028812645A122E22EA20816678DF02967C1B23BD72
+
+
+def fold_table_groups(K):
+    """The coefficients every digit-table builder is tried on, in groups of K (the last group filled up from the front of the list), and
+    one group of zeros at the end (top must come back to -1 after tables that had digits)."""
+    q = secp256k1.q
+    rnd = random.Random(53)
+    vals = [0, 1, 2, 3, q - 1, q - 2, (1 << 128) - 1, 1 << 128, LAMBDA, int("55" * 32, 16), int("AA" * 32, 16)]
+    assert all(v < q for v in vals)
+    vals += [rnd.randrange(q) for _ in range(64)]
+    vals += vals[:-len(vals) % K]
+    return [vals[i:i + K] for i in range(0, len(vals), K)] + [[0] * K]
+
+
+def le32(coefs):
+    return b"".join(c.to_bytes(32, "little") for c in coefs)
+
+
+def mask_rows(flat, rows, words):
+    """rows x words u32 (little-endian words) -> one Python integer per row"""
+    return [sum(flat[r * words + w] << (32 * w) for w in range(words)) for r in range(rows)]
+
+
+def naf_value(nz, sg):
+    """bit i of nz: digit i is non-zero, bit i of sg: it is -1"""
+    assert sg & ~nz == 0
+    assert nz & (nz >> 1) == 0, "two adjacent non-zero digits"
+    return nz - 2 * sg
+
+
+def built_three_ways(build, group):
+    """The builder's output for `group` into a table that holds the previous call's digits, into one filled with 0xA5 bytes and into a
+    zeroed one: the same each time."""
+    after_another, dirty, clean = build(group, -1), build(group, 0xA5), build(group, 0)
+    assert after_another == clean and dirty == clean
+    return clean
+
+
+@pytest.mark.parametrize("K", [1, 2, 16])
+def test_naf_fold_table_spells_the_coefficients(shim, K):
+    """csrc/fold_ops_host.hpp naf_fold_table (the digit table of k_ec_multifold): row t, read as sum digit 2^pos, is coefficient t; no two
+    adjacent non-zero digits; sg is a subset of nz; the rows from K on are zero whatever the table held before; top is the highest
+    non-zero position of any row, -1 if there is none."""
+    shim.t_naf_fold_table.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    shim.t_naf_fold_table.restype = ctypes.c_int
+
+    def build(coefs, fill):
+        nz, sg = (ctypes.c_uint32 * (16 * 9))(), (ctypes.c_uint32 * (16 * 9))()
+        top = shim.t_naf_fold_table(le32(coefs), len(coefs), fill, nz, sg)
+        return top, mask_rows(nz, 16, 9), mask_rows(sg, 16, 9)
+
+    for group in fold_table_groups(K):
+        top, nz, sg = built_three_ways(build, group)
+        for t, c in enumerate(group):
+            assert naf_value(nz[t], sg[t]) == c, (K, t, hex(c))
+        assert not any(nz[K:]) and not any(sg[K:])
+        assert top == max(v.bit_length() for v in nz) - 1
+    assert top == -1                                            # the last group is all zeros
+    assert shim.t_naf_fold_table(bytes(32 * 17), 17, 0, None, None) == -2
+
+
+@pytest.mark.parametrize("K", [1, 2, 16])
+def test_wnaf_fold_table_spells_the_coefficients(shim, K):
+    """csrc/fold_ops_host.hpp wnaf_fold_table (the digit table of k_ec_multifold_w4): every digit is 0 or odd with magnitude <= 7, at
+    most one of any four consecutive positions is non-zero, row t read as sum digit 2^pos is coefficient t; top and the unused rows as
+    for naf_fold_table."""
+    shim.t_wnaf_fold_table.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p]
+    shim.t_wnaf_fold_table.restype = ctypes.c_int
+
+    def build(coefs, fill):
+        dg = (ctypes.c_byte * (16 * 264))()
+        top = shim.t_wnaf_fold_table(le32(coefs), len(coefs), fill, dg)
+        return top, [list(dg[264 * t:264 * (t + 1)]) for t in range(16)]
+
+    for group in fold_table_groups(K):
+        top, rows = built_three_ways(build, group)
+        for t, c in enumerate(group):
+            row = rows[t]
+            assert all(d in (0, 1, -1, 3, -3, 5, -5, 7, -7) for d in row)
+            used = [pos for pos, d in enumerate(row) if d]
+            assert all(b - a >= 4 for a, b in zip(used, used[1:]))
+            assert sum(d << pos for pos, d in enumerate(row)) == c, (K, t, hex(c))
+        assert not any(any(row) for row in rows[K:])
+        assert top == max([pos for row in rows for pos, d in enumerate(row) if d], default=-1)
+    assert top == -1
+    assert shim.t_wnaf_fold_table(bytes(32 * 17), 17, 0, None) == -2
+
+
+@pytest.mark.parametrize("K", [2, 16, 32])
+def test_glv_fold_table_spells_the_coefficients_on_both_sides(shim, K):
+    """csrc/fold_ops_host.hpp glv_fold_table (the digit table of k_ec_fold_glv): on side 0 (the g coefficients) and side 1 (the h
+    coefficients, a different table here, so neither leaks into the other) rows 2 t and 2 t + 1, read as sum digit 2^pos, give
+    coefficient t as row(2 t) + lambda row(2 t + 1) mod q -- a negative half carries its sign in its digits; each half is
+    non-adjacent and fits the 160 bits the struct holds (its value is below 2^129, so no digit was cut off); top and the unused
+    rows as for naf_fold_table."""
+    q = secp256k1.q
+    shim.t_glv_fold_table.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    shim.t_glv_fold_table.restype = ctypes.c_int
+
+    def build(both, fill):
+        nz, sg = (ctypes.c_uint32 * (2 * 64 * 5))(), (ctypes.c_uint32 * (2 * 64 * 5))()
+        top = shim.t_glv_fold_table(le32(both[0]), le32(both[1]), K, fill, nz, sg)
+        return top, mask_rows(nz, 128, 5), mask_rows(sg, 128, 5)
+
+    groups = fold_table_groups(K)
+    for i, group in enumerate(groups):
+        both = (group, groups[(i + 1) % len(groups)] if i + 1 < len(groups) else group)
+        top, nz, sg = built_three_ways(build, both)
+        for side in range(2):
+            rows = [naf_value(nz[64 * side + r], sg[64 * side + r]) for r in range(64)]
+            for t, c in enumerate(both[side]):
+                assert abs(rows[2 * t]) < 1 << 129 and abs(rows[2 * t + 1]) < 1 << 129
+                assert (rows[2 * t] + LAMBDA * rows[2 * t + 1] - c) % q == 0, (K, side, t, hex(c))
+            assert not any(nz[64 * side + 2 * K:64 * (side + 1)]) and not any(sg[64 * side + 2 * K:64 * (side + 1)])
+        assert top == max(v.bit_length() for v in nz) - 1 and top < 160
+    assert top == -1
+    assert shim.t_glv_fold_table(bytes(32 * 33), bytes(32 * 33), 33, 0, None, None) == -2
+
+
 
 def test_sha_block_on_cpu_extensions_equals_the_portable_one(shim):
     """csrc/rp_batch_host.hpp: the SHA-256 compression function on the host CPU's SHA extensions (round 4; chosen at run time) against

@@ -31,5 +31,5 @@ def test_transcript_export_refuses_a_short_buffer_through_the_abi():
     exact-size heap blocks; here the contract is stated once more as a plain test of the header's text)."""
     text = open(os.path.join(INC, "transcript_host.hpp")).read()
     assert "if (dg.size() > cap) return false;" in text
-    bpmi = open(os.path.join(INC, "bpmi.hip")).read()
-    assert 'if (!rpt::export_digest(dg, digest_out, cap, out_len)) return fail(ctx, BPMI_E_ARG, "digest_out too small");' in bpmi
+    ipa = open(os.path.join(INC, "ipa_host.hpp")).read()
+    assert 'if (!rpt::export_digest(dg, digest_out, cap, out_len)) return fail(ctx, BPMI_E_ARG, "digest_out too small");' in ipa
