@@ -46,6 +46,8 @@ using namespace bpmi;
 
 #define BPMI_VERSION 100
 
+#include "shared_defs.hpp"
+#include "msm_plan_host.hpp"
 #include "context.hpp"
 #include "device_util.hpp"
 #include "msm_kernels.hpp"
@@ -102,10 +104,10 @@ bpmi_ctx *bpmi_ctx_create(int device, void *stream) {
 void bpmi_ctx_destroy(bpmi_ctx *ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
-  (void)hipStreamSynchronize(ctx->stream);
+  (void)sync_lanes(ctx);
   for (auto &e : ctx->evs) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
   for (auto e : ctx->ev_pool) (void)hipEventDestroy(e);
-  if (ctx->ws) (void)hipFree(ctx->ws);
+  for (Lane &l : ctx->lane) { if (l.ws) (void)hipFree(l.ws); if (l.ev_accum) (void)hipEventDestroy(l.ev_accum); if (l.ev_sorted) (void)hipEventDestroy(l.ev_sorted); }
   if (ctx->stage_in) (void)hipFree(ctx->stage_in);
   if (ctx->rp_buf) (void)hipFree(ctx->rp_buf);
   if (ctx->vflag) (void)hipHostFree(ctx->vflag);
@@ -113,17 +115,12 @@ void bpmi_ctx_destroy(bpmi_ctx *ctx) {
   if (ctx->pin) (void)hipHostFree(ctx->pin);
   if (ctx->up_ring) (void)hipHostFree(ctx->up_ring);
   if (ctx->up_ev) (void)hipEventDestroy(ctx->up_ev);
-  if (ctx->stream1) { (void)hipStreamSynchronize(ctx->stream1); (void)hipStreamDestroy(ctx->stream1); }
-  if (ctx->stream2) { (void)hipStreamSynchronize(ctx->stream2); (void)hipStreamDestroy(ctx->stream2); }
+  for (int k = 1; k < BPMI_LANES; k++) if (ctx->lane[k].stream) (void)hipStreamDestroy(ctx->lane[k].stream);
   if (ctx->stream_acc) { (void)hipStreamSynchronize(ctx->stream_acc); (void)hipStreamDestroy(ctx->stream_acc); }
-  for (auto e : ctx->ev_sorted) if (e) (void)hipEventDestroy(e);
-  if (ctx->ws2) (void)hipFree(ctx->ws2);
   if (ctx->fold_tab) (void)hipFree(ctx->fold_tab);
   if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
   if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
   for (auto e : ctx->ev_slice) if (e) (void)hipEventDestroy(e);
-  for (auto e : ctx->ev_accum) if (e) (void)hipEventDestroy(e);
-  if (ctx->ws1) (void)hipFree(ctx->ws1);
   for (auto &pd : ctx->pend) { if (pd.pin) (void)hipHostFree(pd.pin); if (pd.done) (void)hipEventDestroy(pd.done); }
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx->helper;
@@ -312,15 +309,13 @@ int bpmi_msm_geometry(bpmi_ctx *ctx, uint64_t n, int pipelined, uint32_t geom[8]
   if (n == 0) return BPMI_OK;
   Segs s = segs_init();
   s.n[0] = (u32)n; s.total = (u32)n;
-  const uint64_t K = pipelined ? 1 : msm_slice_count(ctx, s);
+  const uint64_t K = pipelined ? 1 : msm_slice_count(*ctx, s);
   const uint64_t per = (n + K - 1) / K;
-  MsmGeom g;
-  bool mid, small, glv;
-  const bool saved = ctx->chain_accum;
-  ctx->chain_accum = pipelined ? ctx->opt_async_lanes != 0 : (K > 1 && per >= (1u << 19));
-  msm_pick_geometry(ctx, per, 0, 0, g, mid, small, glv);
-  ctx->chain_accum = saved;
-  geom[0] = small ? 1u : (mid ? 2u : 0u); geom[1] = g.c; geom[2] = g.W; geom[3] = g.top2; geom[4] = g.G; geom[5] = g.L; geom[6] = (uint32_t)K; geom[7] = (uint32_t)per;
+  MsmMode mode;
+  mode.chained = pipelined ? ctx->opt_async_lanes != 0 : (K > 1 && per >= (1u << 19));
+  const MsmPlan pl = msm_pick_geometry(*ctx, mode, per, 0, 0);
+  const MsmGeom &g = pl.g;
+  geom[0] = pl.small ? 1u : (pl.mid ? 2u : 0u); geom[1] = g.c; geom[2] = g.W; geom[3] = g.top2; geom[4] = g.G; geom[5] = g.L; geom[6] = (uint32_t)K; geom[7] = (uint32_t)per;
   return BPMI_OK;
 }
 // Asynchronous pair: enqueue returns as soon as the MSM's kernels and its device->host copy are queued on
@@ -345,22 +340,21 @@ int bpmi_msm_dev_enqueue(bpmi_ctx *ctx, int slot, const void *d_pts, const void 
     if (rc == BPMI_OK) rc = ensure_lane(ctx, 2);               // (both extra lanes exist from the first burst on: see below)
     if (rc) return rc;
   }
-  if (ctx->opt_async_lanes && !ctx->async_lane1_ordered) {
+  if (ctx->opt_async_lanes && !ctx->async_lanes_ordered) {
     // Order EVERY extra lane after whatever produced the inputs on the ctx stream, once per burst and BEFORE this burst's first MSM
     // is queued (the option's contract: inputs complete before the first enqueue of a burst).  Recorded at a lane's first use
     // instead, the event sits behind slot 0's whole MSM: round 3 found that for lane 1 (a caller that queued a pair and waited for
     // both got them one after the other, profiles/r03_pair_modes.txt), and round 4's lane 2 still did it -- its "three in flight"
     // measurements ran on a partly serialised pipeline (re-measured: profiles/r05_pipeline_depth_ab.txt).
     HIPCHK(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-    HIPCHK(ctx, hipStreamWaitEvent(ctx->stream1, ctx->ev_fork, 0));
-    HIPCHK(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-    ctx->async_lane1_ordered = ctx->async_lane2_ordered = true;
+    HIPCHK(ctx, hipStreamWaitEvent(ctx->lane[1].stream, ctx->ev_fork, 0));
+    HIPCHK(ctx, hipStreamWaitEvent(ctx->lane[2].stream, ctx->ev_fork, 0));
+    ctx->async_lanes_ordered = true;
   }
-  ctx->chain_accum = ctx->opt_async_lanes != 0;
-  ctx->chain_free = ctx->opt_accum_chain == 0;
-  rc = msm_enqueue(ctx, lane, slot, s);
-  ctx->chain_free = false;
-  ctx->chain_accum = false;
+  MsmMode mode;
+  mode.chained = ctx->opt_async_lanes != 0;
+  mode.free_run = ctx->opt_accum_chain == 0;
+  rc = msm_enqueue(ctx, mode, lane, slot, s);
   if (rc == BPMI_OK) { ctx->pend[slot].async = true; ctx->pend[slot].async_empty = (n == 0); }
   return rc;
 }
@@ -369,7 +363,7 @@ int bpmi_msm_finish(bpmi_ctx *ctx, int slot, uint8_t out[64]) {
   if (slot < 0 || slot >= BPMI_LANES) return fail(ctx, BPMI_E_ARG, "slot must be 0, 1 or 2");
   if (!ctx->pend[slot].async) return fail(ctx, BPMI_E_STATE, "no MSM was enqueued in this slot");
   ctx->pend[slot].async = false;
-  if (!ctx->pend[0].async && !ctx->pend[1].async && !ctx->pend[2].async) { ctx->async_lane1_ordered = ctx->async_lane2_ordered = false; ctx->accum_chain_lane = -1; }
+  if (!ctx->pend[0].async && !ctx->pend[1].async && !ctx->pend[2].async) { ctx->async_lanes_ordered = false; ctx->accum_chain_lane = -1; }
   HIPCHK(ctx, hipSetDevice(ctx->device));
   // msm_finish reads an inactive slot as "n was 0" (the identity, which a verifier reads as VALID): only a slot that was enqueued
   // with n = 0 may be inactive here
@@ -456,7 +450,7 @@ int bpmi_ec_mul_batch_dev(bpmi_ctx *ctx, const void *d_pts, const void *d_scalar
   const size_t tab_bytes = align_up(3 * 72 * (size_t)m0, 256), scr_bytes = 144 * 3 * (size_t)ODDMUL_PER_THREAD_MULB * 2 * nthr0;
   int rc = ensure_ws(ctx, tab_bytes + scr_bytes);
   if (rc) return rc;
-  u32 *tab = (u32 *)ctx->ws, *scr = (u32 *)((char *)ctx->ws + tab_bytes);
+  u32 *tab = (u32 *)ctx->lane[0].ws, *scr = (u32 *)((char *)ctx->lane[0].ws + tab_bytes);
   for (uint64_t base = 0; base < n; base += slice) {
     const u32 m = (u32)std::min<uint64_t>(slice, n - base), nthr = (m + ODDMUL_PER_THREAD_MULB - 1) / ODDMUL_PER_THREAD_MULB;
     const u32 *p = (const u32 *)d_pts + 16 * base, *k = (const u32 *)d_scalars + 8 * base;
@@ -714,7 +708,7 @@ int bpmi_sc_dot_dev(bpmi_ctx *ctx, const void *d_a, const void *d_b, uint64_t n,
   HIPCHK(ctx, hipSetDevice(ctx->device));
   int rc = ensure_ws(ctx, 32 * 1024 + 256);
   if (rc) return rc;
-  u32 *partial = (u32 *)ctx->ws, *dout = partial + 8 * 1024;
+  u32 *partial = (u32 *)ctx->lane[0].ws, *dout = partial + 8 * 1024;
   sc_dot_dev_to(ctx, d_a, d_b, n, dout, partial);
   rc = ensure_pin(ctx, 4096);
   if (rc) return rc;
@@ -1079,12 +1073,12 @@ static int rp_prepare_enqueue(bpmi_ctx *ctx, uint32_t n_gens, uint32_t m, uint64
     if (b1 > b0) HIPCHK(ctx, h2d(ctx, din + b0, blobs + b0, b1 - b0, ctx->stream));
     if (ctx->opt_rp_overlap) {
       HIPCHK(ctx, hipEventRecord(ctx->ev_slice[c], ctx->stream));
-      HIPCHK(ctx, hipStreamWaitEvent(ctx->stream1, ctx->ev_slice[c], 0));
-      decode(ctx->stream1, g0, g1);
+      HIPCHK(ctx, hipStreamWaitEvent(ctx->lane[1].stream, ctx->ev_slice[c], 0));
+      decode(ctx->lane[1].stream, g0, g1);
     }
   }
   HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->stream1));
+  HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->lane[1].stream));
   u32 *d_lens = v2 ? (u32 *)((char *)ctx->rp_buf + o_lens) : nullptr;
   if (v2) {
     // the expander writes the format-1 proofs word-major itself; what it does not write must read as zero
@@ -1156,7 +1150,7 @@ static int rp_prepare_enqueue(bpmi_ctx *ctx, uint32_t n_gens, uint32_t m, uint64
 }
 // both lanes idle again; the first error of (rc, the two waits)
 static int rp_wait_lanes(bpmi_ctx *ctx, int rc) {
-  const hipError_t e0 = wait_stream(ctx, ctx->stream), e1 = ctx->stream1 ? wait_stream(ctx, ctx->stream1) : hipSuccess;      // (lane 2 never takes part in a batch)
+  const hipError_t e0 = wait_stream(ctx, ctx->stream), e1 = ctx->lane[1].stream ? wait_stream(ctx, ctx->lane[1].stream) : hipSuccess;      // (lane 2 never takes part in a batch)
   if (rc) return rc;
   HIPCHK(ctx, e0);
   HIPCHK(ctx, e1);

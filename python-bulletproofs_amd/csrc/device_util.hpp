@@ -1,41 +1,13 @@
 // device_util.hpp -- part of libbpmi (included by bpmi.hip; one translation unit).
-// Device-side load/store helpers, the multi-segment input descriptor.
+// Device-side load/store helpers.
 #pragma once
 
 // ------------------------------------------------------------------------------------
 // device helpers
 // ------------------------------------------------------------------------------------
-#define XYZZ_WORDS 36
 #define LDS_STRIDE 37   // odd stride: conflict-free ds_read/ds_write of 36-word records
 
-// up to three (points, scalars) segments presented as one logical array, so that
-// e.g. L = <a_lo, g_hi> + <b_hi, h_lo> + cl*u is ONE MSM without any gather/concat
-// (the reference concatenates Python lists: src/utils/commitments.py:13)
-struct Segs {
-  const u32 *pts[3];
-  const u32 *sc[3];
-  u32 n[3];
-  u32 total;
-  // Optional half-block selection per segment: with hlog[s] = h < 32 the logical element j of
-  // segment s is the physical element ((j >> h) << (h + 1)) | (phase[s] << h) | (j & (2^h - 1)),
-  // i.e. only the lower (phase 0) or upper (phase 1) half of every block of 2^(h+1) elements.
-  // The deferred-fold MSMs of the IPA use it to skip the half of the scalars that is zero by
-  // construction.  hlog[s] >= 32: dense (the default, set by segs_init).
-  u32 hlog[3];
-  u32 phase[3];
-  // GLV (scalar.hpp glv_split; prepared per MSM by k_glv_prepare, csrc/msm_kernels.hpp): when glv_sub is set the MSM runs over
-  // 2 * total VIRTUAL pairs -- virtual pair 2i is (P_i, |k1_i|), 2i + 1 is (lambda P_i, |k2_i|) -- with 128-bit magnitudes
-  // glv_sub[4 v ..] and signs glv_neg[v]; lambda P_i = (beta x_i, y_i), the x coordinates precomputed in glv_bx[8 i ..].
-  const u32 *glv_sub;
-  const unsigned char *glv_neg;
-  const u32 *glv_bx;
-};
-static inline Segs segs_init() {
-  Segs s;
-  memset(&s, 0, sizeof(s));
-  s.hlog[0] = s.hlog[1] = s.hlog[2] = 0xFFu;
-  return s;
-}
+// (XYZZ_WORDS, struct Segs: shared_defs.hpp)
 __device__ __forceinline__ u32 seg_phys(const Segs &s, int k, u32 j) {
   const u32 h = s.hlog[k];
   if (h >= 32u) return j;

@@ -5,25 +5,7 @@
 // ------------------------------------------------------------------------------------
 // MSM kernels
 // ------------------------------------------------------------------------------------
-struct MsmGeom {
-  u32 n;       // pairs (with GLV: virtual pairs = 2 x the caller's)
-  u32 c;       // window bits
-  u32 W;       // windows handled by this launch sequence: [w0, w0 + W) of the recoding
-  u32 w0;      // first window (> 0 when one MSM is split into window groups on two lanes)
-  u32 B;       // buckets per window = 2^(c-1)
-  u32 G;       // W * B
-  u32 L;       // entries per thread in k_accum_l0
-  u32 nv;      // partial sums per window that the bucket reduction hands to the tail (1 or 4)
-  u32 prio;    // mask of the stages (PRIO_*) whose kernels raise their waves' issue priority (see raise_priority)
-  u32 fuse;    // 1: k_accum_l0 folds the partial records of a wave's 64 chunks itself (two records per WAVE go to k_segscan, not two per thread)
-  u32 top2;    // Wb, the number of WIDE windows (round 5): the last Wb of the W windows have c + 1 bits and 2B buckets each, chosen so that
-               // (W - Wb) c + Wb (c + 1) = 256 -- the windows cover exactly the 256 bit positions, the top bit of a folded scalar (< 2^255)
-               // is 0, so the last window's digit never exceeds its 2^c and there is NO carry window and no short one (a window of a few
-               // bits is one partition of n entries for the sort and a handful of giant buckets for the accumulation).  c = 15: 16 + 1
-               // windows; c = 13: 10 + 9; c = 12: 17 + 4.  Keys of window w start at (w + max(0, w - (W - Wb))) B;  G = (W + Wb) B.  0: uniform
-  u32 inblock; // 1 (n <= 2^17): k_fine_sort_part sorts a partition of ANY size itself (a heavy one without the LDS staging buffer);
-               // the two tile kernels for heavy partitions are not launched
-};
+// (MsmGeom, the geometry every kernel takes: msm_plan_host.hpp)
 // Experiment (option "priority", default off; profiles/r03_wave_priority_ab.txt).  The stages around the accumulation are chains
 // of dependent work with few waves; beside the OTHER lane's accumulation (three busy waves on every SIMD) they stretch three- to
 // five-fold (k_digit_final: 66 us alone, 320 us beside k_accum_l0).  Raising their waves' issue priority with s_setprio was
@@ -32,11 +14,7 @@ struct MsmGeom {
 // Round 6: re-measured on the multi-round accumulation (chunks of ~30 entries: the accumulation's wave slots turn over while it runs, so the
 // other lane's kernels are RESIDENT beside it and what they lack is issue slots, not occupancy): the finish of the reduction took 276 + 154 us
 // beside an accumulation instead of 18 + 21 alone, and with the priority raised two MSMs in flight gain 2 % on top of the short chunks' 5.6 %
-// (profiles/r06_wave_priority_and_chunk_ab.txt).  MsmGeom.prio is a mask of the stages that raise it:
-#define PRIO_SORT 1u          // recoding, partition, level B of the sort
-#define PRIO_SCAN 2u          // segmented scan over the partial records
-#define PRIO_SUMS 4u          // stage 1 of the bucket reduction (throughput-bound: 2^20 general additions)
-#define PRIO_FINISH 8u        // the reduction's finish on quads of lanes (latency-bound chains)
+// (profiles/r06_wave_priority_and_chunk_ab.txt).  MsmGeom.prio is a mask of the stages that raise it (PRIO_*, shared_defs.hpp).
 __device__ __forceinline__ void raise_priority(u32 on) { if (on) __builtin_amdgcn_s_setprio(3); }
 // mixed window widths (MsmGeom.top2 = Wb): is window w one of the wide ones, and the first key / partition of window w in units of B / (B >> 8)
 __device__ __forceinline__ u32 geom_wide(const MsmGeom &g, u32 w) { return (g.top2 && w + g.top2 >= g.W) ? 1u : 0u; }
@@ -158,9 +136,7 @@ __global__ void __launch_bounds__(256) k_digits_hist(Segs segs, MsmGeom g, u32 *
 // (window, hi) with LDS histograms -- global atomics only to reserve one range per
 // (tile, partition); level B gives every partition to one block, which counting-sorts it
 // by lo entirely in LDS.  No per-element global atomic anywhere.
-#define PART_MAX 2048          // W * (B / 256) <= 2048 for every c in [10, 16]
-#define COARSE_HIST_WORDS (PART_MAX + 192)     // the partition counts, the any_heavy flag (+0), the tickets of the last-block fusions (+1, +2) and of
-                                               // k_digit_final_spread (+8 .. +8 + 4 W), padded to whole 256-byte lines
+// (at most PART_MAX partitions; COARSE_HIST_WORDS words of counts, flags and tickets: shared_defs.hpp)
 #define FINE_CAP 12288          // entries of a partition that level B sorts in one block's LDS
 // The recoded digits are kept, 16 bits each, window-major: dig16[w * n + i] = (b - 1) | digit sign << 15,
 // DIG_NONE for b = 0 (a negative digit has b <= 2^(c-1) - 1, so that code is free), and one byte
@@ -430,7 +406,6 @@ __global__ void __launch_bounds__(FINE_THREADS) k_fine_sort_part(MsmGeom g, cons
 //                         scatter with LDS cursors
 // Both return at once when no partition is heavy.  The LDS table covers FINE_BINS consecutive
 // buckets from the tile's first one; entries beyond it use a global atomic directly.
-#define FINE_TILE 4096
 #define FINE_BINS 4096
 struct FineTile {
   u32 j0, j1;        // positions covered
@@ -530,8 +505,6 @@ __global__ void __launch_bounds__(256) k_chunk_keys(MsmGeom g, const u32 *__rest
 }
 
 // ---- exclusive scan of hist[0..G) -> off[0..G], cursor[0..G) = off ------------------
-#define SCAN_PER_THREAD 16
-#define SCAN_TILE (256 * SCAN_PER_THREAD)
 __global__ void __launch_bounds__(256) k_scan_partials(const u32 *__restrict__ hist, u32 G, u32 *__restrict__ bsum) {
   __shared__ u32 red[256];
   const u32 base = blockIdx.x * SCAN_TILE + threadIdx.x * SCAN_PER_THREAD;
@@ -875,16 +848,7 @@ __device__ __forceinline__ void block_tree_sum(xyzz &val, u32 *s_val) {
 // arrays of <= 16 sums, which k_digit_final (the second application and the finish in one launch) turns into E[a][0..3].  Every sum belongs to a group of
 // 2^gl_log lanes of one wave: each lane adds its share serially (about 8 elements), then a
 // butterfly of __shfl_xor exchanges folds the group -- no LDS, no block barrier.
-struct DigitJob {
-  u32 in_off, in_stride;     // array a starts at record a * in_stride + in_off of X
-  u32 N, s, type;            // entries, split bits, 0 = D0 (by lo) / 1 = D1 (by hi)
-  u32 glanes, gpw;           // lanes per sum (1 .. 64, any value) and sums per wave = 64 / glanes: a sum never straddles two waves
-  u32 nsums;                 // sums per array: 2^s - 1 (type 0) or N >> s (type 1)
-  u32 out_off, out_stride;   // sum idx (1-based) of array a -> record a * out_stride + out_off + idx - 1 of D
-  u32 blk0;                  // first block of this job
-  u32 cnt;                   // arrays (windows) of this job
-};
-struct DigitJobs { DigitJob j[4]; u32 njobs, prio; };
+// (DigitJob / DigitJobs, the parameters of one launch: msm_plan_host.hpp)
 
 __device__ __forceinline__ void xyzz_shfl_xor(xyzz &r, const xyzz &a, int mask) {
 #pragma unroll
@@ -1347,7 +1311,6 @@ __global__ void __launch_bounds__(1024) k_window_weighted_small_quad(MsmGeom g, 
 // Here window w (8 bits, signed digits) is ONE block: every thread multiplies its point by
 // the digit |d| <= 128 (at most 7 doublings + 7 additions, Jacobian), and the block adds the
 // terms up with shuffle butterflies: depth ~ 12 + log2(n), one or two launches, E[w] to the same tail.
-#define SMALL_C 8
 // grid = (W, S): block (w, s) covers the points i = s * blockDim + tid (+ k * S * blockDim) and
 // writes its partial sum to out[w * S + s]; k_small_combine adds the S partials of a window.
 __device__ __forceinline__ void msm_small_block(const Segs &segs, const MsmGeom &g, u32 *__restrict__ out, u32 *s_val, u32 S) {
@@ -1446,10 +1409,8 @@ __global__ void __launch_bounds__(64) k_small_combine_pair(CombinePair c) {
 //      current distance: two or three steps for uniform digits) leaves the bucket sums in LDS;
 //   5. sum_b b X[b] on quads of lanes (suffix scan + tree, 12 dependent four-lane additions), one XYZZ record out.
 // 37 windows of 7 bits; the two MSMs of a pair are blockIdx.y.  ~0.1 ms for a pair of 4 097-pair MSMs.
-#define MID_C 7
-#define MID_B 64                 // 2^(MID_C - 1)
+#define MID_B 64                 // 2^(MID_C - 1); MID_C and MID_NMAX: shared_defs.hpp
 #define MID_THREADS 512
-#define MID_NMAX 8448            // pairs per MSM: the digit and entry arrays live in LDS (139 KB of the 160 KB a gfx950 CU has: this kernel does not build for earlier CDNA parts)
 struct MidPair { Segs segs[2]; MsmGeom g[2]; u32 *E[2]; };
 __global__ void __launch_bounds__(MID_THREADS) k_msm_mid(MidPair p) {
   __shared__ u32 s_cnt[MID_B + 2], s_off[MID_B + 2], s_cur[MID_B + 2], s_lane0[MID_B + 2];

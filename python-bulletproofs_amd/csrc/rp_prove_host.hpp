@@ -393,13 +393,13 @@ static int rp_prove_batch_impl(bpmi_rp_prover *pv, uint64_t n_proofs, const uint
     if (rc) return rc;
     const u32 P0 = (P + 1) / 2;
     HIPCHK(ctx, hipEventRecord(ctx->ev_fork, st));                  // (the inputs are up)
-    HIPCHK(ctx, hipStreamWaitEvent(ctx->stream1, ctx->ev_fork, 0));
-    Half ha = make_half(0, P0, st, true), hb = make_half(P0, P - P0, ctx->stream1, false);
+    HIPCHK(ctx, hipStreamWaitEvent(ctx->lane[1].stream, ctx->ev_fork, 0));
+    Half ha = make_half(0, P0, st, true), hb = make_half(P0, P - P0, ctx->lane[1].stream, false);
     for (u32 sidx = 0; sidx < nsteps; sidx++) {
       step(ha, sidx, pv->ev_chain[0], sidx ? pv->ev_chain[1] : nullptr);          // (queued alternately: an event is recorded before it is waited for)
       step(hb, sidx, pv->ev_chain[1], pv->ev_chain[0]);
     }
-    HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->stream1));
+    HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->lane[1].stream));
     HIPCHK(ctx, hipStreamWaitEvent(st, ctx->ev_join, 0));
   } else {
     Half ha = make_half(0, P, st, true);

@@ -7,6 +7,8 @@
 //   rp_wire_v2_host.hpp   wire formats 2 and 3 -> format 1 (untrusted bytes in: every malformed shape must be refused, never overrun;
 //                         format 3's y coordinates checked with host_tail.hpp's field arithmetic)
 //   host_pool.hpp         the sleeping worker pool those loops run on: concurrent callers, nested loops, every width
+//   msm_plan_host.hpp     the plan of an MSM (geometry, workspace layout, reduction jobs, slices) over the sweep of
+//                         tests/test_msm_plan_cpu.py, through the flat arrays of msm_plan_flat.hpp; once per run
 // Built by tests/test_host_native_sanitizers.py with -fsanitize=address,undefined (every output buffer is a heap block of
 // EXACTLY the documented size, so an overrun of one byte is a report) and again with -fsanitize=thread (the threaded entry
 // points with 1..8 threads).  Besides "no report" it checks what can be checked without an oracle: results do not depend on the
@@ -23,6 +25,7 @@
 #include "transcript_host.hpp"
 #include "rp_wire_v2_host.hpp"
 #include "host_tail.hpp"
+#include "msm_plan_flat.hpp"
 
 static uint64_t rng_state = 0x9E3779B97F4A7C15ULL;
 static uint64_t rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return rng_state; }
@@ -317,9 +320,69 @@ static void test_host_pool() {
   CHECK(bad == 0);
 }
 
+// The planner over every size threshold, random sizes, the option values that reach it, msm_run_split's window groups and every mode,
+// into heap blocks of exactly the documented sizes: no overrun, no overflow or shift the sanitizers object to, and the bounds that
+// keep the kernels inside the workspace (the full list of invariants: tests/test_msm_plan_cpu.py).
+static void test_msm_plan() {
+  static const uint64_t edges[] = {1, 2, 1023, 1024, 2559, 2560, 4608, 4609, 5631, 5632, 8448, 8449, 10239, 10240, 15359, 15360, 18999, 19000, 1u << 15,
+                                   (1u << 17) - 1, 1u << 17, (1u << 17) + 1, 184999, 185000, 1u << 19, 1u << 20, 1u << 23};
+  static const int32_t sets[][2] = {{0, 0}, {0, 2}, {0, 3}, {0, 4}, {0, 5}, {0, 6}, {0, 7}, {0, 8}, {0, 9}, {0, 10}, {0, 11}, {0, 12}, {0, 13}, {0, 14}, {0, 15}, {0, 16},
+                                    {1, 0}, {2, 0}, {3, 1}, {4, 1}, {4, 2}, {4, 3}, {4, 4}, {5, -1}, {6, -1}, {7, 1}, {7, 4}, {7, 16}, {7, 64}, {8, 0},
+                                    {9, 1}, {9, 86}, {9, 4096}, {10, 1}, {10, 3}, {10, 16}, {11, 0}};          // (index into PLAN_OPTION, value)
+  std::vector<uint64_t> sizes(edges, edges + sizeof(edges) / sizeof(edges[0]));
+  for (int i = 0; i < 200; i++) sizes.push_back(1 + rnd() % (1ull << (1 + rnd() % 23)));
+  for (const auto &kv : sets)
+    for (uint64_t n : sizes) {
+      Buf geom(4 * PLAN_GEOM_WORDS), layout(8 * PLAN_LAYOUT_WORDS), reduce(4 * PLAN_REDUCE_WORDS);
+      const uint32_t c = plan_flat(kv, 1, n, 0, 0, 0, (uint32_t *)geom.p, (uint64_t *)layout.p, (uint32_t *)reduce.p);
+      const uint32_t W = 255u / c + 1u, groups[3][2] = {{0, 0}, {0, W / 2}, {W / 2, W - W / 2}};
+      for (const auto &grp : groups)
+        for (uint32_t mode = 0; mode < 6; mode++) {
+          if (grp[1] == 0 && grp[0] != 0) continue;
+          plan_flat(kv, 1, n, grp[0], grp[1], mode, (uint32_t *)geom.p, (uint64_t *)layout.p, (uint32_t *)reduce.p);
+          const uint32_t *g = (const uint32_t *)geom.p, *r = (const uint32_t *)reduce.p;
+          const uint64_t *lay = (const uint64_t *)layout.p;
+          CHECK(g[6] >= 1 && lay[29] * g[6] >= (uint64_t)g[0] * g[2]);                  // chunks cover the entries
+          CHECK(lay[24] == lay[25] && lay[26] <= PART_MAX);
+          for (int i = 0; i < 24; i++) CHECK(lay[i] % 256 == 0 && lay[i] <= lay[24] && (i == 0 || lay[i - 1] <= lay[i]));
+          if (g[4] > 256u) {
+            CHECK(r[3 * PLAN_JOBS_WORDS] >= 1);                                       // stage 1 has blocks
+            for (int k = 0; k < 3; k++)
+              for (uint32_t j = 0; j < r[PLAN_JOBS_WORDS * k]; j++) {
+                const uint32_t *job = r + PLAN_JOBS_WORDS * k + 2 + PLAN_JOB_WORDS * j;
+                CHECK(job[5] >= 1 && job[6] >= 1 && job[5] * job[6] <= 64u);
+              }
+          }
+        }
+    }
+  static const uint32_t totals[] = {(1u << 20) - 1, 1u << 20, 1703936, 1703937, 1u << 21, (1u << 21) + 1, 1u << 23, (1u << 23) + 1, (1u << 24) + 1};
+  static const int32_t slice_sets[][2] = {{14, 0}, {14, 1 << 16}, {14, 1 << 22}, {14, -1}};
+  for (const auto &kv : slice_sets)
+    for (uint32_t total : totals)
+      for (int nsegs = 1; nsegs <= 3; nsegs++) {
+        uint32_t nseg[3] = {total, 0, 0};
+        if (nsegs >= 2) { nseg[1] = (uint32_t)(1 + rnd() % (total - 2)); nseg[0] = total - nseg[1]; }
+        if (nsegs == 3 && nseg[0] > 1) { nseg[2] = (uint32_t)(1 + rnd() % (nseg[0] - 1)); nseg[0] -= nseg[2]; }
+        const uint64_t pts[3] = {1ull << 44, 2ull << 44, 3ull << 44}, sc[3] = {5ull << 44, 6ull << 44, 7ull << 44};
+        Buf none(0);
+        const uint64_t K = plan_flat_slices(kv, 1, nseg, pts, sc, 0, (uint64_t *)none.p);
+        CHECK(K >= 1 && K <= 4096);
+        Buf out(8 * PLAN_SLICE_WORDS * (size_t)K);
+        CHECK(plan_flat_slices(kv, 1, nseg, pts, sc, K, (uint64_t *)out.p) == K);
+        uint64_t covered = 0;
+        for (uint64_t k = 0; k < K; k++) {
+          const uint64_t *q = (const uint64_t *)out.p + PLAN_SLICE_WORDS * k;
+          CHECK(q[0] == q[1] + q[2] + q[3] && q[0] <= (1u << 23) + (K == 1 ? (1u << 24) : 0u));
+          covered += q[0];
+        }
+        CHECK(covered == total);
+      }
+}
+
 int main(int argc, char **argv) {
   const long iters = argc > 1 ? atol(argv[1]) : 200;
   if (argc > 2) rng_state ^= (uint64_t)atoll(argv[2]) * 0x9E3779B97F4A7C15ULL;
+  test_msm_plan();
   for (long it = 0; it < iters; it++) {
     test_algebra();
     test_transcript();

@@ -11,6 +11,7 @@
 #include "../../include/bpmi.h"
 #include "rp_batch_host.hpp"
 #include "host_tail.hpp"
+#include "msm_plan_flat.hpp"
 using namespace bpmi;
 
 static void load_fe(fe &r, const uint8_t *b) { u32 w[8]; memcpy(w, b, 32); fe_from_words(r, w); }
@@ -298,5 +299,12 @@ void t_host_tail(const uint8_t *pts, const uint8_t *zs, u32 W, u32 c, u32 nv, co
   to.nv = nv; to.top = top;
   for (int k = 0; k < 4; k++) { to.off[k] = off[k]; to.top_off[k] = top_off[k]; }
   bpmi_host::tail_combine(out, E.data(), W, c, to);
+}
+// the MSM planner (csrc/msm_plan_host.hpp) as flat arrays: msm_plan_flat.hpp says what is where
+uint32_t t_msm_plan(const int32_t *kv, int nkv, uint64_t n, uint32_t w0, uint32_t wcount, uint32_t mode_bits, uint32_t *geom, uint64_t *layout, uint32_t *reduce) {
+  return plan_flat(kv, nkv, n, w0, wcount, mode_bits, geom, layout, reduce);
+}
+uint64_t t_msm_slices(const int32_t *kv, int nkv, const uint32_t *nseg, const uint64_t *pts, const uint64_t *sc, uint64_t cap, uint64_t *out) {
+  return plan_flat_slices(kv, nkv, nseg, pts, sc, cap, out);
 }
 }

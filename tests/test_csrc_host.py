@@ -18,9 +18,9 @@ SO = os.path.join(REPO, "tests", "csrc_host", "libhost_shim.so")
 P = secp256k1.p
 
 
-@pytest.fixture(scope="module")
-def shim():
-    deps = [SRC] + [os.path.join(INC, f) for f in os.listdir(INC) if f.endswith(".hpp")]
+def load_shim():
+    """Builds tests/csrc_host/libhost_shim.so when it is missing or older than a source, and loads it."""
+    deps = [SRC] + [os.path.join(d, f) for d in (INC, os.path.dirname(SRC)) for f in os.listdir(d) if f.endswith(".hpp")]
     if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", INC, SRC, "-o", SO])
     L = ctypes.CDLL(SO)
@@ -38,6 +38,11 @@ def shim():
     L.t_host_tail.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
                               ctypes.c_char_p]
     return L
+
+
+@pytest.fixture(scope="module")
+def shim():
+    return load_shim()
 
 
 def sc_op(L, op, a, b=0):

@@ -401,3 +401,30 @@ def test_c5_wire_format_2_same_verdicts_as_format_1(gp):
         assert got == want, (trial, kind, j)
         rejected += not got
     assert rejected >= 150
+
+
+def test_msm_geometry_of_the_library_is_the_plan_the_cpu_tests_check(gp):
+    """bpmi_msm_geometry (libbpmi.so, built by hipcc) against the host build of csrc/msm_plan_host.hpp that
+    tests/test_msm_plan_cpu.py checks: the same header, so the same answer, for the documented table points under the default
+    options and for the asynchronous pipeline (pipelined, async_lanes on: the chained mode).  No kernel is launched."""
+    import test_csrc_host
+    import test_msm_plan_cpu as plan_cpu
+    shim = plan_cpu.bind(test_csrc_host.load_shim())
+    eng = gp.engine()
+
+    def same(n, pipelined, mode):
+        got, g = eng.msm_geometry(n, pipelined=pipelined), plan_cpu.plan(shim, {}, n, mode)["g"]
+        want = {"kernel": "small" if g["small"] else ("mid" if g["mid"] else "pipeline"), "window_bits": g["c"], "windows": g["W"], "wide_windows": g["top2"],
+                "buckets": g["G"], "chunk": g["L"], "slices": 1, "pairs_per_slice": n}
+        assert got == want, (n, pipelined, mode)
+
+    for n, _ in plan_cpu.TABLE:
+        same(n, False, 0)
+        same(n, True, 0)                          # pipelined without async_lanes: one stream, nothing chained
+    eng.set_option("async_lanes", 1)
+    try:
+        for n, _ in plan_cpu.TABLE:
+            same(n, True, plan_cpu.CHAINED)
+        assert eng.msm_geometry(1 << 20, pipelined=True)["chunk"] == 29
+    finally:
+        eng.set_option("async_lanes", 0)

@@ -1,6 +1,6 @@
 """Sweep of the MSM's window bits x chunk length at MID sizes (2^13 .. 2^19 and the batch verifier's 311 427 pairs), wall time of
 synchronous calls WITHOUT stage timers (every recorded event is a bubble) and with two calls in flight; the table behind
-pick_window_bits / the chunk choice of csrc/msm_host.hpp.   python tools/tune_msm_mid.py [n ...]   (TUNE_C, TUNE_CHUNK: lists)"""
+pick_window_bits / the chunk choice of csrc/msm_plan_host.hpp.   python tools/tune_msm_mid.py [n ...]   (TUNE_C, TUNE_CHUNK: lists)"""
 import hashlib, os, sys, time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
