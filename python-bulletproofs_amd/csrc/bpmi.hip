@@ -48,6 +48,7 @@ using namespace bpmi;
 
 #include "shared_defs.hpp"
 #include "msm_plan_host.hpp"
+#include "rp_batch_plan_host.hpp"
 #include "context.hpp"
 #include "device_util.hpp"
 #include "msm_kernels.hpp"
@@ -795,7 +796,6 @@ static int svector_launch(bpmi_ctx *ctx, const SvecLayout &L, const void *d_scal
   HIPCHK(ctx, hipGetLastError());
   return BPMI_OK;
 }
-static bool log2_exact(uint64_t n, u32 &k) { k = 0; while ((1ull << k) < n) k++; return n && (1ull << k) == n; }
 
 int bpmi_sc_svector(bpmi_ctx *ctx, const uint8_t *xs, const uint8_t *xinvs, uint32_t k, const uint8_t a[32], const uint8_t b[32],
                     const uint8_t *scale, uint8_t *sa, uint8_t *sb) {
@@ -862,482 +862,10 @@ int bpmi_ipa_verify_dev(bpmi_ctx *ctx, const void *d_g, const void *d_h, const v
 }  // extern "C"
 
 #include "ipa_host.hpp"
+#include "rp_batch_dev_host.hpp"
 
 extern "C" {
 
-// ---- batch verification of range proofs: host-side preparation ---------------------------------------
-int bpmi_rp_batch_prepare(uint32_t n_gens, uint32_t values_per_proof, uint64_t n_proofs, const uint8_t *blobs, uint64_t blobs_len, const uint64_t *blob_off,
-                          const uint8_t *weights, const uint8_t *seed, int threads, uint8_t *v_scalars, uint8_t *pt_scalars, uint8_t *shared, uint8_t *comp_out,
-                          int64_t *first_bad) {
-  if (!blobs || !blob_off || (!weights && !seed) || !v_scalars || !pt_scalars || !shared || !first_bad) return BPMI_E_ARG;
-  if (n_gens < 2 || (n_gens & (n_gens - 1)) || n_gens > 65536) return BPMI_E_ARG;
-  const uint32_t m = values_per_proof;
-  if (m < 1 || n_gens % m) return BPMI_E_ARG;
-  uint32_t k = 0;
-  while ((1u << k) < n_gens) k++;
-  *first_bad = -1;
-  // the offset table comes from the caller, the proofs from the network: never read outside blobs[0, blobs_len)
-  if (blob_off[0] > blobs_len) return BPMI_E_ARG;
-  for (uint64_t g = 0; g < n_proofs; g++) if (blob_off[g] > blob_off[g + 1] || blob_off[g + 1] > blobs_len) return BPMI_E_ARG;
-  // wire formats 2 and 3 (rp_wire_v2_host.hpp): expanded to format 1 here (format 3's y coordinates checked), then everything below
-  // runs as before
-  std::vector<uint8_t> expanded;
-  std::vector<uint64_t> expanded_off;
-  bool any_v2 = false;
-  for (uint64_t g = 0; g < n_proofs && !any_v2; g++)
-    any_v2 = blob_off[g + 1] >= blob_off[g] + 5 && (blobs[blob_off[g] + 4] == '2' || blobs[blob_off[g] + 4] == '3');
-  if (any_v2) {
-    expanded_off.assign(n_proofs + 1, 0);
-    std::vector<uint8_t> one;
-    for (uint64_t g = 0; g < n_proofs; g++) {
-      const uint8_t *b = blobs + blob_off[g];
-      const size_t len = (size_t)(blob_off[g + 1] - blob_off[g]);
-      // a format-1 proof among format-2 ones is taken as it is; so is a blob that claims format 2 and does not expand -- it is not a
-      // format-1 proof either, so the checks below reject it AT ITS INDEX, behind any earlier bad proof (returning here at once made
-      // the host name a later proof than the device: tools/fuzz_batch_prepare.py, round 5)
-      if (len >= 5 && (b[4] == '2' || b[4] == '3') && rpw::expand_v2(b, len, one)) expanded.insert(expanded.end(), one.begin(), one.end());
-      else expanded.insert(expanded.end(), b, b + len);
-      expanded_off[g + 1] = expanded.size();
-    }
-    blobs = expanded.data(); blobs_len = expanded.size(); blob_off = expanded_off.data();
-  }
-  const size_t nacc = 5 + 2 * (size_t)n_gens;
-  if (threads < 1) threads = 1;
-  if ((uint64_t)threads > n_proofs) threads = n_proofs ? (int)n_proofs : 1;
-  std::vector<uint64_t> pt_off(n_proofs + 1);
-  for (uint64_t g = 0; g <= n_proofs; g++) pt_off[g] = g * (6 + 2 * (uint64_t)k);
-  std::vector<std::vector<rp::Sq>> acc(threads, std::vector<rp::Sq>(nacc, rp::q_small(0)));
-  std::vector<uint64_t> bad(threads, UINT64_MAX);
-  auto work = [&](int t) {
-    const uint64_t lo = n_proofs * t / threads, hi = n_proofs * (t + 1) / threads;
-    // sub-chunks bound the scratch memory and keep one modular inversion per ~512 proofs
-    for (uint64_t a = lo; a < hi; a += 512) {
-      const uint64_t b = a + 512 < hi ? a + 512 : hi;
-      uint64_t bd = UINT64_MAX;
-      if (!rp::run_chunk(n_gens, k, m, blobs, blob_off, weights, a, b, pt_off.data(), v_scalars, pt_scalars, comp_out, acc[t].data(), &bd, seed)) { bad[t] = bd; return; }
-    }
-  };
-  if (threads == 1) work(0);
-  else {
-    std::vector<std::thread> th;
-    for (int t = 0; t < threads; t++) th.emplace_back(work, t);
-    for (auto &x : th) x.join();
-  }
-  for (int t = 0; t < threads; t++) if (bad[t] != UINT64_MAX && (*first_bad < 0 || (int64_t)bad[t] < *first_bad)) *first_bad = (int64_t)bad[t];
-  for (size_t i = 0; i < nacc; i++) {
-    rp::Sq sum = rp::q_small(0);
-    for (int t = 0; t < threads; t++) rp::q_add(sum, sum, acc[t][i]);
-    rp::q_to_le(shared + 32 * i, sum);
-  }
-  return BPMI_OK;
-}
-
-// The same preparation on the GPU (rp_batch_kernels.hpp): the wire proofs are uploaded (in a few slices, so that the decoding of
-// the points of slice c runs on the second lane while slice c + 1 is still on the link), one lane per proof and role parses,
-// hashes and checks them, the weighted scalars are written straight into the caller's device scalar arrays, the proofs' points
-// are decoded where they lie in the blobs into d_points, and only the (5 + 2n) shared coefficients and the verdict come back.
-struct RpQueued { u32 *d_shared; unsigned long long *d_bad; u32 ncols; };
-// bpmi_rp_batch_group_values_dev: the preparation sums the cells per GROUP of `group` proofs instead of per batch and leaves one verdict
-// byte per proof (k_rp_verdict, k_rp_group_colsum); the arrays live behind the preparation's own in ctx->rp_buf
-struct RpGroups {
-  u32 group, ngroups;        // in
-  u32 *d_gsum, *d_gfin;      // out: ngroups x (5 + 2n) raw column sums; room for the ngroups x (3 + 2n) scalars of the groups' MSMs
-  uint8_t *d_verdict, *d_ptflag;
-  u32 *d_E, *d_vals;         // room for the window sums (37 per group) and the 64-byte values
-};
-#define RP_UPLOAD_SLICES 4
-// A batch is read in the wire format of its FIRST proof.  A well-formed proof of the OTHER format inside it is not a forged proof: the
-// device paths report it as an argument error ("mixed wire formats"), not as a verdict -- a verifier must be able to tell a
-// sender's mix-up from an attack (the host path, bpmi_rp_batch_prepare, takes the formats proof by proof).
-static int rp_mixed_formats(bpmi_ctx *ctx, const uint8_t *blobs, uint64_t blobs_len, const uint64_t *blob_off, int64_t first_bad) {
-  if (first_bad < 0) return BPMI_OK;
-  const uint64_t a0 = blob_off[0], a = blob_off[first_bad], e = blob_off[first_bad + 1];
-  if (a0 + 5 > blobs_len || e > blobs_len || e < a + 5) return BPMI_OK;
-  const uint8_t *b = blobs + a;
-  const uint8_t call = (blobs[a0 + 4] == '2' || blobs[a0 + 4] == '3') ? blobs[a0 + 4] : (uint8_t)'1';
-  if (!(b[0] == 'B' && b[1] == 'P' && b[2] == 'R' && b[3] == 'P' && b[4] >= '1' && b[4] <= '3' && b[4] != call)) return BPMI_OK;
-  // WELL-FORMED in the format it claims?  (a format-1 proof whose magic a flipped bit turned into "BPRP3" is a bad proof, not a mix-up)
-  const size_t len = (size_t)(e - a);
-  rp::Parsed parsed;
-  const bool well_formed = b[4] == '1' ? rp::parse_blob(parsed, b, len) : (len > 0 && rpw::v2_length(b, len) == len);
-  if (well_formed)
-    return fail(ctx, BPMI_E_ARG, "mixed wire formats: proof " + std::to_string(first_bad) + " is format " + std::string(1, (char)b[4]) + " in a format-" +
-                                     std::string(1, (char)call) + " batch (one format per call; bpmi_rp_wire_v2_to_v1 converts)");
-  return BPMI_OK;
-}
-// queues everything on the ctx's two lanes and returns without waiting; the results stay on the device (d_shared: 5 + 2n
-// scalars of 8 words, *d_bad behind them).  The caller waits for both lanes whatever this returns.
-static int rp_prepare_enqueue(bpmi_ctx *ctx, uint32_t n_gens, uint32_t m, uint64_t n_proofs, const uint8_t *blobs, uint64_t blobs_len, const uint64_t *blob_off,
-                              const uint8_t *weights, const uint8_t *seed, void *d_v_scalars, void *d_pt_scalars, void *d_points, RpQueued &Q,
-                              RpGroups *G = nullptr) {
-  if (n_gens < 2 || (n_gens & (n_gens - 1)) || n_gens > 65536) return fail(ctx, BPMI_E_ARG, "n_gens must be a power of two in [2, 65536]");
-  if (m < 1 || n_gens % m) return fail(ctx, BPMI_E_ARG, "values_per_proof must divide n_gens");
-  if (n_proofs == 0 || n_proofs > (1ull << 22)) return fail(ctx, BPMI_E_ARG, "n_proofs must be in [1, 2^22]");
-  if (blobs_len > (1ull << 32)) return fail(ctx, BPMI_E_ARG, "at most 4 GiB of proofs per call");
-  uint32_t k = 0;
-  while ((1u << k) < n_gens) k++;
-  if (blob_off[0] > blobs_len) return fail(ctx, BPMI_E_ARG, "offset table leaves the buffer");
-  // wire format 2 (rp_wire_v2_host.hpp): told by the first proof's magic; every proof of the call must then be format 2 (the device
-  // expander refuses the others).  The array the roles read holds the EXPANDED proofs: its rows are sized by the longest expansion
-  const uint8_t fmt0 = (blob_off[1] >= blob_off[0] + 5 && blob_off[0] + 5 <= blobs_len) ? blobs[blob_off[0] + 4] : (uint8_t)'1';
-  const bool v2 = fmt0 == '2' || fmt0 == '3';
-  const uint64_t hint_bytes = fmt0 == '3' ? 32ull * (6 + 2 * k) : 0;             // format 3: the points' y coordinates behind the format-2 proof
-  // The expander, the roles and the element kernel are chains of dependent instructions, one wave per SIMD; on formats 1 and 2 they run beside
-  // the second lane's square roots (k_ec_decompress_wire: every issue slot it can get).  Raised issue priority lets the chains run at their
-  // own speed: format 2 alone 1.71-1.73 -> 1.64-1.68 ms, ten in flight +2.4-2.8 % (two boxes, profiles/r06_C5_preparation_priority_ab.txt);
-  // format 3 has no square roots beside it and gains nothing (option "rp_priority": 0 off, 1 = formats 1 and 2 (default), 2 = always)
-  const u32 rp_prio = (ctx->opt_rp_prio == 2 || (ctx->opt_rp_prio == 1 && fmt0 != '3')) ? 1u : 0u;
-  uint64_t maxlen = 0;
-  for (uint64_t g = 0; g < n_proofs; g++) {
-    if (blob_off[g] > blob_off[g + 1] || blob_off[g + 1] > blobs_len) return fail(ctx, BPMI_E_ARG, "offset table leaves the buffer");
-    uint64_t len = blob_off[g + 1] - blob_off[g];
-    if (v2) {
-      // longest expansion a format-2 proof of this length can have (its seeds' lengths are NOT read here: 2^14 scattered reads of
-      // the receive buffer cost more than the upload saves): S seed bytes in all, base64 of them at most three times (the
-      // Protocol-1 seed appears in two transcripts), every point item 45 bytes, every decimal item 79
-      const uint64_t body = 6 + 32ull * (5 + k) + 33ull * (6 + 2 * k);
-      const uint64_t S = len > body + 132 + hint_bytes ? len - body - 132 - hint_bytes : 0;
-      len = body + 2 + 12 + 3 * (4 * ((S + 2) / 3) + 1) + 4 * 45 + 3 * 79 + 2 * 79 + 1 + (uint64_t)k * (45 + 45 + 79);
-    }
-    maxlen = std::max(maxlen, len);
-  }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  const u32 P = (u32)n_proofs, ncols = 5 + 2 * n_gens, per = 6 + 2 * k;
-  // the proofs as 8-byte words, word-major (k_rp_transpose): W rows of P words, 16 rows of zero padding for loads that run past a proof
-  const u32 W = (u32)((std::min<uint64_t>(maxlen, RP_MAX_PROOF_BYTES) + 7) / 8) + 16;
-  // device staging: blobs | offsets | weights | status
-  const size_t o_off = align_up(blobs_len + 128, 256);      // 128 bytes of slack: the kernel's batched 8-byte loads may run past the last proof
-  const size_t o_w = o_off + align_up(8 * ((size_t)P + 1), 256), o_st = o_w + (weights ? align_up(128 * (size_t)P, 256) : 0);
-  int rc = ensure_stage_in(ctx, o_st + align_up(RP_ROLES * (size_t)P, 256));
-  if (rc) return rc;
-  rc = ensure_lane(ctx, 1);
-  if (rc) return rc;
-  rc = ensure_pin(ctx, 32 * (size_t)ncols + 64);
-  if (rc) return rc;
-  for (int c = 0; c < RP_UPLOAD_SLICES; c++)
-    if (!ctx->ev_slice[c]) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_slice[c], hipEventDisableTiming));
-  char *din = (char *)ctx->stage_in;
-  // contributions + contexts: at most ~256 MB of cells per launch
-  const u32 nslots = CTX_SLOTS(k, m);
-  const size_t cell_row = 36 * ((size_t)ncols + nslots), out_row = 32 * (size_t)ncols;       // scratch cells are 9 limbs, the result 8 words
-  u32 rows = (u32)std::min<size_t>(P, std::max<size_t>(1, ((size_t)256 << 20) / cell_row));
-  if (ctx->opt_rp_rows > 0) rows = std::min<u32>(rows, (u32)ctx->opt_rp_rows);
-  const size_t o_ctx = align_up(36 * (size_t)ncols * rows, 256), o_shared = o_ctx + align_up(36 * (size_t)nslots * rows, 256),
-               o_T = o_shared + align_up(2 * out_row + 256, 256), T_bytes = 8 * (size_t)W * P,      // summed columns | verdict | MSM scalars of the shared generators
-               o_lens = o_T + align_up(T_bytes, 256);                                               // format 2: lengths of the expanded proofs
-  size_t need = o_lens + 4 * (size_t)P + 256;
-  size_t o_gsum = 0, o_gfin = 0, o_verdict = 0, o_ptflag = 0, o_E = 0, o_vals = 0;
-  if (G) {
-    const size_t ng = G->ngroups;
-    o_gsum = align_up(need, 256); o_gfin = o_gsum + align_up(32 * (size_t)ncols * ng, 256);
-    o_verdict = o_gfin + align_up(32 * (size_t)(ncols - 2) * ng, 256); o_ptflag = o_verdict + align_up(P, 256);
-    o_E = o_ptflag + align_up(P, 256); o_vals = o_E + align_up(4ull * XYZZ_WORDS * (255u / MID_C + 1u) * ng, 256);
-    need = o_vals + 64 * ng + 256;
-  }
-  if (need > ctx->rp_buf_bytes) {
-    if (ctx->rp_buf) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(ctx->rp_buf)); ctx->rp_buf = nullptr; ctx->rp_buf_bytes = 0; }
-    HIPCHK(ctx, hipMalloc(&ctx->rp_buf, need));
-    ctx->rp_buf_bytes = need;
-  }
-  u32 *d_contrib = (u32 *)ctx->rp_buf, *d_ctx = (u32 *)((char *)ctx->rp_buf + o_ctx), *d_shared = (u32 *)((char *)ctx->rp_buf + o_shared);
-  u64 *d_T = (u64 *)((char *)ctx->rp_buf + o_T);
-  unsigned long long *d_bad = (unsigned long long *)(d_shared + 8 * (size_t)ncols);
-  Q.d_shared = d_shared; Q.d_bad = d_bad; Q.ncols = ncols;
-  HIPCHK(ctx, h2d(ctx, din + o_off, blob_off, 8 * ((size_t)P + 1), ctx->stream));
-  if (weights) HIPCHK(ctx, h2d(ctx, din + o_w, weights, 128 * (size_t)P, ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync(d_shared, 0, out_row, ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync(d_bad, 0xFF, 8, ctx->stream));
-  if (G) {
-    char *b = (char *)ctx->rp_buf;
-    G->d_gsum = (u32 *)(b + o_gsum); G->d_gfin = (u32 *)(b + o_gfin); G->d_verdict = (uint8_t *)(b + o_verdict); G->d_ptflag = (uint8_t *)(b + o_ptflag);
-    G->d_E = (u32 *)(b + o_E); G->d_vals = (u32 *)(b + o_vals);
-    HIPCHK(ctx, hipMemsetAsync(G->d_gsum, 0, 32 * (size_t)ncols * G->ngroups, ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(G->d_ptflag, 0, P, ctx->stream));            // (before the slices' events: the second lane's decoding sets flags)
-  }
-  // Upload in slices of whole proofs; the point decoding of a slice (second lane; it reads only the wire bytes) starts as soon as the
-  // slice has arrived and runs beside the upload of the next one and, for the last slice, beside the preparation kernels.
-  // Option rp_overlap = 0 (measurements only): one decoding launch BEHIND the preparation kernels on the same stream, so that
-  // every kernel's duration is its own.
-  auto decode = [&](hipStream_t st, u32 g0, u32 g1) {
-    StageTimer t(ctx, ST_DECOMP, st);
-    const u64 npts = (u64)(g1 - g0) * per;
-    hipLaunchKernelGGL(k_ec_decompress_wire, dim3((u32)((npts + 255) / 256)), dim3(256), 0, st, (const uint8_t *)din, (const u64 *)(din + o_off) + g0,
-                       k, g1 - g0, (u64)g0, (u32)RP_MAX_PROOF_BYTES, (u32 *)d_points + 16ull * per * g0, d_bad, G ? G->d_ptflag + g0 : (uint8_t *)nullptr);
-  };
-  // (format 3's points are checked, not computed: 0.02 ms for 2^14 proofs -- nothing to hide behind an upload, and four uploads with their
-  // events cost more than one: a batch alone 1.63 ms against 1.72; the one check still runs on the second lane, beside the expander)
-  const u32 nsl = (P >= 4096 && ctx->opt_rp_overlap) ? (ctx->opt_rp_slices > 0 ? (u32)ctx->opt_rp_slices : (fmt0 != '3' ? RP_UPLOAD_SLICES : 1u)) : 1u;
-  for (u32 c = 0; c < nsl; c++) {
-    const u32 g0 = (u32)((uint64_t)P * c / nsl), g1 = (u32)((uint64_t)P * (c + 1) / nsl);
-    const uint64_t b0 = c == 0 ? 0 : blob_off[g0], b1 = c + 1 == nsl ? blobs_len : blob_off[g1];
-    if (b1 > b0) HIPCHK(ctx, h2d(ctx, din + b0, blobs + b0, b1 - b0, ctx->stream));
-    if (ctx->opt_rp_overlap) {
-      HIPCHK(ctx, hipEventRecord(ctx->ev_slice[c], ctx->stream));
-      HIPCHK(ctx, hipStreamWaitEvent(ctx->lane[1].stream, ctx->ev_slice[c], 0));
-      decode(ctx->lane[1].stream, g0, g1);
-    }
-  }
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->lane[1].stream));
-  u32 *d_lens = v2 ? (u32 *)((char *)ctx->rp_buf + o_lens) : nullptr;
-  if (v2) {
-    // the expander writes the format-1 proofs word-major itself; what it does not write must read as zero
-    HIPCHK(ctx, hipMemsetAsync(d_T, 0, T_bytes, ctx->stream));
-    StageTimer t(ctx, ST_RPPREP);
-    hipLaunchKernelGGL(rpd::k_rp_expand_v2, dim3((P + 3) / 4), dim3(64), 0, ctx->stream, (const uint8_t *)din, (const u64 *)(din + o_off), P, k, W, d_T, d_lens,
-                       (u32)fmt0, rp_prio);
-  } else {
-    StageTimer t(ctx, ST_RPPREP);
-    hipLaunchKernelGGL(rpd::k_rp_transpose, dim3((P + 63) / 64, (W + 63) / 64), dim3(256), 0, ctx->stream, (const uint8_t *)din, (const u64 *)(din + o_off), P, W, d_T);
-  }
-  rpd::Params q;
-  q.Tstride = P;
-  q.weights = weights ? (const uint8_t *)(din + o_w) : nullptr;
-  for (int i = 0; i < 8; i++) q.seed[i] = seed ? ((u32)seed[4 * i] << 24) | ((u32)seed[4 * i + 1] << 16) | ((u32)seed[4 * i + 2] << 8) | seed[4 * i + 3] : 0;
-  q.n = n_gens; q.k = k; q.m = m; q.Pall = P; q.only_role = ctx->opt_rp_only_role;
-  q.contrib = d_contrib;
-  q.prio = rp_prio;
-  q.ctx = d_ctx;
-  q.bad = d_bad;
-  const size_t lds_bytes = ((size_t)k + 1) * 9 * 64 * sizeof(u32);            // role 2: k + 1 prefix products of 9 limbs per lane
-  u32 lb = 0;
-  while ((1u << lb) < n_gens / m) lb++;
-  rpd::ElemGeom eg;
-  eg.el_log = std::min<u32>(3u, lb);
-  eg.ranges = n_gens >> eg.el_log;
-  // groups: the per-proof verdict needs the point flags, so the decoding comes first (no overlap: queued here; else the join below)
-  if (G && !ctx->opt_rp_overlap) decode(ctx->stream, 0, P);
-  for (u32 base = 0; base < P; base += rows) {
-    const u32 cnt = std::min(rows, P - base);
-    u32 lanes = (u32)ctx->opt_rp_lanes;
-    if (!lanes) lanes = 64;
-    q.off = (const u64 *)(din + o_off) + base;
-    q.lens = v2 ? d_lens + base : nullptr;
-    q.T = d_T + base;
-    q.P = cnt; q.lanes = lanes; q.first = base;
-    q.v_scalars = (u32 *)d_v_scalars + 8 * (size_t)base * m;
-    q.pt_scalars = (u32 *)d_pt_scalars + 8 * (size_t)base * per;
-    q.status = (uint8_t *)(din + o_st) + base;
-    {
-      StageTimer t(ctx, ST_RPPREP);
-      hipLaunchKernelGGL(rpd::k_rp_roles, dim3(RP_ROLES * ((cnt + lanes - 1) / lanes)), dim3(64), lds_bytes, ctx->stream, q);
-    }
-    {
-      StageTimer t(ctx, ST_RPELEM);
-      hipLaunchKernelGGL(rpd::k_rp_elements, dim3(2 * eg.ranges * ((cnt + 63) / 64)), dim3(64), 0, ctx->stream, q, eg);
-      if (!G) hipLaunchKernelGGL(rpd::k_rp_colsum, dim3(ncols), dim3(256), 0, ctx->stream, (const u32 *)d_contrib, cnt, d_shared);
-    }
-    if (G) {
-      if (base == 0 && ctx->opt_rp_overlap) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));      // the two lanes join: every point flag is set
-      StageTimer t(ctx, ST_RPELEM);
-      rpd::VerdictArgs va;
-      va.role_status = (const uint8_t *)(din + o_st); va.pt_flag = G->d_ptflag; va.verdict = G->d_verdict;
-      va.Pall = P; va.first = base; va.cnt = cnt; va.m = m; va.per = per; va.only_role = ctx->opt_rp_only_role;
-      va.v_scalars = (u32 *)d_v_scalars; va.pt_scalars = (u32 *)d_pt_scalars; va.points = (u32 *)d_points;
-      hipLaunchKernelGGL(rpd::k_rp_verdict, dim3((u32)(((uint64_t)cnt * (m + per) + 255) / 256)), dim3(256), 0, ctx->stream, va);
-      const u32 t0 = base / G->group, nt = (base + cnt - 1) / G->group - t0 + 1;                  // the groups with proofs in this chunk
-      u32 lpg = 1;
-      while (lpg < 64u && lpg < G->group) lpg <<= 1;
-      const u32 gpb = 64u / lpg, nblk = (nt + gpb - 1) / gpb;
-      hipLaunchKernelGGL(rpd::k_rp_group_colsum, dim3(ncols * nblk), dim3(64), 0, ctx->stream, (const u32 *)d_contrib, cnt, base, (const uint8_t *)G->d_verdict,
-                         G->group, t0, nt, lpg, ncols, G->d_gsum);
-    }
-  }
-  if (!ctx->opt_rp_overlap && !G) decode(ctx->stream, 0, P);
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-  return BPMI_OK;
-}
-// both lanes idle again; the first error of (rc, the two waits)
-static int rp_wait_lanes(bpmi_ctx *ctx, int rc) {
-  const hipError_t e0 = wait_stream(ctx, ctx->stream), e1 = ctx->lane[1].stream ? wait_stream(ctx, ctx->lane[1].stream) : hipSuccess;      // (lane 2 never takes part in a batch)
-  if (rc) return rc;
-  HIPCHK(ctx, e0);
-  HIPCHK(ctx, e1);
-  return BPMI_OK;
-}
-int bpmi_rp_batch_prepare_dev(bpmi_ctx *ctx, uint32_t n_gens, uint32_t values_per_proof, uint64_t n_proofs, const uint8_t *blobs, uint64_t blobs_len,
-                              const uint64_t *blob_off, const uint8_t *weights, const uint8_t *seed, void *d_v_scalars, void *d_pt_scalars, void *d_points,
-                              uint8_t *shared, int64_t *first_bad) {
-  if (!ctx) return BPMI_E_ARG;
-  if (!blobs || !blob_off || (!weights && !seed) || !d_v_scalars || !d_pt_scalars || !d_points || !shared || !first_bad) return fail(ctx, BPMI_E_ARG, "null argument");
-  *first_bad = -1;
-  RpQueued Q;
-  int rc = rp_prepare_enqueue(ctx, n_gens, values_per_proof, n_proofs, blobs, blobs_len, blob_off, weights, seed, d_v_scalars, d_pt_scalars, d_points, Q);
-  const size_t out_row = rc ? 0 : 32 * (size_t)Q.ncols;
-  if (!rc && hipMemcpyAsync(ctx->pin, Q.d_shared, out_row + 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = fail(ctx, BPMI_E_HIP, "copy of the shared coefficients failed");
-  // an error in the middle must not return while the second lane is still writing into the caller's point array
-  rc = rp_wait_lanes(ctx, rc);
-  if (rc) return rc;
-  memcpy(shared, ctx->pin, out_row);
-  unsigned long long bad;
-  memcpy(&bad, (char *)ctx->pin + out_row, 8);
-  *first_bad = bad == ~0ull ? -1 : (int64_t)bad;
-  rc = rp_mixed_formats(ctx, blobs, blobs_len, blob_off, *first_bad);
-  if (rc) return rc;
-  if (ctx->opt_rp_only_role >= 0) *first_bad = 0;        // a profiling run checked part of every proof: it must never read as "all valid"
-  return BPMI_OK;
-}
-
-// The whole batch verification in ONE call: preparation as above, the shared coefficients folded on the device into the scalars of
-// the 3 + 2n shared generators (k_rp_shared_scalars), and the batch's one MSM over [shared generators | commitments | proof
-// points] -- no host round trip between the preparation and the MSM.  out = the 64-byte value of the combination (the identity
-// for a valid batch; a sharded caller folds the ranks' values), *first_bad as above (then `out` means nothing).
-//   v_points  HOST, n_proofs x values_per_proof x 64 B: the commitments, in proof order
-//   d_gens    DEVICE, (3 + 2 n_gens) x 64 B: g, h, u, gs, hs (uploaded once per verifier)
-//   d_points  DEVICE scratch, (n_proofs (values_per_proof + 6 + 2k)) x 64 B;  d_scalars  DEVICE scratch, the same count x 32 B
-int bpmi_rp_batch_verify_dev(bpmi_ctx *ctx, uint32_t n_gens, uint32_t values_per_proof, uint64_t n_proofs, const uint8_t *blobs, uint64_t blobs_len,
-                             const uint64_t *blob_off, const uint8_t *weights, const uint8_t *seed, const uint8_t *v_points, const void *d_gens, void *d_points,
-                             void *d_scalars, uint8_t out[64], int64_t *first_bad) {
-  if (!ctx) return BPMI_E_ARG;
-  if (!blobs || !blob_off || (!weights && !seed) || !v_points || !d_gens || !d_points || !d_scalars || !out || !first_bad) return fail(ctx, BPMI_E_ARG, "null argument");
-  *first_bad = -1;
-  uint32_t k = 0;
-  while ((1u << k) < n_gens) k++;
-  const uint64_t nv = n_proofs * values_per_proof, npts = n_proofs * (6 + 2 * (uint64_t)k);
-  if (3 + 2 * (uint64_t)n_gens + nv + npts > (1ull << 23)) return fail(ctx, BPMI_E_ARG, "at most 2^23 points in the batch's MSM");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  // commitments: the first nv points / scalars of the per-proof arrays
-  HIPCHK(ctx, h2d(ctx, d_points, v_points, 64 * nv, ctx->stream));
-  const bool check = ctx->opt_validate >= 1;
-  if (check) {
-    int vrc = validate_begin(ctx, ctx->stream);
-    if (vrc) return vrc;
-    validate_enqueue(ctx, d_points, nv, 0, ctx->stream);
-    if (ctx->opt_validate >= 2) validate_enqueue(ctx, d_gens, 3 + 2 * (uint64_t)n_gens, 1, ctx->stream);
-    vrc = validate_fetch(ctx, ctx->stream);
-    if (vrc) return vrc;
-  }
-  RpQueued Q;
-  int rc = rp_prepare_enqueue(ctx, n_gens, values_per_proof, n_proofs, blobs, blobs_len, blob_off, weights, seed, d_scalars, (char *)d_scalars + 32 * nv,
-                              (char *)d_points + 64 * nv, Q);
-  u32 *d_fin = nullptr;
-  if (!rc) {
-    // scalars of g, h, u, gs_i, hs_i: c_g, c_h, c_u, c_gs[i] + gs_const, c_hs[i] + hs_const -- in place behind the raw sums
-    d_fin = Q.d_shared + 8 * (size_t)Q.ncols + 32;
-    {
-      StageTimer t(ctx, ST_RPELEM);
-      hipLaunchKernelGGL(rpd::k_rp_shared_scalars, dim3((3 + 2 * n_gens + 255) / 256), dim3(256), 0, ctx->stream, (const u32 *)Q.d_shared, n_gens, d_fin);
-    }
-    if (hipMemcpyAsync(ctx->pin, Q.d_bad, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = fail(ctx, BPMI_E_HIP, "copy of the verdict failed");
-  }
-  if (rc) return rp_wait_lanes(ctx, rc);
-  Segs s = segs_init();
-  s.pts[0] = (const u32 *)d_gens; s.sc[0] = d_fin; s.n[0] = 3 + 2 * n_gens;
-  s.pts[1] = (const u32 *)d_points; s.sc[1] = (const u32 *)d_scalars; s.n[1] = (u32)(nv + npts);
-  s.total = s.n[0] + s.n[1];
-  rc = msm_run(ctx, s, out);                      // waits for the MSM (ctx stream: behind everything queued above)
-  rc = rp_wait_lanes(ctx, rc);
-  if (rc) return rc;
-  if (check) {
-    static const char *const names[] = {"v_points", "d_gens"};
-    rc = validate_end(ctx, "bpmi_rp_batch_verify_dev", names);
-    if (rc) { memset(out, 0xFF, 64); return rc; }                  // (never the identity)
-  }
-  unsigned long long bad;
-  memcpy(&bad, ctx->pin, 8);
-  *first_bad = bad == ~0ull ? -1 : (int64_t)bad;
-  rc = rp_mixed_formats(ctx, blobs, blobs_len, blob_off, *first_bad);
-  if (rc) { memset(out, 0xFF, 64); return rc; }
-  if (ctx->opt_rp_only_role >= 0) *first_bad = 0;
-  return BPMI_OK;
-}
-// Which proofs of a rejected batch are the bad ones (replaces what a caller of the reference gets from verifying one proof at a time:
-// src/rangeproofs/rangeproof_verifier.py:55-99, rangeproof_aggreg_verifier.py:55-108): the preparation of bpmi_rp_batch_verify_dev, but the
-// cells are summed per GROUP of `group` consecutive proofs, the groups' MSMs over [shared generators | the group's commitments | the
-// group's proof points] run as ONE launch over (group, window) (k_msm_group) with a device tail (k_group_tail), and every proof gets a
-// verdict byte for its byte-level checks.  values[t] = the 64-byte value of group t's combination over its UNFLAGGED proofs (64 zero
-// bytes: all of them verify); status[i] = bit 0: a byte-level check failed (parse, transcript, scalar range) | bit 1: an invalid point
-// encoding.  A flagged proof contributes to no group.  A group whose MSM does not fit the one-launch kernel (3 + 2n + group (m + 6 + 2k) >
-// MID_NMAX pairs) goes through msm_run, group by group: the same 64 bytes.
-int bpmi_rp_batch_group_values_dev(bpmi_ctx *ctx, uint32_t n_gens, uint32_t values_per_proof, uint64_t n_proofs, const uint8_t *blobs, uint64_t blobs_len,
-                                   const uint64_t *blob_off, const uint8_t *weights, const uint8_t *seed, const uint8_t *v_points, const void *d_gens,
-                                   void *d_points, void *d_scalars, uint64_t group, uint8_t *values, uint8_t *status) {
-  if (!ctx) return BPMI_E_ARG;
-  if (!blobs || !blob_off || (!weights && !seed) || !v_points || !d_gens || !d_points || !d_scalars || !values || !status) return fail(ctx, BPMI_E_ARG, "null argument");
-  if (group < 1) return fail(ctx, BPMI_E_ARG, "group must be at least 1");
-  if (n_proofs == 0 || n_proofs > (1ull << 22)) return fail(ctx, BPMI_E_ARG, "n_proofs must be in [1, 2^22]");
-  uint32_t k = 0;
-  while ((1u << k) < n_gens) k++;
-  const uint32_t m = values_per_proof, per = 6 + 2 * k, nshared = 3 + 2 * n_gens;
-  const uint64_t nv = n_proofs * m, npts = n_proofs * per;
-  if (nshared + nv + npts > (1ull << 23)) return fail(ctx, BPMI_E_ARG, "at most 2^23 points in the batch's MSM");
-  RpGroups G;
-  memset(&G, 0, sizeof(G));
-  G.group = (u32)std::min<uint64_t>(group, n_proofs);
-  G.ngroups = (u32)((n_proofs + G.group - 1) / G.group);
-  if ((uint64_t)G.ngroups * nshared > (1ull << 26)) return fail(ctx, BPMI_E_ARG, "too many groups: n_groups x (3 + 2 n_gens) must not exceed 2^26");
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  const size_t vals_bytes = 64 * (size_t)G.ngroups;
-  int rc = ensure_pin(ctx, std::max<size_t>(32 * (size_t)(5 + 2 * n_gens) + 64, vals_bytes + n_proofs + 64));
-  if (rc) return rc;
-  HIPCHK(ctx, h2d(ctx, d_points, v_points, 64 * nv, ctx->stream));
-  const bool check = ctx->opt_validate >= 1;
-  if (check) {
-    int vrc = validate_begin(ctx, ctx->stream);
-    if (vrc) return vrc;
-    validate_enqueue(ctx, d_points, nv, 0, ctx->stream);
-    if (ctx->opt_validate >= 2) validate_enqueue(ctx, d_gens, nshared, 1, ctx->stream);
-    vrc = validate_fetch(ctx, ctx->stream);
-    if (vrc) return vrc;
-  }
-  RpQueued Q;
-  rc = rp_prepare_enqueue(ctx, n_gens, m, n_proofs, blobs, blobs_len, blob_off, weights, seed, d_scalars, (char *)d_scalars + 32 * nv, (char *)d_points + 64 * nv, Q, &G);
-  if (rc) return rp_wait_lanes(ctx, rc);
-  {
-    StageTimer t(ctx, ST_RPELEM);
-    hipLaunchKernelGGL(rpd::k_rp_group_scalars, dim3((u32)(((uint64_t)G.ngroups * nshared + 255) / 256)), dim3(256), 0, ctx->stream, (const u32 *)G.d_gsum, n_gens,
-                       G.ngroups, G.d_gfin);
-  }
-  const uint64_t pairs = nshared + (uint64_t)G.group * (m + per);          // of a full group
-  const u32 W = 255u / MID_C + 1u;
-  if (pairs <= MID_NMAX) {
-    GroupMsm J;
-    J.gens = (const u32 *)d_gens; J.gsc = G.d_gfin;
-    J.v_pts = (const u32 *)d_points; J.v_sc = (const u32 *)d_scalars;
-    J.p_pts = (const u32 *)d_points + 16 * nv; J.p_sc = (const u32 *)d_scalars + 8 * nv;
-    J.nshared = nshared; J.m = m; J.per = per; J.group = G.group; J.P = (u32)n_proofs; J.W = W; J.E = G.d_E;
-    {
-      StageTimer t(ctx, ST_ACCUM);
-      if (pairs <= GROUP_LIGHT_NMAX) hipLaunchKernelGGL((k_msm_group<GROUP_LIGHT_THREADS, GROUP_LIGHT_NMAX>), dim3(G.ngroups * W), dim3(GROUP_LIGHT_THREADS), 0, ctx->stream, J);
-      else hipLaunchKernelGGL((k_msm_group<MID_THREADS, MID_NMAX>), dim3(G.ngroups * W), dim3(MID_THREADS), 0, ctx->stream, J);
-      hipLaunchKernelGGL(k_group_tail, dim3((G.ngroups + 63) / 64), dim3(64), 0, ctx->stream, (const u32 *)G.d_E, W, (u32)MID_C, G.ngroups, G.d_vals);
-    }
-    if (hipGetLastError() != hipSuccess) rc = fail(ctx, BPMI_E_HIP, "launch of the group MSMs failed");
-    if (!rc && hipMemcpyAsync(ctx->pin, G.d_vals, vals_bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = fail(ctx, BPMI_E_HIP, "copy of the group values failed");
-  }
-  if (!rc && hipMemcpyAsync((char *)ctx->pin + vals_bytes, G.d_verdict, n_proofs, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-    rc = fail(ctx, BPMI_E_HIP, "copy of the verdicts failed");
-  rc = rp_wait_lanes(ctx, rc);
-  if (rc) return rc;
-  memcpy(status, (char *)ctx->pin + vals_bytes, n_proofs);
-  if (pairs <= MID_NMAX) {
-    memcpy(values, ctx->pin, vals_bytes);
-  } else {
-    // groups beyond the one-launch kernel's capacity: one MSM each on the three segments
-    for (u32 t = 0; t < G.ngroups && !rc; t++) {
-      const uint64_t g0 = (uint64_t)t * G.group, cnt = std::min<uint64_t>(G.group, n_proofs - g0);
-      Segs s = segs_init();
-      s.pts[0] = (const u32 *)d_gens; s.sc[0] = G.d_gfin + 8 * (size_t)nshared * t; s.n[0] = nshared;
-      s.pts[1] = (const u32 *)d_points + 16 * m * g0; s.sc[1] = (const u32 *)d_scalars + 8 * m * g0; s.n[1] = (u32)(cnt * m);
-      s.pts[2] = (const u32 *)d_points + 16 * (nv + per * g0); s.sc[2] = (const u32 *)d_scalars + 8 * (nv + per * g0); s.n[2] = (u32)(cnt * per);
-      s.total = s.n[0] + s.n[1] + s.n[2];
-      rc = msm_run(ctx, s, values + 64 * (size_t)t);
-    }
-    rc = rp_wait_lanes(ctx, rc);
-    if (rc) { memset(values, 0xFF, vals_bytes); return rc; }
-  }
-  if (check) {
-    static const char *const names[] = {"v_points", "d_gens"};
-    rc = validate_end(ctx, "bpmi_rp_batch_group_values_dev", names);
-    if (rc) { memset(values, 0xFF, vals_bytes); return rc; }
-  }
-  int64_t first_flagged = -1;
-  for (uint64_t i = 0; i < n_proofs && first_flagged < 0; i++) if (status[i]) first_flagged = (int64_t)i;
-  rc = rp_mixed_formats(ctx, blobs, blobs_len, blob_off, first_flagged);
-  if (rc) { memset(values, 0xFF, vals_bytes); return rc; }
-  return BPMI_OK;
-}
 // page-locked host memory for buffers that are handed to the library again and again (e.g. the receive buffer of wire proofs:
 // uploads from it run at link speed and without a staging copy)
 int bpmi_host_alloc(bpmi_ctx *ctx, size_t bytes, void **out) {

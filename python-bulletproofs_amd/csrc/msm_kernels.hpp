@@ -1742,8 +1742,7 @@ __device__ __forceinline__ void msm_mid_block(const Segs &segs, const MsmGeom &g
   }
 }
 
-#define GROUP_LIGHT_THREADS 256
-#define GROUP_LIGHT_NMAX 512
+// (GROUP_LIGHT_THREADS, GROUP_LIGHT_NMAX: shared_defs.hpp)
 struct GroupMsm {
   const u32 *gens, *gsc;              // the 3 + 2n shared generators; their scalars, one row of `nshared` per group
   const u32 *v_pts, *v_sc;            // commitments and their scalars, m per proof, proof-major

@@ -47,8 +47,6 @@ struct MsmMode {
 };
 struct MsmPlan { MsmGeom g; bool mid, small, glv; };      // mid: the one-block-per-window kernel, small: the one-launch kernel, neither: the bucket pipeline
 
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 // Window bits from the tools/tune_msm.py sweeps on MI355X (profiles/r01_tune_msm_after_sort_and_reduce_rewrites.txt).
 // Besides the usual bucket-count trade-off, windows whose TOP window holds only a few
 // bits (255 mod c small: c = 15, 14, 12, 11) concentrate a whole window's digits in a

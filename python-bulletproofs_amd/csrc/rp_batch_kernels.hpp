@@ -367,7 +367,7 @@ struct Params {
 #define CTX_FH(k_, b_) (2u + (k_) + (b_))      // x_(k-1-b)^-2 y^-(2^b)
 #define CTX_GEO(k_, b_) (2u + 2u * (k_) + (b_))      // (2/y)^(2^b) inside a value block, y^-(2^b) for the block-index bits
 #define CTX_W2Z(k_, j_) (2u + 3u * (k_) + (j_))      // w2 z^(2+j)
-#define CTX_SLOTS(k_, m_) (2u + 3u * (k_) + (m_))
+// (CTX_SLOTS, the number of slots: shared_defs.hpp)
 
 // cell (col, g) = 9 limbs of a loose sq; limb w lives at base[(col * 9 + w) * P + g]: every access of a wave is one
 // coalesced row of dwords
@@ -726,10 +726,7 @@ __device__ __forceinline__ bool role_scalars(const Params &q, u32 g, const Layou
 }
 
 // Four waves per group of `lanes` proofs, one per ROLE (see the head of the file).  status[role * Pall + g] = verdict of a role.
-#define RP_ROLES 4
-// A wire proof longer than this is invalid (both here and in the host twin): it bounds the transposed array.  A 64-bit proof
-// is 2.6 KB, the largest shape the format allows (k = 16) under 8 KB.
-#define RP_MAX_PROOF_BYTES 32768u
+// (RP_ROLES, RP_MAX_PROOF_BYTES: shared_defs.hpp)
 __global__ void __launch_bounds__(64) k_rp_roles(Params q) {
   ::raise_priority(q.prio);
   if (threadIdx.x >= q.lanes) return;

@@ -1,16 +1,21 @@
 // shared_defs.hpp -- part of libbpmi; plain C++17 (no HIP), also compiled for the host by tests/csrc_host.
-// What the kernels, the host orchestration and the host-only planner (msm_plan_host.hpp) all read: the engine's options,
-// the multi-segment input descriptor and the sizing constants of the MSM.  One definition of each.
+// What the kernels, the host orchestration and the host-only planners (msm_plan_host.hpp, rp_batch_plan_host.hpp) all read: the
+// engine's options, the multi-segment input descriptor and the sizing constants of the MSM and of the batch verifier.  One
+// definition of each.
 #pragma once
 #include <stdint.h>
 #include <string.h>
 
+#include "../../include/bpmi.h"
 #include "curve.hpp"
 
 using bpmi::u32;
 using bpmi::TailOffs;
 
 #define XYZZ_WORDS 36
+static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// k = the smallest one with 2^k >= n; true when n is that power of two
+static inline bool log2_exact(uint64_t n, u32 &k) { k = 0; while ((1ull << k) < n) k++; return n && (1ull << k) == n; }
 
 // up to three (points, scalars) segments presented as one logical array, so that
 // e.g. L = <a_lo, g_hi> + <b_hi, h_lo> + cl*u is ONE MSM without any gather/concat
@@ -56,6 +61,17 @@ static inline Segs segs_init() {
 #define SMALL_C 8                // window bits of k_msm_small
 #define MID_C 7                  // window bits of k_msm_mid
 #define MID_NMAX 8448            // pairs per MSM: the digit and entry arrays live in LDS (139 KB of the 160 KB a gfx950 CU has: this kernel does not build for earlier CDNA parts)
+#define GROUP_LIGHT_THREADS 256  // the light shape of k_msm_group (small groups: 52 KB of LDS) ...
+#define GROUP_LIGHT_NMAX 512     // ... and the pairs per group it takes
+
+// ---- sizing constants of the batch verifier (the kernels they belong to: rp_batch_kernels.hpp) ---------------------------------
+// Four waves per group of `lanes` proofs, one per ROLE (see the head of rp_batch_kernels.hpp)
+#define RP_ROLES 4
+// A wire proof longer than this is invalid (on the device and in the host twin, rp_batch_host.hpp): it bounds the transposed
+// array.  A 64-bit proof is 2.6 KB, the largest shape the format allows (k = 16) under 8 KB.
+#define RP_MAX_PROOF_BYTES 32768u
+#define CTX_SLOTS(k_, m_) (2u + 3u * (k_) + (m_))      // context slots of one proof (the CTX_* indices, rp_batch_kernels.hpp)
+#define RP_UPLOAD_SLICES 4       // a batch of 4 096 proofs or more is uploaded in up to this many slices (ctx->ev_slice)
 
 // ---- options (bpmi_set_option, include/bpmi.h); bpmi_ctx inherits them, so ctx->opt_c is this opt_c ----------------------------
 struct BpmiOptions {

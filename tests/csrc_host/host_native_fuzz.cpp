@@ -9,6 +9,9 @@
 //   host_pool.hpp         the sleeping worker pool those loops run on: concurrent callers, nested loops, every width
 //   msm_plan_host.hpp     the plan of an MSM (geometry, workspace layout, reduction jobs, slices) over the sweep of
 //                         tests/test_msm_plan_cpu.py, through the flat arrays of msm_plan_flat.hpp; once per run
+//   rp_batch_plan_host.hpp  the plan of a batch preparation on the device (argument errors, the walk of the caller's offset table, buffer
+//                         layouts, rows, slices) over a random slice of the sweep of tests/test_rp_plan_cpu.py, through rp_plan_flat.hpp; the bound
+//                         of a format-2/3 expansion against what rpw::expand_v2 writes
 // Built by tests/test_host_native_sanitizers.py with -fsanitize=address,undefined (every output buffer is a heap block of
 // EXACTLY the documented size, so an overrun of one byte is a report) and again with -fsanitize=thread (the threaded entry
 // points with 1..8 threads).  Besides "no report" it checks what can be checked without an oracle: results do not depend on the
@@ -26,6 +29,7 @@
 #include "rp_wire_v2_host.hpp"
 #include "host_tail.hpp"
 #include "msm_plan_flat.hpp"
+#include "rp_plan_flat.hpp"
 
 static uint64_t rng_state = 0x9E3779B97F4A7C15ULL;
 static uint64_t rnd() { rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17; return rng_state; }
@@ -212,7 +216,7 @@ static const uint8_t GX[32] = {0x79, 0xBE, 0x66, 0x7E, 0xF9, 0xDC, 0xBB, 0xAC, 0
                                0x02, 0x9B, 0xFC, 0xDB, 0x2D, 0xCE, 0x28, 0xD9, 0x59, 0xF2, 0x81, 0x5B, 0x16, 0xF8, 0x17, 0x98};
 static const uint8_t GY[32] = {0x48, 0x3A, 0xDA, 0x77, 0x26, 0xA3, 0xC4, 0x65, 0x5D, 0xA4, 0xFB, 0xFC, 0x0E, 0x11, 0x08, 0xA8,
                                0xFD, 0x17, 0xB4, 0x48, 0xA6, 0x85, 0x54, 0x19, 0x9C, 0x47, 0xD0, 0x8F, 0xFB, 0x10, 0xD4, 0xB8};
-static std::vector<uint8_t> random_v2(uint32_t k, bool v3 = false) {
+static std::vector<uint8_t> random_v2(uint32_t k, bool v3 = false, size_t max_seed = 40) {
   std::vector<uint8_t> b = {'B', 'P', 'R', 'P', (uint8_t)(v3 ? '3' : '2'), (uint8_t)k};
   std::vector<uint8_t> ys;
   uint8_t sc32[32];
@@ -232,7 +236,7 @@ static std::vector<uint8_t> random_v2(uint32_t k, bool v3 = false) {
   }
   for (int j = 0; j < 4; j++) put_scalar();
   for (int s = 0; s < 2; s++) {
-    const size_t sl = rnd() % 3 == 0 ? 0 : rnd() % 40;
+    const size_t sl = rnd() % 3 == 0 ? 0 : rnd() % max_seed;
     b.push_back((uint8_t)(sl >> 8)); b.push_back((uint8_t)sl);
     for (size_t i = 0; i < sl; i++) b.push_back((uint8_t)rnd());
   }
@@ -379,6 +383,58 @@ static void test_msm_plan() {
       }
 }
 
+// The batch verifier's planner on the table and the bytes of a caller it does not trust: the offset table and the blobs lie in heap
+// blocks of exactly their sizes, so a read past either is a report; a table that decreases or leaves the buffer is refused; what
+// a plan lays out stays inside what it asks for (the full list of invariants: tests/test_rp_plan_cpu.py).
+static void test_rp_plan() {
+  static const uint32_t gens[][2] = {{2, 1}, {2, 2}, {8, 1}, {8, 8}, {64, 1}, {64, 4}, {1024, 16}, {65536, 1}, {65536, 1024}, {8, 3}, {96, 1}, {0, 0}, {131072, 1}};
+  static const uint64_t proofs[] = {1, 2, 63, 64, 65, 4095, 4096, 4100, 0, (1ull << 22) + 1};
+  const auto &ge = gens[rnd() % 13];
+  const uint64_t P = proofs[rnd() % 10], Ptab = P && P <= 4100 ? P : 1;      // (beyond 2^22 and at 0 the table is never walked: one proof's worth is there)
+  const int fmt = 1 + (int)(rnd() % 3);
+  std::vector<uint64_t> t(Ptab + 1);
+  t[0] = rnd() % 4 == 0 ? rnd() % 7 : 0;
+  for (uint64_t g = 0; g < Ptab; g++) t[g + 1] = t[g] + (rnd() % 9 == 0 ? rnd() % 40000 : 500 + rnd() % 700);
+  uint64_t blobs_len = t[Ptab];
+  const int damage = (int)(rnd() % 6);                          // 0, 1: none
+  if (damage == 2) t[rnd() % (Ptab + 1)] = blobs_len + 1 + rnd() % 3;
+  if (damage == 3 && blobs_len) blobs_len -= 1 + rnd() % std::min<uint64_t>(blobs_len, 3);
+  if (damage == 4) { const uint64_t g = rnd() % Ptab; if (t[g + 1]) t[g] = t[g + 1] + 1; }
+  if (damage == 5) t[rnd() % (Ptab + 1)] = ~0ull - rnd() % 3;
+  Buf table(8 * (Ptab + 1)), blobs((size_t)blobs_len), out(8 * RP_PLAN_WORDS), msg(64);
+  memcpy(table.p, t.data(), table.n);
+  if (blobs.n >= t[0] + 5 && damage < 2) { memcpy(blobs.p + t[0], "BPRP", 4); blobs.p[t[0] + 4] = (uint8_t)('0' + fmt); }
+  const int32_t kv[10] = {0, (int32_t)(rnd() % 3 ? 0 : 1 + rnd() % 100), 1, (int32_t)(rnd() % 2 ? 0 : 1 << (rnd() % 7)), 2, (int32_t)(rnd() % 5), 3, (int32_t)(rnd() % 2),
+                          4, (int32_t)(rnd() % 3)};
+  const uint64_t group = rnd() % 2 ? 0 : (rnd() % 3 ? 1 + rnd() % 9 : P + rnd() % 3);
+  const int weights = (int)(rnd() % 2);
+  uint64_t *w = (uint64_t *)out.p;
+  const int rc = rp_plan_flat(kv, 5, ge[0], ge[1], P, blobs.p, blobs_len, (const uint64_t *)table.p, weights, group, w, (char *)msg.p, msg.n);
+  const bool args_ok = ge[0] >= 2 && ge[0] <= 65536 && !(ge[0] & (ge[0] - 1)) && ge[1] >= 1 && ge[0] % ge[1] == 0 && P >= 1 && P <= (1ull << 22);
+  bool table_ok = t[0] <= blobs_len;
+  for (uint64_t g = 0; g < Ptab; g++) table_ok &= t[g] <= t[g + 1] && t[g + 1] <= blobs_len;
+  CHECK((rc == 0) == (args_ok && table_ok));
+  CHECK(rc == 0 || (rc == BPMI_E_ARG && msg.p[0] != 0 && strlen((const char *)msg.p) < msg.n));
+  if (rc == 0) {
+    const uint64_t *region = w + 16, need = w[40], rows = w[43], nsl = w[49];
+    CHECK(w[12] >= blobs_len + 128 && w[14] + RP_ROLES * P <= w[15]);                       // stage-in: the blobs' slack, the status bytes
+    uint64_t pos = 0;
+    for (int i = 0; i < (group ? RP_PLAN_NREGIONS : 5); i++) { CHECK(region[2 * i] % 256 == 0 && region[2 * i] >= pos); pos = region[2 * i] + region[2 * i + 1]; }
+    CHECK(pos == need && w[38] + 8 <= w[39] && w[39] + 32 * (3 + 2 * (uint64_t)ge[0]) <= region[4] + region[5]);
+    CHECK(rows >= 1 && rows <= P && (rows == 1 || rows * w[41] <= (256ull << 20)) && (!kv[1] || rows <= (uint64_t)kv[1]));
+    CHECK(nsl >= 1 && nsl <= RP_UPLOAD_SLICES && w[50] == 0 && w[52] == 0 && w[50 + 4 * (nsl - 1) + 1] == P && w[50 + 4 * (nsl - 1) + 3] == blobs_len);
+    for (uint64_t c = 0; c + 1 < nsl; c++) CHECK(w[50 + 4 * c + 1] == w[50 + 4 * c + 4] && w[50 + 4 * c + 3] == w[50 + 4 * c + 6] && w[50 + 4 * c + 2] <= w[50 + 4 * c + 3]);
+  }
+  // the expansion bound from the LENGTH of a proof alone: never below what the expander writes, with seeds of up to 9 000 bytes
+  const uint32_t k = (uint32_t)(rnd() % 17);
+  const bool v3 = rnd() % 2 == 0;
+  static const size_t seed_max[] = {1, 3, 40, 300, 9001};
+  const std::vector<uint8_t> pr = random_v2(k, v3, seed_max[rnd() % 5]);
+  std::vector<uint8_t> one;
+  CHECK(rpw::expand_v2(pr.data(), pr.size(), one));
+  CHECK(rp_expansion_bound(pr.size(), k, v3 ? '3' : '2') >= one.size());
+}
+
 int main(int argc, char **argv) {
   const long iters = argc > 1 ? atol(argv[1]) : 200;
   if (argc > 2) rng_state ^= (uint64_t)atoll(argv[2]) * 0x9E3779B97F4A7C15ULL;
@@ -390,6 +446,7 @@ int main(int argc, char **argv) {
     test_host_tail();
     if (it % 8 == 0) test_host_pool();
     for (int r = 0; r < 8; r++) test_wire_v2();
+    for (int r = 0; r < 4; r++) test_rp_plan();
   }
   printf("host_native_fuzz: %ld iterations, %d failed checks\n", iters, fails);
   return fails ? 1 : 0;

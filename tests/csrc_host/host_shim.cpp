@@ -12,6 +12,7 @@
 #include "rp_batch_host.hpp"
 #include "host_tail.hpp"
 #include "msm_plan_flat.hpp"
+#include "rp_plan_flat.hpp"
 using namespace bpmi;
 
 static void load_fe(fe &r, const uint8_t *b) { u32 w[8]; memcpy(w, b, 32); fe_from_words(r, w); }
@@ -307,4 +308,11 @@ uint32_t t_msm_plan(const int32_t *kv, int nkv, uint64_t n, uint32_t w0, uint32_
 uint64_t t_msm_slices(const int32_t *kv, int nkv, const uint32_t *nseg, const uint64_t *pts, const uint64_t *sc, uint64_t cap, uint64_t *out) {
   return plan_flat_slices(kv, nkv, nseg, pts, sc, cap, out);
 }
+// the batch verifier's planner (csrc/rp_batch_plan_host.hpp) as flat arrays: rp_plan_flat.hpp says what is where
+int t_rp_plan(const int32_t *kv, int nkv, uint32_t n_gens, uint32_t m, uint64_t n_proofs, const uint8_t *blobs, uint64_t blobs_len, const uint64_t *blob_off,
+              int has_weights, uint64_t group, uint64_t *out, char *msg, uint64_t msg_cap) {
+  return rp_plan_flat(kv, nkv, n_gens, m, n_proofs, blobs, blobs_len, blob_off, has_weights, group, out, msg, (size_t)msg_cap);
+}
+void t_rp_group_chunk(uint32_t group, uint32_t base, uint32_t cnt, uint32_t *out) { rp_group_chunk_flat(group, base, cnt, out); }
+uint64_t t_rp_expansion_bound(uint64_t len, uint32_t k, int fmt) { return rp_expansion_bound(len, k, (uint8_t)fmt); }
 }

@@ -15,7 +15,7 @@ from bulletproofs_amd.rangeproofs.codec import proof_to_bytes
 
 from helpers import Q
 from test_batch_verify_cpu import make_batch, oracle_msm
-from test_gpu_batch_dev import _v2, _v3, offsets_of
+from test_gpu_batch_dev import _v2, _v3, dev_prepare, offsets_of
 
 pytestmark = pytest.mark.gpu
 
@@ -258,6 +258,40 @@ def test_row_chunks_do_not_change_the_group_values(eng, batch):
         assert group_values(batch, Vs, blobs, ws, 4) == want
     finally:
         eng.set_option("rp_rows", 0)
+
+
+@pytest.mark.parametrize("fmt", ["v1", "v2", "v3"])
+def test_overlap_off_never_changes_a_result(eng, batch, fmt):
+    """Option rp_overlap = 0 (tools and the benchmark library set it for measurements) moves the point decoding from the second lane
+    to the ctx stream: behind the preparation kernels, and in group mode in FRONT of them, since k_rp_verdict reads the flags the
+    decoding sets.  9 proofs of n = 8, once clean and once with an invalid point encoding in proof 6 (format 3: and a wrong y in proof
+    2), through bpmi_rp_batch_prepare_dev and through the group values (groups of 4 over row chunks of 5 + 4, one wrong commitment):
+    scalars, coefficients, points, verdicts, values and status bytes are the same bytes as with the default."""
+    Vs, clean = list(batch["Vs"][:9]), list(batch[fmt][:9])
+    Vs[4] = batch["Vs"][0]
+    broken = list(clean)
+    broken[6] = off_curve_point(clean[6])
+    if fmt == "v3":
+        broken[2] = wrong_y(clean[2])
+    flagged = [2, 6] if fmt == "v3" else [6]
+    ws, seed = weights_for(9, 61), b"\x47" * 32
+
+    def run():
+        return [(dev_prepare(eng, 8, 1, blobs, None, seed), group_values(batch, Vs, blobs, ws, 4)) for blobs in (clean, broken)]
+    try:
+        eng.set_option("rp_rows", 5)
+        want = run()
+        eng.set_option("rp_overlap", 0)
+        got = run()
+    finally:
+        eng.set_option("rp_overlap", 1)
+        eng.set_option("rp_rows", 0)
+    for res in (want, got):
+        (prep, (values, status)), (prep_b, (values_b, status_b)) = res
+        assert prep[:2] == (0, -1) and status == bytes(9) and values[0] == ZERO and values[1] != ZERO
+        assert prep_b[:2] == (0, flagged[0]) and [i for i in range(9) if status_b[i]] == flagged and all(status_b[i] & 2 for i in flagged)
+        assert values_b == expected_values(batch, Vs, broken, ws, 4, skip=flagged)
+    assert got == want
 
 
 @pytest.mark.parametrize("group", [37, 38, 648, 649])
