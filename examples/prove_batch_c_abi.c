@@ -12,7 +12,7 @@
  * The generators here are multiples of the curve's base point (a demonstration, not a setup ceremony).  spoil = 1 changes one
  * commitment after proving: the batch must be rejected.  values_per_proof > 1 (round 6): AGGREGATED proofs -- a loop of
  * AggregNIRangeProver (/root/reference/src/rangeproofs/rangeproof_aggreg_prover.py:36-146) over proofs of that many values of `bits`
- * bits each (bits x values <= 128), bpmi_rp_prover_create_aggregated.  Exit code 0: proved and verified; 1: the batch did not verify; 2: error. */
+ * bits each (bits x values <= 1024), bpmi_rp_prover_create_aggregated.  Exit code 0: proved and verified; 1: the batch did not verify; 2: error. */
 #define _POSIX_C_SOURCE 200809L
 #include <stdio.h>
 #include <stdlib.h>

@@ -117,9 +117,14 @@ int bpmi_sync(bpmi_ctx *ctx);
  *                  (0 = default 4096, 1 = never, else a power of two; the later rounds then run on the one-launch small-MSM kernel)
  *   "pair_phases"  1: bpmi_msm2 on the bucket pipeline queues both MSMs' sorts before either accumulation.  An experiment that came out
  *                  neutral (profiles/r04_C3_pair_phases_ab.txt); default 0
- *   "prover_table_bits" window bits of the fixed-base tables a bpmi_rp_prover builds, read by bpmi_rp_prover_create: 0 = default 16, else 4 .. 16
+ *   "prover_table_bits" window bits of the fixed-base tables a bpmi_rp_prover builds, read by bpmi_rp_prover_create: 0 = default, else 4 .. 16
  *                  (wider: fewer additions per scalar multiplication, a larger table -- 16 bits: 64 KB x 32 768 entries per (generator, window),
- *                  4.4 GB and 72 ms to build for 64-bit proofs; 12 bits: 378 MB, 17 ms, 22 % slower proving; profiles/r06_batch_prover_table_bits.txt)
+ *                  4.4 GB and 72 ms to build for 64-bit proofs; 12 bits: 378 MB, 17 ms, 22 % slower proving; profiles/r06_batch_prover_table_bits.txt).
+ *                  Default: 16 for proofs of up to 128 elements (bits x values); above, the widest width whose table -- (3 + 2 elements) x
+ *                  ceil(256 / w) x 2^(w-1) x 64 B -- is no larger than the 8.7 GB of 128 elements at 16 bits: 14 bits at 256 elements (5.1 GB),
+ *                  13 at 512, 12 at 1 024 (csrc/rp_prove_plan_host.hpp)
+ *   "prover_job_lanes" lanes bpmi_rp_prove_batch gives a multi-scalar multiplication of a proof: 0 (default) automatic -- 16, and a wave of 64 in
+ *                  launches of few jobs of proofs of more than 128 elements (profiles/r07_batch_prover_wide.txt) --, 16 or 64 forced
  *   "rp_priority"  the batch preparation's chain kernels (expander, roles, elements) raise their waves' issue priority: 0 never, 1 (default) on wire
  *                  formats 1 and 2, where the point decoding's square roots run beside them (format 2: a batch alone 1.72 -> 1.66 ms, ten in
  *                  flight +2.4-2.8 %), 2 always (format 3: nothing; profiles/r06_C5_preparation_priority_ab.txt)
@@ -417,20 +422,24 @@ int bpmi_rp_batch_group_values_dev(bpmi_ctx *ctx, uint32_t n_gens, uint32_t valu
  * of the fixed generators, and the Fiat-Shamir hashes run on the device.
  *   bpmi_rp_prover_create   nbits: a power of two in [2, 128]; g, h, u: 64-byte points; gs, hs: nbits points each.  Builds the tables
  *                           (windows of "prover_table_bits" bits, default 16: 4.4 GB of device memory and ~72 ms for 64-bit proofs;
- *                           12 bits: 378 MB, 17 ms, 22 % slower proving) and keeps them for the prover's lifetime.
+ *                           12 bits: 378 MB, 17 ms, 22 % slower proving) and keeps them for the prover's lifetime.  A table that does
+ *                           not fit the device is BPMI_E_NOMEM.
  *                           The points are checked to be on the curve (option "validate_points" >= 1, the default): BPMI_E_ARG names the first bad one.
  *   bpmi_rp_prove_batch     values, gammas: n_proofs x 32 B little-endian, in [0, q) -- checked: BPMI_E_ARG names the first index that is not -- (of a value only the low nbits bits enter the
  *                           proof, as in rangeproof_prover.py:40); seeds: proof i's transcript seed = seeds[seed_off[i] .. seed_off[i+1])
  *                           (at most 65 535 bytes).  out[out_off[i] .. out_off[i+1]) = proof i in wire format 2 (3 under option "prover_wire_format")
  *                           (python-bulletproofs_amd/rangeproofs/codec.py; bpmi_rp_wire_v2_to_v1 expands it, bpmi_rp_batch_verify_dev
  *                           takes it as it is); out_off has n_proofs + 1 entries; cap >= n_proofs x bpmi_rp_prove_batch_proof_bytes
- *                           (of the longest seed).  At most 2^20 proofs per call; one call at a time per prover and ctx.
+ *                           (of the longest seed).  At most 2^20 proofs and 2^27 elements (n_proofs x nbits x m) per call -- beyond
+ *                           either BPMI_E_ARG names the bound, before anything is read or allocated; one call at a time per prover and ctx.
  *   bpmi_rp_prover_last_ms  device milliseconds of the last batch: A and S | y, z, T1, T2 | x, the vectors, P_new | the rounds of the
  *                           inner-product argument | the wire bytes | their copy to the host | the whole batch */
 /* The same for AGGREGATED proofs (round 6): a proof covers m values of nbits bits each (AggregNIRangeProver,
- * /root/reference/src/rangeproofs/rangeproof_aggreg_prover.py:36-146); nbits and m powers of two with 2 <= nbits x m <= 128, gs and hs nbits x m
+ * /root/reference/src/rangeproofs/rangeproof_aggreg_prover.py:36-146); nbits (at most 128) and m powers of two with 2 <= nbits x m <= 1024 --
+ * 4, 8 or 16 amounts of 64 bits are 256, 512 or 1 024 elements --, gs and hs nbits x m
  * points each; bpmi_rp_prove_batch then takes n_proofs x m values and blinding factors (proof p: entries p m .. p m + m - 1).  m = 1 is
- * bpmi_rp_prover_create.  Longer vectors (the 128 x 64-bit proof of config C4) are the single-proof prover's: one proof fills the chip there. */
+ * bpmi_rp_prover_create.  The kernels with a lane per element run in blocks of 256 threads up to 256 elements, of 512 and 1 024 above.
+ * Longer vectors (the 128 x 64-bit proof of config C4) are the single-proof prover's: one proof fills the chip there. */
 int bpmi_rp_prover_create_aggregated(bpmi_ctx *ctx, uint32_t nbits, uint32_t m, const uint8_t g[64], const uint8_t h[64], const uint8_t u[64], const uint8_t *gs,
                                      const uint8_t *hs, bpmi_rp_prover **out);
 int bpmi_rp_prover_create(bpmi_ctx *ctx, uint32_t nbits, const uint8_t g[64], const uint8_t h[64], const uint8_t u[64], const uint8_t *gs, const uint8_t *hs,
@@ -440,6 +449,14 @@ uint64_t bpmi_rp_prove_batch_proof_bytes(const bpmi_rp_prover *pv, uint64_t seed
 int bpmi_rp_prove_batch(bpmi_rp_prover *pv, uint64_t n_proofs, const uint8_t *values, const uint8_t *gammas, const uint8_t *seeds, const uint64_t *seed_off,
                         uint8_t *out, uint64_t cap, uint64_t *out_off);
 int bpmi_rp_prover_last_ms(const bpmi_rp_prover *pv, double ms[7]);
+/* out[i] = values[i] g + gammas[i] h: `commitment(g, h, x, r)` (/root/reference/src/utils/commitments.py:5-6) for count pairs
+ * in one launch, from the prover's fixed-base tables of g and h (the path T1 and T2 take) -- the commitments V every verifier of the
+ * prover's proofs needs, in the order bpmi_rp_batch_verify_dev takes them (an aggregated prover: count = n_proofs x m).
+ * values, gammas: count x 32 B little-endian in [0, q), checked like bpmi_rp_prove_batch's: BPMI_E_ARG names the first index that is not.
+ * The WHOLE value enters the commitment, not only its low nbits bits -- what makes the proof of an out-of-range value fail.
+ * out: count x 64 B affine (x, y little-endian; the identity is 64 zero bytes).  count <= 2^24; count = 0 is BPMI_OK.  Shares the
+ * prover's buffers: one call at a time per prover, like proving. */
+int bpmi_rp_prover_commit_batch(bpmi_rp_prover *pv, uint64_t count, const uint8_t *values, const uint8_t *gammas, uint8_t *out);
 
 /* Page-locked host memory (hipHostMalloc) for buffers handed to the library repeatedly, e.g. the receive buffer of wire proofs. */
 int bpmi_host_alloc(bpmi_ctx *ctx, size_t bytes, void **out);

@@ -49,6 +49,7 @@ using namespace bpmi;
 #include "shared_defs.hpp"
 #include "msm_plan_host.hpp"
 #include "rp_batch_plan_host.hpp"
+#include "rp_prove_plan_host.hpp"
 #include "context.hpp"
 #include "device_util.hpp"
 #include "msm_kernels.hpp"
@@ -157,6 +158,7 @@ int bpmi_set_option(bpmi_ctx *ctx, const char *name, int64_t value) {
   if (!strcmp(name, "mid_parts")) { if (value < 0 || value > 4) return fail(ctx, BPMI_E_ARG, "mid_parts must be 0 .. 4"); ctx->opt_mid_parts = (int)value; msm_graphs_clear(ctx); return BPMI_OK; }
   if (!strcmp(name, "mixed_windows")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "mixed_windows must be 0 or 1"); ctx->opt_mixed = (int)value; msm_graphs_clear(ctx); return BPMI_OK; }
   if (!strcmp(name, "top_window_unsigned")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "top_window_unsigned must be 0 or 1"); ctx->opt_top2 = (int)value; msm_graphs_clear(ctx); return BPMI_OK; }
+  if (!strcmp(name, "prover_job_lanes")) { if (value != 0 && value != 16 && value != 64) return fail(ctx, BPMI_E_ARG, "prover_job_lanes must be 0, 16 or 64"); ctx->opt_prover_job_lanes = (int)value; return BPMI_OK; }
   if (!strcmp(name, "prover_table_bits")) { if (value != 0 && (value < 4 || value > 16)) return fail(ctx, BPMI_E_ARG, "prover_table_bits must be 0 or 4..16"); ctx->opt_prover_tw = (int)value; return BPMI_OK; }
   if (!strcmp(name, "ipa_fixed_generators")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "ipa_fixed_generators must be 0 or 1"); ctx->opt_ipa_fixed = (int)value; ctx->fold_key_g = ctx->fold_key_h = nullptr; return BPMI_OK; }
   if (!strcmp(name, "validate_points")) { if (value < 0 || value > 2) return fail(ctx, BPMI_E_ARG, "validate_points must be 0, 1 or 2"); ctx->opt_validate = (int)value; return BPMI_OK; }

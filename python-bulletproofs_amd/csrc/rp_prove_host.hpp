@@ -5,10 +5,11 @@
 #pragma once
 
 #define PV_SPLIT_MIN 2048u               // a batch of 2 x this many proofs or more runs as two halves on two lanes
-#define PROVER_TW_DEFAULT 16u          // 16 additions per term, 4.4 GB and 72 ms to build for 64-bit proofs (profiles/r06_batch_prover_table_bits.txt); 12: 22 additions, 378 MB, 17 ms
 struct bpmi_rp_prover {
   bpmi_ctx *ctx = nullptr;
   u32 n = 0, k = 0, nbases = 0;                // n: elements of a proof's vectors = nb m
+  u32 NT = 256;                                // threads of a block of the n-lanes-per-proof kernels (rp_prove_plan_host.hpp)
+  uint64_t max_proofs = 0;                     // per call (rpp_batch_error)
   u32 nb = 0, m = 1;                           // bits per value, values per proof (m > 1: aggregated proofs)
   u32 *table = nullptr;                        // [(3 + 2n)][wt][bt] affine points
   u32 tw = 16, wt = 16, bt = 32768;            // table windows: tw bits, wt = ceil(256 / tw) per scalar, bt = 2^(tw-1) entries each
@@ -89,9 +90,9 @@ static int rp_prover_create_impl(bpmi_ctx *ctx, uint32_t vbits, uint32_t m, cons
                                  bpmi_rp_prover **out, bpmi_rp_prover *&partial) {
   if (!ctx || !g || !h || !u || !gs || !hs || !out) return ctx ? fail(ctx, BPMI_E_ARG, "null argument") : BPMI_E_ARG;
   *out = nullptr;
-  if (vbits < 1 || vbits > 128 || (vbits & (vbits - 1)) || m < 1 || (m & (m - 1)) || (uint64_t)vbits * m < 2 || (uint64_t)vbits * m > 128)
-    return fail(ctx, BPMI_E_ARG, "the bit width and the number of values must be powers of two with 2 <= bits x values <= 128");
-  const uint32_t nbits = vbits * m;                      // elements of a proof's vectors
+  const RppPlan plan = rpp_plan(vbits, m, ctx->opt_prover_tw);        // (option "prover_table_bits" is read HERE)
+  if (plan.err) return fail(ctx, plan.err, plan.msg);
+  const uint32_t nbits = plan.n;                         // elements of a proof's vectors
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (ctx->opt_validate >= 1) {
     int vrc = validate_host(ctx, g, 1, "bpmi_rp_prover_create", "g");
@@ -103,9 +104,9 @@ static int rp_prover_create_impl(bpmi_ctx *ctx, uint32_t vbits, uint32_t m, cons
   }
   bpmi_rp_prover *pv = new bpmi_rp_prover();
   partial = pv;
-  pv->ctx = ctx; pv->n = nbits; pv->nb = vbits; pv->m = m; pv->k = 0;
-  while ((1u << pv->k) < nbits) pv->k++;
-  const u32 n = nbits, nb = 3 + 2 * n;
+  pv->ctx = ctx; pv->n = nbits; pv->nb = vbits; pv->m = m; pv->k = plan.k;
+  pv->NT = plan.NT; pv->max_proofs = plan.max_proofs;
+  const u32 n = nbits, nb = plan.nbases;
   pv->nbases = nb;
   auto bail = [&](int rc) { bpmi_rp_prover_destroy(pv); partial = nullptr; return rc; };
   for (int i = 0; i < 7; i++) { hipError_t ee = hipEventCreate(&pv->ev[i]); if (ee != hipSuccess) return bail(fail(ctx, BPMI_E_HIP, std::string("bpmi_rp_prover_create: ") + hipGetErrorString(ee))); }
@@ -125,12 +126,11 @@ static int rp_prover_create_impl(bpmi_ctx *ctx, uint32_t vbits, uint32_t m, cons
     pv->ip_prefix = "&&" + rpp_host::decimal_of(le) + "&";
   }
   // points of the bases, the table's inputs and the table: entry (b, k, d) = d 2^(8k) base_b by the engine's batched multiplication
-  // table windows (ctx option "prover_table_bits", read HERE): wider windows are fewer additions per term and a larger table
+  // table windows (ctx option "prover_table_bits"; the default by size: rpp_default_table_bits): wider windows are fewer additions per term and a larger table
   // (measured at 2^14 64-bit proofs, profiles/r05_batch_prover_table_bits.txt: 8 bits 36.0 ms / 34 MB / 16 ms to build, 10: 31.0 / 112 / 29,
   // 11: 29.3 / 206 / 44, 12: 28.1 / 378 / 72, 13: 26.6 / 687 / 126 with round 5's builder; round 6's builder and 14 .. 16 bits:
   // profiles/r06_batch_prover_table_bits.txt)
-  pv->tw = ctx->opt_prover_tw ? (u32)ctx->opt_prover_tw : PROVER_TW_DEFAULT;
-  pv->wt = (256u + pv->tw - 1u) / pv->tw; pv->bt = 1u << (pv->tw - 1u);
+  pv->tw = plan.tw; pv->wt = plan.wt; pv->bt = plan.bt;
   const size_t entries = (size_t)nb * pv->wt * pv->bt;
   const u32 nbk = nb * pv->wt;                       // (base, window) pairs
   std::vector<uint8_t> basepts(64 * (size_t)nb);
@@ -173,27 +173,9 @@ static int rp_prover_create_impl(bpmi_ctx *ctx, uint32_t vbits, uint32_t m, cons
   }
   free_tmp();
   if (rc) return bail(rc);
-  // base lists: S / P_new: gs_0.., hs_0.., then h (S) or u (P_new); T: g, h; round r: L then R (rp_prove_kernels.hpp k_pv_round_wide)
-  std::vector<unsigned short> bl;
-  pv->off_S = 0;
-  for (u32 i = 0; i < n; i++) bl.push_back((unsigned short)(3 + i));
-  for (u32 i = 0; i < n; i++) bl.push_back((unsigned short)(3 + n + i));
-  bl.push_back(1);
-  pv->off_T = (u32)bl.size();
-  bl.push_back(0); bl.push_back(1);
-  pv->off_P = (u32)bl.size();
-  for (u32 i = 0; i < n; i++) bl.push_back((unsigned short)(3 + i));
-  for (u32 i = 0; i < n; i++) bl.push_back((unsigned short)(3 + n + i));
-  bl.push_back(2);
-  pv->off_round = (u32)bl.size();
-  for (u32 r = 0; r < pv->k; r++) {
-    const u32 len = n >> r, half = len >> 1;
-    for (int side = 0; side < 2; side++) {               // 0: L, 1: R
-      for (u32 j = 0; j < n; j++) if (((j & (len - 1)) >= half) == (side == 0)) bl.push_back((unsigned short)(3 + j));
-      for (u32 j = 0; j < n; j++) if (((j & (len - 1)) < half) == (side == 0)) bl.push_back((unsigned short)(3 + n + j));
-      bl.push_back(2);
-    }
-  }
+  // the base lists of every job kind (rpp_plan)
+  const std::vector<unsigned short> &bl = plan.bases;
+  pv->off_S = plan.off_S; pv->off_T = plan.off_T; pv->off_P = plan.off_P; pv->off_round = plan.off_round;
   e = hipMalloc(&pv->bases, 2 * bl.size());
   if (e == hipSuccess) e = hipMemcpy(pv->bases, bl.data(), 2 * bl.size(), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMalloc(&pv->d_ip_prefix, pv->ip_prefix.size() + 16);
@@ -231,9 +213,11 @@ static int rp_prove_batch_impl(bpmi_rp_prover *pv, uint64_t n_proofs, const uint
                                uint8_t *out, uint64_t cap, uint64_t *out_off) {
   if (!pv) return BPMI_E_ARG;
   bpmi_ctx *ctx = pv->ctx;
-  if (!values || !gammas || !seed_off || !out || !out_off || (!seeds && seed_off[n_proofs] != seed_off[0])) return fail(ctx, BPMI_E_ARG, "null argument");
+  if (!values || !gammas || !seed_off || !out || !out_off) return fail(ctx, BPMI_E_ARG, "null argument");
   if (n_proofs == 0) { out_off[0] = 0; return BPMI_OK; }
-  if (n_proofs > (1u << 20)) return fail(ctx, BPMI_E_ARG, "at most 2^20 proofs per call");
+  // the per-call caps come first: nothing of a batch beyond them is read or allocated
+  if (const char *over = rpp_batch_error(pv->max_proofs, n_proofs)) return fail(ctx, BPMI_E_ARG, over);
+  if (!seeds && seed_off[n_proofs] != seed_off[0]) return fail(ctx, BPMI_E_ARG, "null argument");
   // the reference's prover takes ModP values: reduced by construction (/root/reference/src/utils/utils.py:24-27); raw bytes are checked here
   for (uint64_t p = 0; p < n_proofs * pv->m; p++) {
     if (!rp_scalar_reduced(values + 32 * p)) return fail(ctx, BPMI_E_ARG, "bpmi_rp_prove_batch: values[" + std::to_string(p) + "] is not below the group order");
@@ -336,8 +320,17 @@ static int rp_prove_batch_impl(bpmi_rp_prover *pv, uint64_t n_proofs, const uint
   // [kernels before] [ONE multi-scalar multiplication] [kernels behind]; with two halves (`other` set) the multiplication waits for the other
   // half's previous one and is followed by an event of its own: the additions of the two halves alternate on the chip, and a half's
   // one-lane-per-proof chains (hash, inversion) run beside the OTHER half's additions instead of beside their own twin's.
-  const u32 per_block = 256u / n;                        // proofs per block of the n-lanes-per-proof kernels
+  const u32 NT = pv->NT, per_block = NT / n;             // proofs per block of the n-lanes-per-proof kernels
+  const int job_lanes = ctx->opt_prover_job_lanes;       // 0: by the launch's job count (rpp_job_lanes_log2)
   const u32 nsteps = 4 + k;
+  // an n-lanes-per-proof kernel in the instantiation of the prover's block size
+#define PV_WIDE(kern, ...)                                                                                                           \
+  do {                                                                                                                               \
+    const dim3 grid_((Pc + per_block - 1) / per_block);                                                                              \
+    if (NT == 256u) hipLaunchKernelGGL(rpp::kern<256>, grid_, dim3(256), 0, hs, __VA_ARGS__);                                        \
+    else if (NT == 512u) hipLaunchKernelGGL(rpp::kern<512>, grid_, dim3(512), 0, hs, __VA_ARGS__);                                   \
+    else hipLaunchKernelGGL(rpp::kern<1024>, grid_, dim3(1024), 0, hs, __VA_ARGS__);                                                 \
+  } while (0)
   auto step = [&](Half &h, u32 sidx, hipEvent_t mine, hipEvent_t other) {
     rpp::Batch &H = h.H;
     hipStream_t hs = h.st;
@@ -347,7 +340,8 @@ static int rp_prove_batch_impl(bpmi_rp_prover *pv, uint64_t n_proofs, const uint
       J.njobs = njobs; J.ntypes = ntypes; J.T = T; J.bases = pv->bases + base_off; J.scalars = scalars; J.stride = stride; J.out = H.jout;
       const uint64_t threads = (uint64_t)njobs << gl;
       if (other) (void)hipStreamWaitEvent(hs, other, 0);
-      if (gl == 4) hipLaunchKernelGGL(rpp::k_pv_msm<4>, blocks(threads, 256), dim3(256), 0, hs, J, H.table);
+      if (gl == 6) hipLaunchKernelGGL(rpp::k_pv_msm<6>, blocks(threads, 256), dim3(256), 0, hs, J, H.table);
+      else if (gl == 4) hipLaunchKernelGGL(rpp::k_pv_msm<4>, blocks(threads, 256), dim3(256), 0, hs, J, H.table);
       else hipLaunchKernelGGL(rpp::k_pv_msm<1>, blocks(threads, 256), dim3(256), 0, hs, J, H.table);
       if (mine) (void)hipEventRecord(mine, hs);
     };
@@ -359,34 +353,35 @@ static int rp_prove_batch_impl(bpmi_rp_prover *pv, uint64_t n_proofs, const uint
       hipLaunchKernelGGL(rpp::k_pv_blind, blocks((uint64_t)Pc * (2 * n + 2), 256), dim3(256), 0, hs, H);
       hipLaunchKernelGGL(rpp::k_pv_commit_A, blocks((uint64_t)Pc * 16, 256), dim3(256), 0, hs, H, H.jout);
       affine(Pc, 1, PV_PT_A, 0);
-      msm(Pc, 1, 2 * n + 1, pv->off_S, H.slr, 2 * n + 1, 4);
+      msm(Pc, 1, 2 * n + 1, pv->off_S, H.slr, 2 * n + 1, rpp_job_lanes_log2(n, Pc, job_lanes));
       affine(Pc, 1, PV_PT_S, 0);
       if (h.rec) (void)hipEventRecord(ev[1], hs);
     } else if (sidx == 1) {                              // y, z, tau1, tau2; t1, t2; T1, T2 (:60-67)
       hipLaunchKernelGGL(rpp::k_pv_chal_yz, blocks(Pc, 64), dim3(64), 0, hs, H);
-      hipLaunchKernelGGL(rpp::k_pv_poly, dim3((Pc + per_block - 1) / per_block), dim3(256), 0, hs, H);
+      PV_WIDE(k_pv_poly, H);
       msm(2 * Pc, 1, 2, pv->off_T, H.tsc, 2, 1);
       affine(2 * Pc, 2, PV_PT_T1, 1);
       if (h.rec) (void)hipEventRecord(ev[2], hs);
     } else if (sidx == 2) {                              // x; l, r, t_hat, taux, mu; P_new (:68-90; inner_product_prover.py:33-37)
       hipLaunchKernelGGL(rpp::k_pv_final_chal, blocks(Pc, 64), dim3(64), 0, hs, H);
-      hipLaunchKernelGGL(rpp::k_pv_final_wide, dim3((Pc + per_block - 1) / per_block), dim3(256), 0, hs, H);
-      msm(Pc, 1, 2 * n + 1, pv->off_P, H.jsc, 2 * n + 1, 4);
+      PV_WIDE(k_pv_final_wide, H);
+      msm(Pc, 1, 2 * n + 1, pv->off_P, H.jsc, 2 * n + 1, rpp_job_lanes_log2(n, Pc, job_lanes));
       affine(Pc, 1, PV_PT_PNEW, 0);
       if (h.rec) (void)hipEventRecord(ev[3], hs);
-      hipLaunchKernelGGL(rpp::k_pv_round_wide, dim3((Pc + per_block - 1) / per_block), dim3(256), 0, hs, H, 0u, 1u);
+      PV_WIDE(k_pv_round_wide, H, 0u, 1u);
     } else if (sidx < 3 + k) {                           // a round of Protocol 2 (inner_product_prover.py:94-110)
       const u32 r = sidx - 3;
-      msm(2 * Pc, 2, n + 1, pv->off_round + r * 2 * (n + 1), H.jsc, n + 1, 4);
+      msm(2 * Pc, 2, n + 1, pv->off_round + r * 2 * (n + 1), H.jsc, n + 1, rpp_job_lanes_log2(n, 2 * (uint64_t)Pc, job_lanes));
       affine(2 * Pc, 2, 6 + r, k);
       hipLaunchKernelGGL(rpp::k_pv_round_chal, blocks(Pc, 64), dim3(64), 0, hs, H, r);
-      hipLaunchKernelGGL(rpp::k_pv_round_wide, dim3((Pc + per_block - 1) / per_block), dim3(256), 0, hs, H, r, 0u);
+      PV_WIDE(k_pv_round_wide, H, r, 0u);
     } else {
       if (h.rec) (void)hipEventRecord(ev[4], hs);
       hipLaunchKernelGGL(rpp::k_pv_emit, blocks(Pc, 64), dim3(64), 0, hs, H, (const unsigned char *)(d + o_seeds), (const uint64_t *)(d + o_soff) + h.p0,
                          (unsigned char *)(d + o_out), (const uint64_t *)(d + o_ooff) + h.p0, (u32)wire_fmt);
     }
   };
+#undef PV_WIDE
   const bool split = ctx->opt_prover_split && P >= 2u * (ctx->opt_prover_split > 1 ? (u32)ctx->opt_prover_split : PV_SPLIT_MIN);
   if (split) {
     int rc = ensure_lane(ctx, 1);
@@ -423,6 +418,59 @@ static int rp_prove_batch_impl(bpmi_rp_prover *pv, uint64_t n_proofs, const uint
   for (int i = 0; i < 6; i++) { float ms = 0; (void)hipEventElapsedTime(&ms, ev[i], ev[i + 1]); pv->last_ms[i] = ms; }
   { float ms = 0; (void)hipEventElapsedTime(&ms, ev[0], ev[6]); pv->last_ms[6] = ms; }
   return BPMI_OK;
+}
+
+// out[i] = values[i] g + gammas[i] h from the prover's tables: the pairs laid out as the scalars of count two-term jobs over the base
+// list T (g, h: what T1 and T2 run on), k_pv_msm<1>, k_pv_affine.  The prover's device and staging buffers are shared with proving.
+static int rp_prover_commit_batch_impl(bpmi_rp_prover *pv, uint64_t count, const uint8_t *values, const uint8_t *gammas, uint8_t *out) {
+  if (!pv) return BPMI_E_ARG;
+  bpmi_ctx *ctx = pv->ctx;
+  if (count == 0) return BPMI_OK;
+  if (!values || !gammas || !out) return fail(ctx, BPMI_E_ARG, "null argument");
+  if (count > PROVER_COMMIT_MAX) return fail(ctx, BPMI_E_ARG, "at most 2^24 commitments per call");
+  for (uint64_t i = 0; i < count; i++) {
+    if (!rp_scalar_reduced(values + 32 * i)) return fail(ctx, BPMI_E_ARG, "bpmi_rp_prover_commit_batch: values[" + std::to_string(i) + "] is not below the group order");
+    if (!rp_scalar_reduced(gammas + 32 * i)) return fail(ctx, BPMI_E_ARG, "bpmi_rp_prover_commit_batch: gammas[" + std::to_string(i) + "] is not below the group order");
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  using rpp_host::up256;
+  const u32 C = (u32)count;
+  const size_t o_val = 0, o_gam = up256(32ull * C), in_bytes = o_gam + up256(32ull * C);
+  const size_t o_jsc = in_bytes, o_jout = o_jsc + up256(64ull * C), o_pts = o_jout + up256(144ull * C), need = o_pts + up256(64ull * C);
+  if (need > pv->buf_bytes) {
+    if (pv->buf) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(pv->buf)); pv->buf = nullptr; pv->buf_bytes = 0; }
+    HIPCHK(ctx, hipMalloc(&pv->buf, need + need / 8));
+    pv->buf_bytes = need + need / 8;
+  }
+  const size_t pin_need = std::max(in_bytes, (size_t)(64ull * C));
+  if (pin_need > pv->pin_bytes) {
+    if (pv->pin) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipHostFree(pv->pin)); pv->pin = nullptr; pv->pin_bytes = 0; }
+    HIPCHK(ctx, hipHostMalloc(&pv->pin, pin_need + pin_need / 8, hipHostMallocDefault));
+    pv->pin_bytes = pin_need + pin_need / 8;
+  }
+  char *d = (char *)pv->buf, *hp = (char *)pv->pin;
+  hipStream_t st = ctx->stream;
+  memcpy(hp + o_val, values, 32ull * C);
+  memcpy(hp + o_gam, gammas, 32ull * C);
+  HIPCHK(ctx, hipMemcpyAsync(d, hp, in_bytes, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(rpp::k_pv_commit_pairs, dim3((2u * C + 255u) / 256u), dim3(256), 0, st, (const u32 *)(d + o_val), (const u32 *)(d + o_gam), C, (u32 *)(d + o_jsc));
+  rpp::MsmJobs J;
+  J.njobs = C; J.ntypes = 1; J.T = 2; J.bases = pv->bases + pv->off_T; J.scalars = (const u32 *)(d + o_jsc); J.stride = 2; J.out = (u32 *)(d + o_jout);
+  hipLaunchKernelGGL(rpp::k_pv_msm<1>, dim3((u32)((2ull * C + 255) / 256)), dim3(256), 0, st, J, rpp::Tab{pv->table, pv->tw, pv->wt, pv->bt});
+  hipLaunchKernelGGL(rpp::k_pv_affine, dim3((C + 255u) / 256u), dim3(256), 0, st, (const u32 *)(d + o_jout), C, 1u, (u32 *)(d + o_pts), 1u, 0u, 0u);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(hp, d + o_pts, 64ull * C, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return fail(ctx, BPMI_E_HIP, std::string("bpmi_rp_prover_commit_batch: ") + hipGetErrorString(e));
+  memcpy(out, hp, 64ull * C);
+  return BPMI_OK;
+}
+int bpmi_rp_prover_commit_batch(bpmi_rp_prover *pv, uint64_t count, const uint8_t *values, const uint8_t *gammas, uint8_t *out) {
+  try {
+    return rp_prover_commit_batch_impl(pv, count, values, gammas, out);
+  } catch (const std::bad_alloc &) {
+    return pv && pv->ctx ? fail(pv->ctx, BPMI_E_NOMEM, "bpmi_rp_prover_commit_batch: out of host memory") : BPMI_E_NOMEM;
+  }
 }
 
 int bpmi_rp_prover_last_ms(const bpmi_rp_prover *pv, double ms[7]) {

@@ -1,11 +1,12 @@
 // rp_prove_kernels.hpp -- part of libbpmi (included by bpmi.hip; one translation unit).  DEVICE code.
-// A BATCH of single-value range proofs over shared generators, proved on the GPU from the first blinding scalar to the wire bytes
+// A BATCH of range proofs (single-value, or aggregated: up to 1 024 elements) over shared generators, proved on the GPU from the first blinding scalar to the wire bytes
 // (SURVEY.md section 2.1 K11).  It replaces a loop of NIRangeProver.prove (/root/reference/src/rangeproofs/rangeproof_prover.py:35-91)
 // with NIProver.prove / FastNIProver2.prove inside (/root/reference/src/innerproduct/inner_product_prover.py:27-44, :84-110): the same
 // transcripts (/root/reference/src/utils/transcript.py:13-33), the same seeded scalars (mod_hash, /root/reference/src/utils/utils.py:84-97),
 // the same proof, byte for byte (tests/test_gpu_prove_batch.py compares every proof with the single-proof prover's).
 //
-// Shape of the work.  One proof is ~16 multi-scalar multiplications of 2 .. 129 terms and a dozen Fiat-Shamir hashes between them:
+// Shape of the work.  One proof is ~16 multi-scalar multiplications of 2 .. 129 terms (64-bit proofs; up to 2 049 terms and 24
+// multiplications for the widest, 1 024 elements) and a dozen Fiat-Shamir hashes between them:
 // per-proof launches made it 2.1 ms a proof (474 proofs/s, profiles/r04_rocprofv3_kernel_stats_C5_batch_verify_2e14.csv).  Here
 // every step is ONE launch over all proofs of the batch:
 //   * the generators are fixed for a prover, so every scalar multiplication is a FIXED-BASE one: table[b][k][d - 1] = d 2^(8k) base_b
@@ -13,7 +14,7 @@
 //     windows, 34 MB for 64-bit proofs, built once per prover), and a term costs one mixed addition per window with no doubling.  The inner-product rounds never
 //     fold a generator: L and R are sums over the ORIGINAL generators with the fold coefficients in the scalars (cg, hf below) -- 65
 //     terms per side and round, whatever the round;
-//   * a multi-scalar multiplication is a JOB of k_pv_msm: 2^G lanes take its terms round-robin, each walks the 32 windows of its
+//   * a multi-scalar multiplication is a JOB of k_pv_msm: 2^G lanes (16; a wave for a few proofs of more than 128 elements) take its terms round-robin, each walks the 32 windows of its
 //     terms with the next table entry in flight, a shuffle butterfly adds the lanes' sums; k_pv_affine turns the results into affine
 //     points (one inversion per point, all lanes busy);
 //   * the transcripts are hashed where they are needed, one lane per proof (k_pv_chal_*): SHA-256 over the text the reference builds
@@ -112,11 +113,12 @@ __device__ __noinline__ sc mod_hash_q(u64 tag, u32 taglen, const u8 *msg, u32 ml
     if (c >= 999u) return r;
   }
 }
-__device__ __forceinline__ u64 tag_of_index(u32 i, u32 &len) {            // str(i), i < 1000
+__device__ __forceinline__ u64 tag_of_index(u32 i, u32 &len) {            // str(i), i < 10000 (the prover's indices end at 2 x 1024 - 1)
   if (i < 10u) { len = 1; return (u64)('0' + i); }
   if (i < 100u) { len = 2; return (u64)('0' + i / 10u) | ((u64)('0' + i % 10u) << 8); }
-  len = 3;
-  return (u64)('0' + i / 100u) | ((u64)('0' + (i / 10u) % 10u) << 8) | ((u64)('0' + i % 10u) << 16);
+  if (i < 1000u) { len = 3; return (u64)('0' + i / 100u) | ((u64)('0' + (i / 10u) % 10u) << 8) | ((u64)('0' + i % 10u) << 16); }
+  len = 4;
+  return (u64)('0' + i / 1000u) | ((u64)('0' + (i / 100u) % 10u) << 8) | ((u64)('0' + (i / 10u) % 10u) << 16) | ((u64)('0' + i % 10u) << 24);
 }
 
 // ---- text of a transcript ---------------------------------------------------------------------------------------------------------
@@ -256,7 +258,7 @@ __device__ __forceinline__ u32 bit_of(const Batch &B, size_t p, u32 i) {
   const u32 jv = i / B.nb, jb = i % B.nb;
   return (B.values[8ull * (p * B.m + jv) + (jb >> 5)] >> (jb & 31u)) & 1u;
 }
-// z^(2 + e), e < m (a short loop: m is 1 for single-value proofs and a handful for aggregated ones)
+// z^(2 + e), e < m (a short loop: m is 1 for single-value proofs and a handful for aggregated ones; at most 1 023 steps, for 1 024 one-bit values)
 __device__ __forceinline__ sc z_pow2p(const sc &z, const sc &zz, u32 e) {
   sc r = zz;
   for (u32 t = 0; t < e; t++) r = mulq(r, z);
@@ -407,6 +409,14 @@ __global__ void __launch_bounds__(256) k_pv_affine(const u32 *__restrict__ in, u
   ::store_words16(pts + 16ull * ((size_t)(j / per) * pt_stride + slot0 + (j % per) * slot_step), w);
 }
 
+// ---- commitments from the prover's tables (bpmi_rp_prover_commit_batch): job i of k_pv_msm<1> over the base list T (g, h) takes the
+// scalars (values[i], gammas[i]) -- V_i = v_i g + gamma_i h, commitment(g, h, x, r) of /root/reference/src/utils/commitments.py:5-6
+__global__ void __launch_bounds__(256) k_pv_commit_pairs(const u32 *__restrict__ values, const u32 *__restrict__ gammas, u32 count, u32 *__restrict__ jsc) {
+  const u32 t = blockIdx.x * blockDim.x + threadIdx.x;          // count <= 2^24: 2 count fits
+  if (t >= 2u * count) return;
+  st_sc(jsc + 8ull * t, ld_sc(((t & 1u) ? gammas : values) + 8ull * (t >> 1)));
+}
+
 // ---- challenges y, z and the blinding factors of T1, T2 (rangeproof_prover.py:60-67) ------------------------------------------------------
 __global__ void __launch_bounds__(64) k_pv_chal_yz(Batch B) {
   const u32 p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -430,7 +440,8 @@ __global__ void __launch_bounds__(64) k_pv_chal_yz(Batch B) {
   st_sc(B.tau + 16ull * p + 8, mod_hash_q(t2, 4, tr, len));
 }
 
-// ---- the vector steps with n lanes per proof (block = 256 threads = 256 / n proofs, n <= 128 a power of two) -------------------------------
+// ---- the vector steps with n lanes per proof (block = NT threads = NT / n proofs; n <= 1024 a power of two, NT = 256 for n <= 256, else n:
+// rp_prove_plan_host.hpp) ----------------------------------------------------------------------------------------------------------------
 // With ONE lane per proof these two steps ran 2^14 lanes of 64 serial iterations on a quarter of the SIMDs (0.65 + 0.88 ms of a 28 ms
 // batch); here lane j owns element j: the powers y^j / y^-j are an inclusive PRODUCT scan over the proof's lanes in LDS (log2 n
 // multiplications per lane), the sums over j an LDS tree.  The hashes and the inversion of y stay one lane per proof (k_pv_final_chal).
@@ -454,17 +465,17 @@ __device__ __forceinline__ sc lane_tree_sum(u32 *s_v, u32 tid, u32 j, u32 n, sc 
   }
   return ld_sc(s_v + 8u * tid);
 }
-__device__ __forceinline__ sc sc_pow2(u32 e) {                // 2^e, e < 128
+__device__ __forceinline__ sc sc_pow2(u32 e) {                // 2^e, e < 256 (the callers pass e < nb <= 128: a bit position of one value)
   sc r = sc_u32(0);
   r.v[e >> 5] = 1u << (e & 31u);
   return r;
 }
 // ---- t1, t2 (rangeproof_prover.py:93-101) -------------------------------------------------------------------------------------------------
 //   t1 = sum sL_i (y^i (aR_i + z) + z^(2 + i / nb) 2^(i % nb)) + sum (aL_i - z) y^i sR_i,   t2 = sum sL_i y^i sR_i;   y^j is left in cg_j for k_pv_final_wide
-__global__ void __launch_bounds__(256) k_pv_poly(Batch B) {
-  __shared__ u32 s_v[256 * 8], s_w[256 * 8];
+template <u32 NT> __global__ void __launch_bounds__(NT) k_pv_poly(Batch B) {
+  __shared__ u32 s_v[NT * 8], s_w[NT * 8];
   const u32 n = B.n, tid = threadIdx.x;
-  const u32 p = blockIdx.x * (256u / n) + tid / n, j = tid & (n - 1u);
+  const u32 p = blockIdx.x * (NT / n) + tid / n, j = tid & (n - 1u);
   const bool live = p < B.P;
   const size_t pc = live ? p : 0;                             // (lanes past the batch compute on proof 0 and store nothing)
   const sc y = ld_sc(B.chal + 32ull * pc), z = ld_sc(B.chal + 32ull * pc + 8);
@@ -518,10 +529,10 @@ __global__ void __launch_bounds__(64) k_pv_final_chal(Batch B) {
   for (u32 i = 0; i < B.ip_prefix_len; i++) tr[i] = B.ip_prefix[i];
   B.tr_len[p] = B.ip_prefix_len;
 }
-__global__ void __launch_bounds__(256) k_pv_final_wide(Batch B) {
-  __shared__ u32 s_v[256 * 8];
+template <u32 NT> __global__ void __launch_bounds__(NT) k_pv_final_wide(Batch B) {
+  __shared__ u32 s_v[NT * 8];
   const u32 n = B.n, tid = threadIdx.x;
-  const u32 p = blockIdx.x * (256u / n) + tid / n, j = tid & (n - 1u);
+  const u32 p = blockIdx.x * (NT / n) + tid / n, j = tid & (n - 1u);
   const bool live = p < B.P;
   const size_t pc = live ? p : 0;
   const sc y_inv = ld_sc(B.chal + 32ull * pc + 24), z = ld_sc(B.chal + 32ull * pc + 8), x = ld_sc(B.chal + 32ull * pc + 16);
@@ -572,13 +583,13 @@ __global__ void __launch_bounds__(64) k_pv_round_chal(Batch B, u32 round) {
   st_sc(B.xr + 16ull * p, x);
   st_sc(B.xr + 16ull * p + 8, invq(x));
 }
-// n lanes per proof (block = 256 threads = 256 / n proofs; n <= 128).  round = the round whose challenge was just drawn: the state is
+// n lanes per proof (block = NT threads = NT / n proofs; NT = 1024: 4 x 32 KB of LDS, a block per CU).  round = the round whose challenge was just drawn: the state is
 // folded with it (:107-110), then the scalars of the NEXT round's L and R are written; first = 1: no fold, the state is the one
 // k_pv_final left (the scalars of round 0).  After the last fold a[0], b[0] are the proof's scalars.
-__global__ void __launch_bounds__(256) k_pv_round_wide(Batch B, u32 round, u32 first) {
-  __shared__ u32 s_a[256 * 8], s_b[256 * 8], s_l[256 * 8], s_r[256 * 8];
+template <u32 NT> __global__ void __launch_bounds__(NT) k_pv_round_wide(Batch B, u32 round, u32 first) {
+  __shared__ u32 s_a[NT * 8], s_b[NT * 8], s_l[NT * 8], s_r[NT * 8];
   const u32 n = B.n, tid = threadIdx.x;
-  const u32 p = blockIdx.x * (256u / n) + tid / n, j = tid & (n - 1u);
+  const u32 p = blockIdx.x * (NT / n) + tid / n, j = tid & (n - 1u);
   const bool live = p < B.P;
   const u32 base = tid - j;                                  // first thread of this proof in the block
   u32 len = first ? n : (n >> round);                        // length BEFORE this call's fold

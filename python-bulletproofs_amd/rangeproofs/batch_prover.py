@@ -11,10 +11,17 @@ per prover, and the transcripts are hashed on the device.  Same proofs, byte for
     # blobs[i] == proof_to_bytes(NIRangeProver(vs[i], n, g, h, gs, hs, gammas[i], u, group, seeds[i]).prove(), version=2)
 
 Round 6: AGGREGATED proofs too -- a loop of AggregNIRangeProver(vs_i, n, g, h, gs, hs, gammas_i, u, group, seed_i).prove()
-(/root/reference/src/rangeproofs/rangeproof_aggreg_prover.py:36-146) over proofs of m values each, n m <= 128:
+(/root/reference/src/rangeproofs/rangeproof_aggreg_prover.py:36-146) over proofs of m values each, n m <= 1024 (4, 8 or 16 amounts
+of 64 bits: 256, 512 or 1 024 elements per proof):
 
     bp = BatchRangeProver(n, g, h, gs, hs, u, m=4)        # gs, hs: n m points
     blobs = bp.prove_wire(vss, gammass, seeds)            # vss[i], gammass[i]: the m values / blinding factors of proof i
+
+The commitments V = v g + gamma h every verifier needs come from the same tables, all of them in one launch -- a loop of
+commitment(g, h, v, gamma) (/root/reference/src/utils/commitments.py:5-6):
+
+    Vs = bp.commit(vs, gammas)                            # Points (aggregated provers: a list of m per proof)
+    bv.verify_wire(bp.commit_packed(vs, gammas), blobs)   # 64 bytes per value, as BatchRangeVerifier.*_wire take them
 """
 import ctypes
 
@@ -31,9 +38,12 @@ def _le32(v):
 
 class BatchRangeProver:
     def __init__(self, n, g, h, gs, hs, u, engine=None, m=1, wire_format=2):
-        """n: bits per value, m: values per proof (powers of two, 2 <= n m <= 128; m = 1: single-value proofs); g, h, u: points; gs, hs:
-        n m points each.  Builds the fixed-base tables on the engine's device (4.4 GB and ~72 ms for n m = 64 with the default 16-bit
-        windows; engine option prover_table_bits: 12 bits are 378 MB, 17 ms and 22 % slower proving) and keeps them until close().
+        """n: bits per value (at most 128), m: values per proof (powers of two, 2 <= n m <= 1024; m = 1: single-value proofs); g, h, u:
+        points; gs, hs: n m points each.  Builds the fixed-base tables on the engine's device (4.4 GB and ~72 ms for n m = 64 with the
+        default 16-bit windows; engine option prover_table_bits: 12 bits are 378 MB, 17 ms and 22 % slower proving) and keeps them until
+        close().  Above 128 elements the default windows are the widest whose table is no larger than the 8.7 GB of 128 elements at 16
+        bits: 14 bits at 256 elements, 13 at 512, 12 at 1 024 (csrc/rp_prove_plan_host.hpp).  A call proves at most 2^20 proofs and
+        2^27 elements (proofs x n m).
         wire_format: 2, or 3 -- the proofs then end with their points' y coordinates (rangeproofs/codec.py), which the batch verifier
         checks instead of taking square roots; the prover has them anyway."""
         if len(gs) != n * m or len(hs) != n * m:
@@ -49,15 +59,9 @@ class BatchRangeProver:
         self._handle = handle.value
         self._out = None
 
-    def prove_wire_packed(self, vs, gammas, seeds, copy=True):
-        """(packed bytes, offsets): proof i = packed[offsets[i]: offsets[i + 1]], wire format 2 (or 3) -- what
-        BatchRangeVerifier.add_wire_native / bpmi_rp_batch_verify_dev take as they are.
-        vs, gammas: lists of ModP / int (aggregated provers: a list of m values per proof), or ALREADY PACKED bytes (32 bytes
-        little-endian per value, reduced mod q, proof after proof): a service that receives its inputs as bytes skips 2 x len Python
-        conversions.  seeds: a list of bytes, or (joined bytes, offsets) -- offsets a list or a ctypes c_uint64 array (taken as it is).
-        copy=False: `packed` is a memoryview of the prover's page-locked output buffer and `offsets` the ctypes array the library
-        filled -- valid until the next call on this prover or its close(); a service that forwards the bytes (a socket, the batch verifier's
-        receive buffer) saves the one host copy of the batch (18 MB at 2^14 proofs) and the list of 2^14 Python integers."""
+    def _packed_scalars(self, vs, gammas):
+        """(values, blinding factors, count) as packed bytes, 32 little-endian per value, from lists of ModP / int (aggregated provers:
+        a list of m per proof) or from bytes already packed."""
         vm = self.m
 
         def flat(xs):
@@ -68,11 +72,46 @@ class BatchRangeProver:
                     raise ValueError("every proof of this prover takes %d values" % vm)
             return [x for row in xs for x in row]
         if isinstance(vs, (bytes, bytearray, memoryview)):
-            vb, m = bytes(vs), len(vs) // (32 * vm)
+            vb, count = bytes(vs), len(vs) // (32 * vm)
         else:
-            m = len(vs)
+            count = len(vs)
             vb = b"".join([_le32(v) for v in flat(vs)])
         gb = bytes(gammas) if isinstance(gammas, (bytes, bytearray, memoryview)) else b"".join([_le32(x) for x in flat(gammas)])
+        if len(vb) != 32 * count * vm or len(gb) != 32 * count * vm:
+            raise ValueError("values and blinding factors must have the same length")
+        return vb, gb, count
+
+    def commit_packed(self, vs, gammas):
+        """The commitments V = v g + gamma h of every value, 64 bytes each (x, y little-endian; the identity is 64 zero bytes), proof
+        after proof: what BatchRangeVerifier.verify_wire / partial_wire / locate_wire take as Vs.  One launch over the prover's tables
+        (bpmi_rp_prover_commit_batch) instead of a loop of commitment(g, h, v, gamma).  The WHOLE value enters, not only its low n bits:
+        the proof of an out-of-range value fails against its commitment.  vs, gammas: as for prove_wire_packed."""
+        vb, gb, count = self._packed_scalars(vs, gammas)
+        total = count * self.m
+        out = ctypes.create_string_buffer(64 * total)
+        eng = self._engine
+        eng._ck(eng.lib.bpmi_rp_prover_commit_batch(self._handle, total, vb, gb, ctypes.cast(out, ctypes.c_void_p)))
+        return out.raw
+
+    def commit(self, vs, gammas):
+        """The same as Points: one per value; aggregated provers (m > 1): a list of m per proof."""
+        from ..ec import Point
+        raw = self.commit_packed(vs, gammas)
+        pts = [Point.from_le64(raw[o: o + 64]) for o in range(0, len(raw), 64)]
+        if self.m == 1:
+            return pts
+        return [pts[i: i + self.m] for i in range(0, len(pts), self.m)]
+
+    def prove_wire_packed(self, vs, gammas, seeds, copy=True):
+        """(packed bytes, offsets): proof i = packed[offsets[i]: offsets[i + 1]], wire format 2 (or 3) -- what
+        BatchRangeVerifier.add_wire_native / bpmi_rp_batch_verify_dev take as they are.
+        vs, gammas: lists of ModP / int (aggregated provers: a list of m values per proof), or ALREADY PACKED bytes (32 bytes
+        little-endian per value, reduced mod q, proof after proof): a service that receives its inputs as bytes skips 2 x len Python
+        conversions.  seeds: a list of bytes, or (joined bytes, offsets) -- offsets a list or a ctypes c_uint64 array (taken as it is).
+        copy=False: `packed` is a memoryview of the prover's page-locked output buffer and `offsets` the ctypes array the library
+        filled -- valid until the next call on this prover or its close(); a service that forwards the bytes (a socket, the batch verifier's
+        receive buffer) saves the one host copy of the batch (18 MB at 2^14 proofs) and the list of 2^14 Python integers."""
+        vb, gb, m = self._packed_scalars(vs, gammas)
         if isinstance(seeds, tuple):
             sb, offs = seeds
             if len(offs) != m + 1:
@@ -88,8 +127,6 @@ class BatchRangeProver:
                 pos += len(sd)
             off[m] = pos
             sb = b"".join(seeds)
-        if len(vb) != 32 * m * vm or len(gb) != 32 * m * vm:
-            raise ValueError("values, blinding factors and seeds must have the same length")
         eng = self._engine
         eng.set_option("prover_wire_format", self.wire_format)           # (an engine option: set per call, provers may share the engine)
         cap = m * eng.lib.bpmi_rp_prove_batch_proof_bytes(self._handle, 0) + (off[m] - off[0]) + 16      # a proof is a fixed part + its seed
