@@ -274,6 +274,35 @@ int bpmi_ipa_verify_dev(bpmi_ctx *ctx, const void *d_g, const void *d_h, const v
                         const uint8_t *xinvs, uint32_t k, const uint8_t a[32], const uint8_t b[32], const uint8_t *extra_pts,
                         const uint8_t *extra_scalars, uint64_t n_extra, uint8_t out[64]);
 
+/* ---- a BATCH of inner-product proofs over the same generators in one MSM ----------------
+ * Verifier2.verify's check (/root/reference/src/innerproduct/inner_product_verifier.py:127-147) is one equation per proof p,
+ *   sum_i a_p s_{p,i} g_i + sum_i b_p s_{p,i}^-1 c_i h_i + a_p b_p u_p - P_p - sum_j (x_{p,j}^2 L_{p,j} + x_{p,j}^-2 R_{p,j}) = 0
+ * with s_{p,i} as in bpmi_sc_svector (get_ss, :91-102).  Multiplied by a random weight w_p each and added up, the generator terms
+ * of all proofs collapse to 2n pairs with the scalars
+ *   SA_i = sum_p w_p a_p s_{p,i},   SB_i = c_i sum_p w_p b_p s_{p,i}^-1
+ * so n_proofs proofs cost n_proofs x n x 2 multiplications mod q and ONE multi-scalar multiplication instead of one each.  The two
+ * equalities of Verifier1 (:44-58: P_new = P + x c u, u_new = x u) are point equations too and can ride along as extra pairs under
+ * weights of their own.  The weights must be unpredictable to whoever made the proofs: with known weights the errors of two
+ * invalid proofs can be made to cancel.
+ * Per call: n = 2^k with k <= 22; 1 <= n_proofs <= 2^16; n_proofs x n <= 2^32; the half tables (n_proofs x 64 (2^(k/2) + 2^(k - k/2))
+ * bytes) at most 1 GiB; at most 2^22 extra points.  A call outside these bounds is refused with BPMI_E_ARG before anything is read
+ * or allocated.  One call at a time per ctx.
+ *
+ * SA, SB of a batch, to host memory (the testable half, as bpmi_sc_svector is for bpmi_ipa_verify_dev).  xs, xinvs: n_proofs x k x 32
+ * bytes; a, b, weights: n_proofs x 32 bytes, values in [0, q); scale: n x 32 bytes or NULL; sa, sb: n = 2^k scalars each. */
+int bpmi_sc_svector_sum(bpmi_ctx *ctx, uint32_t k, uint64_t n_proofs, const uint8_t *xs, const uint8_t *xinvs, const uint8_t *a,
+                        const uint8_t *b, const uint8_t *weights, const uint8_t *scale, uint8_t *sa, uint8_t *sb);
+/* The whole batch over generators in device memory (n points each, d_hscale: n scalars or NULL):
+ *   out = sum_i SA_i g_i + sum_i SB_i h_i + sum_t extra_scalars[t] * extra_pts[t]
+ * the identity (64 zero bytes) iff every weighted equation holds.  The caller passes every proof's u, L_j, R_j and P as extra points
+ * with the scalars (a b, -x_j^2, -x_j^-2, -1) ALREADY multiplied by that proof's weight: the library does not know which extra
+ * point belongs to which proof.  Points are checked as in bpmi_ipa_verify_dev (option "validate_points": the extra points at
+ * level 1, the generators at level 2); a call refused for a point leaves 0xFF.. in out, never the identity. */
+int bpmi_ipa_verify_batch_dev(bpmi_ctx *ctx, const void *d_g, const void *d_h, const void *d_hscale, uint64_t n, uint64_t n_proofs,
+                              const uint8_t *xs, const uint8_t *xinvs, uint32_t k, const uint8_t *a, const uint8_t *b,
+                              const uint8_t *weights, const uint8_t *extra_pts, const uint8_t *extra_scalars, uint64_t n_extra,
+                              uint8_t out[64]);
+
 /* ---- inner-product argument prover, split at the Fiat-Shamir edge ----------------------
  * One object = one run of FastNIProver2.prove (src/innerproduct/inner_product_prover.py:70-110).
  * g, h: n points; a, b: n scalars; u: one point; all copied to the device once and kept

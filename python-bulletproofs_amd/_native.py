@@ -44,6 +44,8 @@ SIGNATURES = {
     "bpmi_sc_fold_dev": (_i, [_vp, _vp, _vp, _cp, _cp, _u64, _vp]),
     "bpmi_sc_svector": (_i, [_vp, _cp, _cp, ctypes.c_uint32, _cp, _cp, _cp, _cp, _cp]),
     "bpmi_ipa_verify_dev": (_i, [_vp, _vp, _vp, _vp, _u64, _cp, _cp, ctypes.c_uint32, _cp, _cp, _cp, _cp, _u64, _cp]),
+    "bpmi_sc_svector_sum": (_i, [_vp, ctypes.c_uint32, _u64, _cp, _cp, _cp, _cp, _cp, _cp, _cp, _cp]),
+    "bpmi_ipa_verify_batch_dev": (_i, [_vp, _vp, _vp, _vp, _u64, _u64, _cp, _cp, ctypes.c_uint32, _cp, _cp, _cp, _cp, _cp, _u64, _cp]),
     "bpmi_ipa_create": (_i, [_vp, _cp, _cp, _cp, _cp, _u64, _cp, ctypes.POINTER(_vp)]),
     "bpmi_ipa_create_scaled": (_i, [_vp, _cp, _cp, _cp, _cp, _u64, _cp, _cp, ctypes.POINTER(_vp)]),
     "bpmi_ipa_create_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _cp, ctypes.POINTER(_vp)]),

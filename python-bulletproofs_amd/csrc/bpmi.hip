@@ -24,7 +24,7 @@
 //                   (host thread on 4x64-bit limbs, host_tail.hpp, or the one-lane device
 //                   kernel k_tail; same Horner chain)
 // This file: the C-ABI entry points.  The inner-product prover (the IPA state object, deferred generator folding) is ipa_host.hpp,
-// included below where its section stood.
+// included below where its section stood; the batch verifier of inner-product proofs is ipa_batch_host.hpp, behind it.
 // Kernels and host orchestration live in the *.hpp files included below (one translation unit).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -50,11 +50,13 @@ using namespace bpmi;
 #include "msm_plan_host.hpp"
 #include "rp_batch_plan_host.hpp"
 #include "rp_prove_plan_host.hpp"
+#include "ipa_batch_plan_host.hpp"
 #include "context.hpp"
 #include "device_util.hpp"
 #include "msm_kernels.hpp"
 #include "fold_ops_host.hpp"
 #include "point_kernels.hpp"
+#include "svector_batch.hpp"
 #include "scalar_kernels.hpp"
 #include "host_tail.hpp"
 #include "msm_host.hpp"
@@ -864,6 +866,7 @@ int bpmi_ipa_verify_dev(bpmi_ctx *ctx, const void *d_g, const void *d_h, const v
 }  // extern "C"
 
 #include "ipa_host.hpp"
+#include "ipa_batch_host.hpp"
 #include "rp_batch_dev_host.hpp"
 
 extern "C" {

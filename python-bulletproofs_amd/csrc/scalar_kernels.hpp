@@ -240,6 +240,49 @@ __global__ void __launch_bounds__(256) k_sc_svector(const u32 *__restrict__ tab,
   store_words8(sb + 8ull * i, r.v);
 }
 
+// ---- the s-vectors of a BATCH of proofs over the same generators, summed under random weights (bpmi_ipa_verify_batch_dev) ------------
+//   SA_i = sum_p w_p a_p s_{p,i},   SB_i = c_i sum_p w_p b_p s_{p,i}^-1
+// The per-thread bodies are svector_batch.hpp (plain C++: tests/test_ipa_batch_host_cpu.py checks the host build limb for limb); the
+// launch shapes, the workspace and the rule for `parts` are ipa_batch_plan_host.hpp.
+// The half tables of k_sc_svector_tables for every proof in one launch: proof = blockIdx.y + gridDim.y * blockIdx.z.  Same index split,
+// table layout and bit order; the high half is seeded with w_p a_p and w_p b_p.  recs: rec_words words per proof -- k pairs
+// (x_j, x_j^-1), then a, b, w.
+__global__ void __launch_bounds__(256) k_sc_svector_tables_batch(const u32 *__restrict__ recs, u32 rec_words, u32 k, u32 kl, u32 n_proofs,
+                                                                 u32 *__restrict__ tabs) {
+  const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+  const u32 p = blockIdx.y + gridDim.y * blockIdx.z;
+  const u32 ntab = (1u << kl) + (1u << (k - kl));
+  if (t >= ntab || p >= n_proofs) return;
+  u32 e[16];
+  svb_table_entry(e, recs + (uint64_t)rec_words * p, k, kl, t);
+  u32 *dst = tabs + 16ull * ((uint64_t)ntab * p + t);
+  store_words8(dst, e);
+  store_words8(dst + 8, e + 8);
+}
+// The hot loop: one lane per element i, the proofs [blockIdx.y per_part, ...) of range blockIdx.y.  out_a / out_b: SA and SB
+// themselves (one range, no scale: part_words = 0) or the A and B halves of the partial sums (part_words = 16 n words per range).
+__global__ void __launch_bounds__(256) k_sc_svector_sum(const u32 *__restrict__ tabs, u32 ntab, u32 kl, u32 n, u32 n_proofs, u32 per_part,
+                                                        u32 *__restrict__ out_a, u32 *__restrict__ out_b, uint64_t part_words) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const u32 p0 = blockIdx.y * per_part;
+  const u32 p1 = p0 + per_part < n_proofs ? p0 + per_part : n_proofs;
+  u32 ra[8], rb[8];
+  svb_sum_element(ra, rb, tabs, ntab, kl, i, p0, p1);
+  store_words8(out_a + part_words * blockIdx.y + 8ull * i, ra);
+  store_words8(out_b + part_words * blockIdx.y + 8ull * i, rb);
+}
+// SA_i, SB_i from the partial sums of the `parts` ranges; SB_i times the shared scale c_i (or scale == null)
+__global__ void __launch_bounds__(256) k_sc_svector_sum_finish(const u32 *__restrict__ part, u32 parts, u32 n, const u32 *__restrict__ scale,
+                                                               u32 *__restrict__ sa, u32 *__restrict__ sb) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  u32 ra[8], rb[8];
+  svb_finish_element(ra, rb, part, parts, n, scale, i);
+  store_words8(sa + 8ull * i, ra);
+  store_words8(sb + 8ull * i, rb);
+}
+
 // Self-test hook: the DEVICE bodies of the multiplication family (csrc/field_gen.hpp) on raw limbs, so that a
 // test can feed lazy magnitudes and compare the limbs with the host build of the same header (tests/test_gpu_field.py).
 // op 0 mul(a,b), 1 sqr(a), 2 mul_add(a,b,c), 3 sqr_add(a,c), 4 mul2(a,b,c,d), 5 carry(a), 6 canon(a), 7 sqr3(a), 8 mul_add8(a,b,c),

@@ -205,6 +205,23 @@ class Engine:
                                               sc_bytes(a), sc_bytes(b), extra_pts, extra_scalars, n_extra, out))
         return out.raw
 
+    def sc_svector_sum_bytes(self, k, n_proofs, xs, xinvs, a, b, weights, scale=None):
+        """(SA, SB) of bpmi_sc_svector_sum as packed bytes, 2^k scalars each: the weighted sums of n_proofs s-vectors.  xs, xinvs:
+        n_proofs x k packed scalars; a, b, weights: n_proofs packed scalars each; scale: 2^k packed scalars or None."""
+        n = 1 << k
+        sa, sb = ctypes.create_string_buffer(32 * n), ctypes.create_string_buffer(32 * n)
+        self._ck(self.lib.bpmi_sc_svector_sum(self.ctx, k, n_proofs, xs, xinvs, a, b, weights, scale, sa, sb))
+        return sa.raw, sb.raw
+
+    def ipa_verify_batch_dev(self, d_g, d_h, n, n_proofs, xs, xinvs, a, b, weights, extra_pts, extra_scalars, n_extra, d_hscale=None):
+        """The 64-byte value of a batch of Verifier2 checks over device-resident generators under the given weights (identity =
+        every proof accepted).  Packed bytes throughout; the extra scalars arrive multiplied by their proof's weight."""
+        out = ctypes.create_string_buffer(64)
+        k = n.bit_length() - 1
+        self._ck(self.lib.bpmi_ipa_verify_batch_dev(self.ctx, _ptr(d_g), _ptr(d_h), None if d_hscale is None else _ptr(d_hscale), n, n_proofs,
+                                                    xs, xinvs, k, a, b, weights, extra_pts, extra_scalars, n_extra, out))
+        return out.raw
+
     # ---- IPA prover state ----
     def ipa_create(self, g, h, a, b, n, u, h_scale=None):
         st = ctypes.c_void_p()

@@ -1,0 +1,189 @@
+"""Batch verification of inner-product proofs over shared generators in ONE multi-scalar multiplication
+(bpmi_ipa_verify_batch_dev; the per-proof verifiers are Verifier1 / Verifier2 of inner_product_verifier.py,
+reference: src/innerproduct/inner_product_verifier.py:44-58 and :127-147).
+
+Verifier2's check is one point equation per proof.  Multiplied by a random weight each and added up, the generator terms of
+all proofs collapse to 2n pairs -- their scalars are sums of weighted s-vectors, computed on the device -- so B proofs cost
+one MSM of 2n + B (2 log n + 2) pairs instead of B MSMs of 2n.  The weights MUST be unpredictable to whoever made the
+proofs: two invalid proofs whose errors are e and -e pass `verify(weights=[1, 1])`, and with any known weights a pair of
+errors can be scaled to cancel.  `verify()` draws them from `secrets`."""
+import secrets
+
+from .. import engine as _engine
+from ..ec import PackedPoints, pack_points, pack_scalars, secp256k1
+from ..utils.utils import mod_hash
+from .inner_product_verifier import Verifier2
+
+Q = secp256k1.q
+
+
+def locate_by_bisection(count, subset_is_valid):
+    """The sorted indices in range(count) of the invalid items, found with subset probes: subset_is_valid(indices) is True iff
+    every item of the (sorted, non-empty) index list is valid.  One probe over everything; then every subset known to hold an
+    invalid item is halved: the left half is probed, and the right half only when the left one was invalid (a valid left half
+    proves the right one invalid).  At most 1 + 2 bad ceil(log2 count) probes."""
+    if count <= 0:
+        return []
+    everything = list(range(count))
+    if subset_is_valid(everything):
+        return []
+    bad, todo = [], [everything]          # todo: subsets known to hold an invalid item
+    while todo:
+        sub = todo.pop()
+        if len(sub) == 1:
+            bad.append(sub[0])
+            continue
+        mid = (len(sub) + 1) // 2
+        left, right = sub[:mid], sub[mid:]
+        if subset_is_valid(left):
+            todo.append(right)
+        else:
+            todo.append(left)
+            if not subset_is_valid(right):
+                todo.append(right)
+    return sorted(bad)
+
+
+class _Item:
+    """One queued proof: the inputs of its row of the s-vector sum and its extra pairs, grouped by the weight they take --
+    group 0 under the proof's own weight, every further group (the equalities of Protocol 1) under a fresh one."""
+    __slots__ = ("valid", "xs", "xinvs", "a", "b", "groups")
+
+    def __init__(self):
+        self.valid, self.xs, self.xinvs, self.a, self.b, self.groups = False, (), (), 0, 0, ()
+
+
+class BatchInnerProductVerifier:
+    """Verifier2 / Verifier1 for many proofs over the same generators g, h (and the same optional h_scale)."""
+
+    def __init__(self, g, h, h_scale=None, engine=None, rng=None):
+        """g, h: lists of points or PackedPoints (those keep their device copy), n = 2^k each, uploaded once.  h_scale: integers
+        c_i, the statements are over c_i * h[i] (see Verifier2), uploaded once.  rng() -> int: the source of the random weights;
+        default: secrets (a CSPRNG)."""
+        n = len(g)
+        if n < 1 or n & (n - 1) or len(h) != n or (h_scale is not None and len(h_scale) != n):
+            raise ValueError("g, h (and h_scale) must have the same power-of-two length")
+        self.n, self.k = n, n.bit_length() - 1
+        self.engine = engine or _engine.default_engine()
+        self._rng = rng or (lambda: secrets.randbelow(Q - 1) + 1)
+        self._own = []
+        self._d = []
+        for lst in (g, h):
+            if isinstance(lst, PackedPoints):
+                self._d.append(lst.device(self.engine))
+            else:
+                self._d.append(self.engine.upload(pack_points(lst)))
+                self._own.append(self._d[-1])
+        self._d_scale = None
+        if h_scale is not None:
+            self._d_scale = self.engine.upload(pack_scalars(h_scale, Q))
+            self._own.append(self._d_scale)
+        self._keep = (g, h)                      # PackedPoints free their device copy when collected
+        self._items = []
+
+    def __len__(self):
+        return len(self._items)
+
+    def reset(self):
+        """Forget the queued proofs; the generators stay resident."""
+        self._items = []
+
+    def release(self):
+        """Free the device buffers this object uploaded (not the device copies of PackedPoints)."""
+        for d in self._own:
+            d.free()
+        self._own, self._d, self._d_scale, self._items = [], [], None, []
+
+    def _weight(self):
+        return self._rng() % Q or 1
+
+    # ---- queueing ------------------------------------------------------------------------------------------------------------
+    def _queue2(self, u, P, proof2, head=()):
+        it = _Item()
+        self._items.append(it)
+        try:
+            v = Verifier2(None, None, u, P, proof2)
+            v.verify_transcript(self.k)
+            xv, xi, pts, scs = v._extra_terms()            # refuses a challenge = 0 (mod q)
+            it.xs, it.xinvs = [x % Q for x in xv[:self.k]], [x % Q for x in xi[:self.k]]
+            it.a, it.b = proof2.a.x % Q, proof2.b.x % Q
+            it.groups = ((list(pts), [int(s) % Q for s in scs]),) + tuple(head)
+            for pts_g, _ in it.groups:
+                for p in pts_g:
+                    p.to_le64()
+            it.valid = True
+        except Exception:
+            it.valid = False                             # "Proof invalid" at the byte level: it never reaches the device
+        return len(self._items) - 1
+
+    def add(self, u, P, proof2):
+        """Queue a Protocol-2 proof of the statement (u, P); returns its index.  The transcript is re-derived here, on the host
+        (Verifier2.verify_transcript); a proof that fails it is recorded as invalid."""
+        return self._queue2(u, P, proof2)
+
+    def add_proof1(self, u, P, c, proof1):
+        """Queue a Protocol-1 proof of (u, P, c).  Verifier1's re-hash runs on the host; its two equalities P_new = P + x c u and
+        u_new = x u join the MSM as five extra pairs, each equality under a random weight of its own."""
+        try:
+            items = proof1.transcript.split(b"&")
+            if items[1] != str(mod_hash(b"&".join(items[:1]) + b"&", Q)).encode():
+                raise ValueError("transcript")
+            x = int(items[1]) % Q
+            cv = (c.x if hasattr(c, "x") else int(c)) % Q
+            head = (([proof1.P_new, P, u], [1, Q - 1, (Q - x * cv % Q) % Q]), ([proof1.u_new, u], [1, (Q - x) % Q]))
+        except Exception:
+            it = _Item()
+            self._items.append(it)
+            return len(self._items) - 1
+        return self._queue2(proof1.u_new, proof1.P_new, proof1.proof2, head)
+
+    # ---- verification --------------------------------------------------------------------------------------------------------
+    def _probe(self, idx, weights):
+        """True iff the weighted sum of the equations of the (host-valid) proofs idx is the identity: one native call (its per-call
+        caps -- include/bpmi.h -- are the engine's to refuse)."""
+        xs, xinvs, a, b, pts, scs = [], [], [], [], [], []
+        for i, w in zip(idx, weights):
+            it = self._items[i]
+            xs += it.xs
+            xinvs += it.xinvs
+            a.append(it.a)
+            b.append(it.b)
+            for gi, (gp, gs) in enumerate(it.groups):
+                r = w if gi == 0 else self._weight()
+                pts += gp
+                scs += [s * r % Q for s in gs]
+        out = self.engine.ipa_verify_batch_dev(self._d[0], self._d[1], self.n, len(idx), pack_scalars(xs, Q), pack_scalars(xinvs, Q),
+                                               pack_scalars(a, Q), pack_scalars(b, Q), pack_scalars([w % Q for w in weights], Q),
+                                               pack_points(pts), pack_scalars(scs, Q), len(pts), self._d_scale)
+        return out == bytes(64)
+
+    def verify(self, weights=None):
+        """True iff every queued proof is valid (an empty batch is).  weights: one integer per queued proof instead of the random
+        ones -- for tests and for callers that shard a batch under weights drawn elsewhere; never values a prover could know."""
+        if weights is not None and len(weights) != len(self._items):
+            raise ValueError("one weight per queued proof")
+        if not self._items:
+            return True
+        if not all(it.valid for it in self._items):
+            return False
+        ws = [int(w) % Q for w in weights] if weights is not None else [self._weight() for _ in self._items]
+        return self._probe(list(range(len(self._items))), ws)
+
+    def locate(self):
+        """The sorted indices of the invalid proofs: those that failed on the host, and those found by bisection over subsets of the
+        rest -- every probe one native call over the resident generators, under fresh weights."""
+        good = [i for i, it in enumerate(self._items) if it.valid]
+        bad = [i for i, it in enumerate(self._items) if not it.valid]
+        found = locate_by_bisection(len(good), lambda sub: self._probe([good[j] for j in sub], [self._weight() for _ in sub]))
+        return sorted(bad + [good[j] for j in found])
+
+
+def batch_verify_inner_products(g, h, statements, h_scale=None, engine=None, rng=None):
+    """True iff every (u, P, proof2) of `statements` is a valid Protocol-2 proof over g, h."""
+    bv = BatchInnerProductVerifier(g, h, h_scale, engine, rng)
+    try:
+        for u, P, proof2 in statements:
+            bv.add(u, P, proof2)
+        return bv.verify()
+    finally:
+        bv.release()
