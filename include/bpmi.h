@@ -244,6 +244,35 @@ int bpmi_ec_decompress_batch(bpmi_ctx *ctx, const uint8_t *comp, uint64_t n, uin
 /* the same with the decoded points left on the device (d_out: n x 64 bytes of device memory), ready to be MSM input */
 int bpmi_ec_decompress_batch_dev(bpmi_ctx *ctx, const uint8_t *comp, uint64_t n, void *d_out, uint8_t *ok);
 
+/* ---- bulk hash to the curve: the generators of every protocol, derived on the device ----------------
+ * out[i] = elliptic_hash(message i) of the reference (src/utils/elliptic_curve_hash.py:7-23), try and increment: the counters
+ * c = 1, 2, ... are tried in turn, pre = str(c) || message (decimal ASCII, no padding), x = SHA-256(pre) read big-endian; x >= p
+ * or x^3 + 7 not a square: the next c.  The sign rule: with r = (x^3 + 7)^((p+1)/4) and bit = the low bit of the last byte of
+ * MD5(pre), the point is (x, r) when bit = 1, else (x, p - r) -- chosen by MD5 of the same prefixed message and by which root
+ * the exponentiation returns, NOT by the parity of y.  Under these generators, and only these, proofs interoperate with the
+ * reference's.
+ *   batch form   message i = msgs[msg_off[i] .. msg_off[i + 1]), msg_off: n + 1 offsets
+ *   range form   message i = str(lo + i) || tail[0 .. tail_len), i in [0, hi - lo): the idiom
+ *                [elliptic_hash(str(i).encode() + seed, CURVE) for i in range(n)] of the reference's tests and main; only the tail
+ *                is uploaded
+ * max_tries: the candidates a message gets at most, 1 .. 255; 0 means 255 (the chance of a message needing more is 2^-255).
+ * tries (n bytes, may be NULL): tries[i] = the counter that succeeded, or 0 when none did within max_tries -- out[i] is then 64
+ * zero bytes.  With tries == NULL a message without a point fails the call with BPMI_E_STATE naming the first such index (an
+ * identity must never pass silently for a generator); with tries given the call is BPMI_OK and the caller reads the flags.
+ * Refused with BPMI_E_ARG before any message is read or anything is allocated: n > BPMI_MAX_N, a message of more than 65 535
+ * bytes, decreasing offsets, more than 4 GiB of messages, tail_len > 65 535, anything but lo <= hi <= 2^32, max_tries > 255.
+ * n = 0 (lo == hi) is BPMI_OK and touches nothing.  out: n x 64 bytes in the point format above; the _dev forms leave the points in
+ * device memory (d_out: n x 64 bytes), ready to be the g / h of bpmi_ipa_create_dev, bpmi_ipa_verify_dev, bpmi_msm_dev or the batch
+ * verifier.  Ordered on the ctx stream, and complete on return, like bpmi_ec_decompress_batch[_dev].
+ * A call of up to 196 608 messages runs one message per lane with a loop per lane; a larger one gives every wave a span of several
+ * messages per lane and a lane takes the span's next message when its own is done (profiles/r09_hash_to_curve.txt).  Options for A/B
+ * runs and tests: "h2c_plain" = 1 forces the loop per lane at every size; "h2c_per_lane" = 1 .. 64 forces the queue with that many
+ * messages per lane (0 = by the call's size). */
+int bpmi_ec_hash_batch(bpmi_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off, uint64_t n, uint32_t max_tries, uint8_t *out, uint8_t *tries);
+int bpmi_ec_hash_batch_dev(bpmi_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off, uint64_t n, uint32_t max_tries, void *d_out, uint8_t *tries);
+int bpmi_ec_hash_range(bpmi_ctx *ctx, const uint8_t *tail, uint64_t tail_len, uint64_t lo, uint64_t hi, uint32_t max_tries, uint8_t *out, uint8_t *tries);
+int bpmi_ec_hash_range_dev(bpmi_ctx *ctx, const uint8_t *tail, uint64_t tail_len, uint64_t lo, uint64_t hi, uint32_t max_tries, void *d_out, uint8_t *tries);
+
 /* ---- bulk scalar (mod q) operations ------------------------------------------------
  * out = sum_i a[i] * b[i] mod q       replaces inner_product (src/utils/utils.py:134-137) */
 int bpmi_sc_dot(bpmi_ctx *ctx, const uint8_t *a, const uint8_t *b, uint64_t n, uint8_t out[32]);

@@ -36,6 +36,10 @@ SIGNATURES = {
     "bpmi_ec_sum_dev_enqueue": (_i, [_vp, _vp, _u64, _vp]),
     "bpmi_ec_decompress_batch": (_i, [_vp, _cp, _u64, _cp, _cp]),
     "bpmi_ec_decompress_batch_dev": (_i, [_vp, _vp, _u64, _vp, _vp]),
+    "bpmi_ec_hash_batch": (_i, [_vp, _cp, _vp, _u64, ctypes.c_uint32, _cp, _cp]),
+    "bpmi_ec_hash_batch_dev": (_i, [_vp, _cp, _vp, _u64, ctypes.c_uint32, _vp, _cp]),
+    "bpmi_ec_hash_range": (_i, [_vp, _cp, _u64, _u64, _u64, ctypes.c_uint32, _cp, _cp]),
+    "bpmi_ec_hash_range_dev": (_i, [_vp, _cp, _u64, _u64, _u64, ctypes.c_uint32, _vp, _cp]),
     "bpmi_memcpy_dev": (_i, [_vp, _vp, _vp, _sz]),
     "bpmi_msm_segs_dev": (_i, [_vp, ctypes.c_uint32, _vp, _vp, _vp, _cp]),
     "bpmi_sc_dot": (_i, [_vp, _cp, _cp, _u64, _cp]),

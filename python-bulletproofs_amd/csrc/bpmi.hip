@@ -67,6 +67,9 @@ using namespace bpmi;
 #include "rp_wire_v2_host.hpp"
 #include "rp_batch_kernels.hpp"
 #include "rp_prove_kernels.hpp"
+#include "h2c.hpp"
+#include "h2c_kernels.hpp"
+#include "h2c_host.hpp"
 
 // ------------------------------------------------------------------------------------
 // C-ABI
@@ -149,6 +152,8 @@ int bpmi_set_option(bpmi_ctx *ctx, const char *name, int64_t value) {
   if (!strcmp(name, "window_bits")) { if (value != 0 && (value < 2 || value > 16)) return fail(ctx, BPMI_E_ARG, "window_bits must be 0 or 2..16"); ctx->opt_c = (int)value; return BPMI_OK; }
   if (!strcmp(name, "accum_stream")) { if (value < 0 || value > 2) return fail(ctx, BPMI_E_ARG, "accum_stream must be 0, 1 or 2"); ctx->opt_accum_stream = (int)value; return BPMI_OK; }
   if (!strcmp(name, "lane_priority")) { if (value < -1 || value > 1) return fail(ctx, BPMI_E_ARG, "lane_priority must be -1, 0 or 1"); ctx->opt_lane_prio = (int)value; return BPMI_OK; }
+  if (!strcmp(name, "h2c_plain")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "h2c_plain must be 0 or 1"); ctx->opt_h2c_plain = (int)value; return BPMI_OK; }
+  if (!strcmp(name, "h2c_per_lane")) { if (value < 0 || value > 64) return fail(ctx, BPMI_E_ARG, "h2c_per_lane must be 0 .. 64"); ctx->opt_h2c_per_lane = (int)value; return BPMI_OK; }
   if (!strcmp(name, "pair_sched")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "pair_sched must be 0 or 1"); ctx->opt_pair_sched = (int)value; return BPMI_OK; }
   if (!strcmp(name, "prover_wire_format")) { if (value != 2 && value != 3) return fail(ctx, BPMI_E_ARG, "prover_wire_format must be 2 or 3"); ctx->opt_prover_wire = (int)value; return BPMI_OK; }
   if (!strcmp(name, "prover_split")) { if (value < 0 || value > (1 << 20)) return fail(ctx, BPMI_E_ARG, "prover_split must be 0, 1 or the smallest half"); ctx->opt_prover_split = (int)value; return BPMI_OK; }
@@ -664,6 +669,31 @@ int bpmi_ec_decompress_batch_dev(bpmi_ctx *ctx, const uint8_t *comp, uint64_t n,
   HIPCHK(ctx, hipMemcpyAsync(ok, dok, n, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return BPMI_OK;
+}
+// ---- bulk hash to the curve (h2c_host.hpp) --------------------------------------------------------------------------------------------
+int bpmi_ec_hash_batch(bpmi_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off, uint64_t n, uint32_t max_tries, uint8_t *out, uint8_t *tries) {
+  if (!ctx) return BPMI_E_ARG;
+  uint64_t total = 0;
+  const int rc = h2c_check(ctx, false, msgs, msg_off, 0, 0, 0, n, max_tries, out, &total);
+  return rc ? rc : h2c_run(ctx, false, msgs, total, msg_off, 0, n, max_tries, nullptr, out, tries);
+}
+int bpmi_ec_hash_batch_dev(bpmi_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off, uint64_t n, uint32_t max_tries, void *d_out, uint8_t *tries) {
+  if (!ctx) return BPMI_E_ARG;
+  uint64_t total = 0;
+  const int rc = h2c_check(ctx, false, msgs, msg_off, 0, 0, 0, n, max_tries, d_out, &total);
+  return rc ? rc : h2c_run(ctx, false, msgs, total, msg_off, 0, n, max_tries, d_out, nullptr, tries);
+}
+int bpmi_ec_hash_range(bpmi_ctx *ctx, const uint8_t *tail, uint64_t tail_len, uint64_t lo, uint64_t hi, uint32_t max_tries, uint8_t *out, uint8_t *tries) {
+  if (!ctx) return BPMI_E_ARG;
+  uint64_t total = 0;
+  const int rc = h2c_check(ctx, true, tail, nullptr, tail_len, lo, hi, 0, max_tries, out, &total);
+  return rc ? rc : h2c_run(ctx, true, tail, total, nullptr, lo, hi - lo, max_tries, nullptr, out, tries);
+}
+int bpmi_ec_hash_range_dev(bpmi_ctx *ctx, const uint8_t *tail, uint64_t tail_len, uint64_t lo, uint64_t hi, uint32_t max_tries, void *d_out, uint8_t *tries) {
+  if (!ctx) return BPMI_E_ARG;
+  uint64_t total = 0;
+  const int rc = h2c_check(ctx, true, tail, nullptr, tail_len, lo, hi, 0, max_tries, d_out, &total);
+  return rc ? rc : h2c_run(ctx, true, tail, total, nullptr, lo, hi - lo, max_tries, d_out, nullptr, tries);
 }
 int bpmi_memcpy_dev(bpmi_ctx *ctx, void *d_dst, const void *d_src, size_t bytes) {
   if (!ctx || (bytes && (!d_dst || !d_src))) return ctx ? fail(ctx, BPMI_E_ARG, "null argument") : BPMI_E_ARG;

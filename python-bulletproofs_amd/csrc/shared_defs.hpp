@@ -139,4 +139,7 @@ struct BpmiOptions {
   int opt_accum_chain = 1;              // experiment: 0 = the asynchronous pipeline's accumulations are NOT ordered after each other (the lanes run free)
   int opt_accum_stream = 0;             // experiment: the chained pipeline's accumulations on one low-priority stream of their own (msm_host.hpp)
   int opt_lane_prio = 0;                // experiment: queue priority of lanes 1 / 2 created AFTER the option is set (0 default, -1 high, 1 low)
+  // bulk hash to the curve (h2c_host.hpp)
+  int opt_h2c_plain = 0;                // 1: one message per lane with a loop per lane (k_h2c_plain) at EVERY size, not only where a lane has one message anyway
+  int opt_h2c_per_lane = 0;             // 1 .. 64: k_h2c_queue with that many messages per lane of a wave's span (0 = by the call's size, h2c_span)
 };

@@ -13,6 +13,7 @@ from . import _native
 
 Q = 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEBAAEDCE6AF48A03BBFD25E8CD0364141
 P_FIELD = 2**256 - 2**32 - 977
+MAX_N = 1 << 26         # BPMI_MAX_N
 
 
 class HostBuffer:
@@ -180,6 +181,49 @@ class Engine:
         self._ck(self.lib.bpmi_ec_decompress_batch(self.ctx, comp, n, out, ok))
         return out.raw, ok.raw[:n]
 
+    # ---- bulk hash to the curve (bpmi_ec_hash_*): the reference's elliptic_hash for many messages at once ----
+    @staticmethod
+    def _hash_buffers(n, with_tries, points=True):
+        n = n if 0 < n <= MAX_N else 0               # (a count the library refuses: nothing is allocated for it here either)
+        return (ctypes.create_string_buffer(max(64 * n, 1)) if points else None), (ctypes.create_string_buffer(max(n, 1)) if with_tries else None)
+
+    def _hash_result(self, n, out, tries):
+        if tries is None:
+            return out
+        return out, tries.raw[:n]
+
+    def ec_hash_batch_bytes(self, msgs, max_tries=0, with_tries=False, offsets=None):
+        """elliptic_hash of every message -> n x 64-byte wire points.  msgs: a list of byte strings, or with `offsets` (n + 1
+        numbers) the packed bytes they index.  with_tries: also the n counters that succeeded (0: no point within max_tries, the
+        point is then 64 zero bytes); without it such a message raises EngineError."""
+        packed, off, n = _pack_messages(msgs, offsets)
+        out, tries = self._hash_buffers(n, with_tries)
+        self._ck(self.lib.bpmi_ec_hash_batch(self.ctx, packed, off, n, max_tries, out, tries))
+        return self._hash_result(n, out.raw[:64 * n], tries)
+
+    def ec_hash_batch_dev(self, msgs, max_tries=0, with_tries=False, offsets=None, d_out=None):
+        """The same with the points left in device memory: `d_out` (n x 64 bytes) is filled, or a new DeviceBuffer returned."""
+        packed, off, n = _pack_messages(msgs, offsets)
+        d_out = self.alloc(max(64 * n, 16) if n <= MAX_N else 16) if d_out is None else d_out
+        _, tries = self._hash_buffers(n, with_tries, points=False)
+        self._ck(self.lib.bpmi_ec_hash_batch_dev(self.ctx, packed, off, n, max_tries, _ptr(d_out), tries))
+        return self._hash_result(n, d_out, tries)
+
+    def ec_hash_range_bytes(self, tail, lo, hi, max_tries=0, with_tries=False):
+        """elliptic_hash(str(i) || tail) for i in [lo, hi) -> (hi - lo) x 64-byte wire points (and the counters, as above)."""
+        n = max(hi - lo, 0)
+        out, tries = self._hash_buffers(n, with_tries)
+        self._ck(self.lib.bpmi_ec_hash_range(self.ctx, bytes(tail), len(tail), lo, hi, max_tries, out, tries))
+        return self._hash_result(n, out.raw[:64 * n], tries)
+
+    def ec_hash_range_dev(self, tail, lo, hi, max_tries=0, with_tries=False, d_out=None):
+        """The same with the points left in device memory, ready to be the generators of an MSM or of an inner-product argument."""
+        n = max(hi - lo, 0)
+        d_out = self.alloc(max(64 * n, 16) if n <= MAX_N else 16) if d_out is None else d_out
+        _, tries = self._hash_buffers(n, with_tries, points=False)
+        self._ck(self.lib.bpmi_ec_hash_range_dev(self.ctx, bytes(tail), len(tail), lo, hi, max_tries, _ptr(d_out), tries))
+        return self._hash_result(n, d_out, tries)
+
     def sc_dot_bytes(self, a, b, n):
         out = ctypes.create_string_buffer(32)
         self._ck(self.lib.bpmi_sc_dot(self.ctx, a, b, n, out))
@@ -315,6 +359,17 @@ def _ptr(x):
     if hasattr(x, "data_ptr"):  # torch tensor on the engine's device
         return x.data_ptr()
     return int(x)
+
+
+def _pack_messages(msgs, offsets):
+    """(packed bytes, n + 1 offsets as a C array, n) of a list of byte strings; `offsets` given: msgs is the packed bytes already."""
+    if offsets is None:
+        offsets = [0]
+        for m in msgs:
+            offsets.append(offsets[-1] + len(m))
+        msgs = b"".join(msgs)
+    n = len(offsets) - 1
+    return bytes(msgs), (ctypes.c_uint64 * (n + 1))(*offsets), n
 
 
 def sc_bytes(k):
