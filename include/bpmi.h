@@ -25,7 +25,7 @@
  *   - a ctx, the objects made from it and the library's host worker threads do not survive fork(): a child process creates
  *     its own ctx (the HIP runtime does not survive a fork either);
  *   - points handed in through HOST pointers are checked to be the identity or on the curve (option "validate_points", default 1;
- *     BPMI_E_ARG names the first bad index and no result is written).  Points behind DEVICE pointers are the caller's
+ *     BPMI_E_ARG names the first bad index and no result is written: a 64-byte result is zeroed).  Points behind DEVICE pointers are the caller's
  *     responsibility unless the option is 2: each must be 64 zero bytes or (x, y) with x, y < p and y^2 = x^3 + 7; anything else
  *     gives an unspecified (never out-of-bounds) result;
  *   - `*_dev` variants take DEVICE pointers (hipMalloc'd, or torch tensors'

@@ -574,7 +574,7 @@ int bpmi_ec_sum(bpmi_ctx *ctx, const uint8_t *pts, uint64_t n, uint8_t out[64]) 
   HIPCHK(ctx, h2d(ctx, dp, pts, 64 * n, ctx->stream));
   // (the per-GPU partial results a sharded caller folds here are the library's own outputs; a few points: checked on the host)
   const bool check = ctx->opt_validate >= 1;
-  if (check && n <= VALIDATE_HOST_MAX) { rc = validate_host(ctx, pts, n, "bpmi_ec_sum", "pts"); if (rc) return rc; }
+  if (check && n <= VALIDATE_HOST_MAX) { rc = validate_host(ctx, pts, n, "bpmi_ec_sum", "pts"); if (rc) { memset(out, 0, 64); return rc; } }
   else if (check) {
     rc = validate_begin(ctx, ctx->stream);
     if (rc) return rc;
@@ -592,7 +592,7 @@ int bpmi_ec_sum(bpmi_ctx *ctx, const uint8_t *pts, uint64_t n, uint8_t out[64]) 
   if (check && n > VALIDATE_HOST_MAX) {
     static const char *const names[] = {"pts"};
     rc = validate_end(ctx, "bpmi_ec_sum", names);
-    if (rc) return rc;
+    if (rc) { memset(out, 0, 64); return rc; }             // as bpmi_msm: a refused call leaves the identity's bytes, never a stale value
   }
   memcpy(out, tmp, 64);
   return BPMI_OK;

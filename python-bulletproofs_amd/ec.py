@@ -47,7 +47,8 @@ class Point:
         if curve is None:
             if x or y:
                 raise ValueError("identity must be (0, 0)")
-        elif not curve.is_point_on_curve((x, y)):
+        elif not (0 <= x < curve.p and 0 <= y < curve.p and curve.is_point_on_curve((x, y))):
+            # (the equation holds modulo p: x + p or y + p would pass it, be != the point, and reach the device unreduced)
             raise ValueError("coordinates are not on curve %s" % curve)
         self.x, self.y, self.curve = x, y, curve
         self._le = None

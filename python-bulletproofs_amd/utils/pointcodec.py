@@ -24,6 +24,12 @@ def point_to_b64(g: Point) -> bytes:
 def bytes_to_point(b: bytes) -> Point:
     if b == 0:                      # never true for bytes; kept because the reference has it (utils.py:121)
         return Point.IDENTITY_ELEMENT
+    if len(b) in (1, 1 + BYTE_LENGTH) and not any(b):    # what point_to_bytes writes for the identity, or the 33 zero bytes of the wire formats
+        return Point.IDENTITY_ELEMENT
+    if len(b) != 1 + BYTE_LENGTH or b[0] not in (2, 3):
+        # strict, like the device decoders (csrc/point_kernels.hpp ec_decompress_one): any other tag used to read as "odd", a
+        # second encoding of the same point; x >= p is refused by Point
+        raise ValueError("not a compressed point")
     want_odd = b[0] != 2
     x = int.from_bytes(b[1:], "big")
     y = mod_sqrt((x * x * x + CURVE.a * x + CURVE.b) % CURVE.p, CURVE.p)[0]
