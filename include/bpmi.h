@@ -167,6 +167,13 @@ int bpmi_sync(bpmi_ctx *ctx);
  *   "segscan_fused" / "hist_scan_fused" 1: the segmented scan's last level / the scan of the sort's partition counts run in the block that
  *                  finishes the level / the histogram kernel last (one launch fewer each).  Experiments that lost to the cost of the
  *                  device-scope fence every block needs (profiles/r05_last_block_fusions_ab.txt); default 0
+ *   "msm_batch_route" bpmi_msm_batch[_dev[_enqueue]]: 0 (default) the route follows the sizes -- the light shape up to 512 pairs per vector, the
+ *                  k_msm_mid shape with ceil(pairs / 8 448) blocks per window up to 25 344 pairs, above that a loop of single MSMs, which
+ *                  also runs a batch of fewer than 32 vectors (64 with three blocks per window): the measured crossovers,
+ *                  profiles/r10_msm_batch.txt --; 1 / 2 / 3 forces the light shape / the k_msm_mid shape (up to 33 792 pairs) / the loop
+ *                  (tests, A/B runs: a forced shape that cannot hold the vectors is BPMI_E_ARG)
+ *   "msm_batch_vecs" ... vectors per launch: 0 (default) as many as keep a launch's window sums (vectors x 37 x parts x 144 B) within
+ *                  256 MB; a larger batch runs as consecutive launches over row ranges
  *   "fold_wnaf"    the ladder of that 16-way fold: 2 (default) width-4 non-adjacent forms of the coefficients' GLV halves over affine
  *                  tables of 3P, 5P, 7P and of beta x (k_ec_multifold_w4g; 792 B of workspace per generator, kept by the ctx after the first fold),
  *                  1 of the whole coefficients (k_ec_multifold_w4), 0 the plain NAF ladder without tables (k_ec_multifold) */
@@ -213,6 +220,33 @@ int bpmi_msm_segs_dev(bpmi_ctx *ctx, uint32_t nseg, const void *const *d_pts, co
  * such as A / S (rangeproof_prover.py:52,60) and T1 / T2 (:71-72) cost one round trip instead of two. */
 int bpmi_msm2(bpmi_ctx *ctx, const uint8_t *pts0, const uint8_t *scalars0, uint64_t n0, uint8_t out0[64], const uint8_t *pts1,
               const uint8_t *scalars1, uint64_t n1, uint8_t out1[64]);
+
+/* ---- MANY scalar vectors over ONE shared point set: n_vec multi-scalar multiplications in one launch ----------------
+ *   out[v] = sum_s sum_{i < n[s]} scalars[s][v][i] * pts[s][i]        v in [0, n_vec)
+ * Replaces a LOOP of Pippenger.multiexp over the same gs (src/pippenger/pippenger.py:22-61) -- the Pedersen vector commitments
+ * vector_commitment(gs, hs, a_p, b_p) of many vectors (src/utils/commitments.py:13), the statements P_p = <a_p, g> + <b_p, h> + c_p u
+ * of a run of inner-product arguments, the columns of a table under one generator set.  Below ~10^4 pairs such a loop is almost all
+ * fixed cost per call; here block (vector, window) of ONE launch runs the one-block-per-window method in LDS and a second launch
+ * combines every vector's windows, one lane per vector.
+ *   nseg        1 .. 3 segments, as in bpmi_msm_segs_dev; d_pts[s]: n[s] points shared by every vector (n[s] = 0 is allowed, the
+ *               segment's pointers are then not read)
+ *   d_scalars[s] a row-major matrix of n_vec rows x n[s] scalars of 32 bytes: row v starts at byte v * n[s] * 32
+ *   out         HOST, n_vec x 64 bytes, complete on return (bpmi_msm_batch_dev, bpmi_msm_batch)
+ *   d_out       DEVICE, n_vec x 64 bytes (bpmi_msm_batch_dev_enqueue): the same work without the wait, ordered on the ctx stream; read it
+ *               after bpmi_sync, like bpmi_ec_sum_dev_enqueue's.  (Vectors of more than 25 344 pairs, and batches of fewer than 32
+ *               vectors, run as a loop of single MSMs whose tails are the host's: that route waits here too.)
+ * Conventions of bpmi_msm: scalars are any 256-bit values, reduced mod q as they are loaded; the identity is 64 zero bytes on input
+ * and output; no pairs at all gives n_vec identities; n_vec = 0 is BPMI_OK and touches nothing.  bpmi_msm_batch (one segment, HOST
+ * pointers) checks its points under "validate_points" >= 1 exactly as bpmi_msm does (BPMI_E_ARG names the first bad index, out is
+ * zeroed); level 2 also checks the points of bpmi_msm_batch_dev.
+ * Refused with BPMI_E_ARG before anything is read or allocated, the message naming the bound: nseg outside 1 .. 3, a NULL pointer, more
+ * than BPMI_MAX_N pairs per vector, n_vec > 2^20, n_vec x pairs > 2^30.  The calls use the workspace of the ctx's first lane: while an
+ * asynchronous MSM is pending in a slot that lives there (slot 0; every slot without "async_lanes") they fail with BPMI_E_STATE.
+ * Routes and launch shapes: csrc/msm_batch_plan_host.hpp; options "msm_batch_route", "msm_batch_vecs". */
+int bpmi_msm_batch(bpmi_ctx *ctx, const uint8_t *pts, uint64_t n, const uint8_t *scalars, uint64_t n_vec, uint8_t *out);
+int bpmi_msm_batch_dev(bpmi_ctx *ctx, uint32_t nseg, const void *const *d_pts, const uint64_t *n, const void *const *d_scalars, uint64_t n_vec, uint8_t *out);
+int bpmi_msm_batch_dev_enqueue(bpmi_ctx *ctx, uint32_t nseg, const void *const *d_pts, const uint64_t *n, const void *const *d_scalars, uint64_t n_vec,
+                               void *d_out);
 
 /* ---- batched point operations ----------------------------------------------------
  * out[i] = scalars[i] * pts[i]       replaces `ModP * Point` / `int * Point`

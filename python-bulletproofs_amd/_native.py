@@ -42,6 +42,9 @@ SIGNATURES = {
     "bpmi_ec_hash_range_dev": (_i, [_vp, _cp, _u64, _u64, _u64, ctypes.c_uint32, _vp, _cp]),
     "bpmi_memcpy_dev": (_i, [_vp, _vp, _vp, _sz]),
     "bpmi_msm_segs_dev": (_i, [_vp, ctypes.c_uint32, _vp, _vp, _vp, _cp]),
+    "bpmi_msm_batch": (_i, [_vp, _cp, _u64, _cp, _u64, _vp]),
+    "bpmi_msm_batch_dev": (_i, [_vp, ctypes.c_uint32, _vp, _vp, _vp, _u64, _vp]),
+    "bpmi_msm_batch_dev_enqueue": (_i, [_vp, ctypes.c_uint32, _vp, _vp, _vp, _u64, _vp]),
     "bpmi_sc_dot": (_i, [_vp, _cp, _cp, _u64, _cp]),
     "bpmi_sc_dot_dev": (_i, [_vp, _vp, _vp, _u64, _cp]),
     "bpmi_sc_fold": (_i, [_vp, _cp, _cp, _cp, _cp, _u64, _cp]),

@@ -51,6 +51,7 @@ using namespace bpmi;
 #include "rp_batch_plan_host.hpp"
 #include "rp_prove_plan_host.hpp"
 #include "ipa_batch_plan_host.hpp"
+#include "msm_batch_plan_host.hpp"
 #include "context.hpp"
 #include "device_util.hpp"
 #include "msm_kernels.hpp"
@@ -153,6 +154,8 @@ int bpmi_set_option(bpmi_ctx *ctx, const char *name, int64_t value) {
   if (!strcmp(name, "accum_stream")) { if (value < 0 || value > 2) return fail(ctx, BPMI_E_ARG, "accum_stream must be 0, 1 or 2"); ctx->opt_accum_stream = (int)value; return BPMI_OK; }
   if (!strcmp(name, "lane_priority")) { if (value < -1 || value > 1) return fail(ctx, BPMI_E_ARG, "lane_priority must be -1, 0 or 1"); ctx->opt_lane_prio = (int)value; return BPMI_OK; }
   if (!strcmp(name, "h2c_plain")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "h2c_plain must be 0 or 1"); ctx->opt_h2c_plain = (int)value; return BPMI_OK; }
+  if (!strcmp(name, "msm_batch_route")) { if (value < 0 || value > 3) return fail(ctx, BPMI_E_ARG, "msm_batch_route must be 0 .. 3"); ctx->opt_msm_batch_route = (int)value; return BPMI_OK; }
+  if (!strcmp(name, "msm_batch_vecs")) { if (value < 0 || value > (1 << 20)) return fail(ctx, BPMI_E_ARG, "msm_batch_vecs must be 0 .. 2^20"); ctx->opt_msm_batch_vecs = (int)value; return BPMI_OK; }
   if (!strcmp(name, "h2c_per_lane")) { if (value < 0 || value > 64) return fail(ctx, BPMI_E_ARG, "h2c_per_lane must be 0 .. 64"); ctx->opt_h2c_per_lane = (int)value; return BPMI_OK; }
   if (!strcmp(name, "pair_sched")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "pair_sched must be 0 or 1"); ctx->opt_pair_sched = (int)value; return BPMI_OK; }
   if (!strcmp(name, "prover_wire_format")) { if (value != 2 && value != 3) return fail(ctx, BPMI_E_ARG, "prover_wire_format must be 2 or 3"); ctx->opt_prover_wire = (int)value; return BPMI_OK; }
@@ -897,6 +900,7 @@ int bpmi_ipa_verify_dev(bpmi_ctx *ctx, const void *d_g, const void *d_h, const v
 
 #include "ipa_host.hpp"
 #include "ipa_batch_host.hpp"
+#include "msm_batch_host.hpp"
 #include "rp_batch_dev_host.hpp"
 
 extern "C" {

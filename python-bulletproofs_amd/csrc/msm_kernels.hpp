@@ -1818,6 +1818,64 @@ __global__ void __launch_bounds__(64) k_group_tail(const u32 *__restrict__ E, u3
   store_words16(out + 16ull * t, w16);
 }
 
+// ---- many scalar vectors over ONE shared point set in one launch (bpmi_msm_batch*, msm_batch_host.hpp) --------------------------------
+// out[v] = sum_s sum_i sc[s][v][i] pts[s][i]: the point segments are the same for every vector, vector v's scalars of segment s are row
+// v of a row-major matrix of n[s] columns.  Block (v, w) = blockIdx.x, part = blockIdx.z: the Segs of row v in registers, then window w
+// of it with the body of k_msm_mid on pairs [total part / parts, total (part + 1) / parts) -- k_msm_group's launch shape with a `parts`
+// split (msm_batch_plan_host.hpp picks shape and parts).  A launch runs rows [v0, v0 + gridDim.x / W); its window sums go to
+// E[row - v0][w][part].
+struct BatchMsm {
+  const u32 *pts[3], *sc[3];          // the shared points; the scalar matrices, row v of matrix s at sc[s] + 8 n[s] v words
+  u32 n[3];
+  u32 W, parts, v0;
+  u32 *E;
+};
+template <u32 THREADS, u32 NMAX> __global__ void __launch_bounds__(THREADS) k_msm_batch(BatchMsm J) {
+  const u32 t = blockIdx.x / J.W, w = blockIdx.x - t * J.W;
+  const u64 v = (u64)J.v0 + t;
+  Segs s;
+#pragma unroll
+  for (int k = 0; k < 3; k++) { s.pts[k] = J.pts[k]; s.sc[k] = J.sc[k] + 8ull * J.n[k] * v; s.n[k] = J.n[k]; }
+  s.total = s.n[0] + s.n[1] + s.n[2];
+  s.hlog[0] = s.hlog[1] = s.hlog[2] = 0xFFu;
+  s.phase[0] = s.phase[1] = s.phase[2] = 0;
+  s.glv_sub = nullptr; s.glv_neg = nullptr; s.glv_bx = nullptr;
+  MsmGeom g = {};                                  // (the body reads n and W only)
+  g.n = s.total; g.c = MID_C; g.W = J.W; g.B = MID_B;
+  u32 *const Et = J.E + (u64)t * J.W * J.parts * XYZZ_WORDS;
+  msm_mid_block<THREADS, NMAX>(s, g, w, J.parts, blockIdx.z, Et);
+}
+template __global__ void k_msm_batch<MID_THREADS, MID_NMAX>(BatchMsm);
+template __global__ void k_msm_batch<GROUP_LIGHT_THREADS, GROUP_LIGHT_NMAX>(BatchMsm);
+
+// the tails of a launch of k_msm_batch: ONE LANE per vector, as k_group_tail (64 chains of dependent additions in the lanes of a wave
+// take the time of one).  msm_tail_combine picks ONE record per bit position, so the `parts` records of a window -- all at the same bit
+// offset -- are added here first; then c doublings per window down the Horner chain, canonical affine, 16 words to out[t].  A vector of
+// zeros, or one whose terms cancel, ends at the identity: 64 zero bytes.
+__global__ void __launch_bounds__(64) k_msm_batch_tail(const u32 *__restrict__ E, u32 W, u32 c, u32 parts, u32 nvec, u32 *__restrict__ out) {
+  const u32 t = blockIdx.x * 64u + threadIdx.x;
+  if (t >= nvec) return;
+  const u32 *Et = E + (u64)t * W * parts * XYZZ_WORDS;
+  xyzz acc;
+  xyzz_set_inf(acc);
+#pragma unroll 1
+  for (u32 w = W; w-- > 0;) {
+#pragma unroll 1
+    for (u32 r = 0; r < c; r++) xyzz_dbl(acc, acc);
+#pragma unroll 1
+    for (u32 p = 0; p < parts; p++) {
+      xyzz e;
+      xyzz_load(e, Et + ((u64)w * parts + p) * XYZZ_WORDS);
+      xyzz_add(acc, acc, e);
+    }
+  }
+  affine r_aff;
+  xyzz_to_affine(r_aff, acc);
+  u32 w16[16];
+  affine_to_words(w16, r_aff);
+  store_words16(out + 16ull * t, w16);
+}
+
 #if defined(BPMI_ISA_PROBE)
 // tools/isa_counts.py: the main path of the mixed addition on its own (no loads from the point array, no exceptional
 // cases), so that its instructions can be counted in the ISA.  Not part of the product build.

@@ -142,4 +142,7 @@ struct BpmiOptions {
   // bulk hash to the curve (h2c_host.hpp)
   int opt_h2c_plain = 0;                // 1: one message per lane with a loop per lane (k_h2c_plain) at EVERY size, not only where a lane has one message anyway
   int opt_h2c_per_lane = 0;             // 1 .. 64: k_h2c_queue with that many messages per lane of a wave's span (0 = by the call's size, h2c_span)
+  // batched MSM over shared points (msm_batch_plan_host.hpp)
+  int opt_msm_batch_route = 0;          // 0 by the sizes, 1 / 2 / 3 forces the light shape / the k_msm_mid shape / the loop of single MSMs (tests, A/B runs)
+  int opt_msm_batch_vecs = 0;           // vectors per launch (0 = as many as keep a launch's window sums within 256 MB)
 };

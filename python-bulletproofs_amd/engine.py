@@ -146,6 +146,29 @@ class Engine:
         self._ck(self.lib.bpmi_msm_finish(self.ctx, slot, out))
         return out.raw
 
+    def msm_batch_dev(self, d_pts, ns, d_scalars, n_vec, d_out=None):
+        """n_vec MSMs over ONE shared point set (bpmi_msm_batch_dev): d_pts / ns / d_scalars name 1 .. 3 segments -- ns[s] points each,
+        d_scalars[s] a row-major matrix of n_vec rows of ns[s] scalars.  Returns the n_vec x 64 result bytes; with d_out (device memory,
+        n_vec x 64 bytes) the work is only queued (bpmi_msm_batch_dev_enqueue), None is returned and d_out is read after sync()."""
+        nseg = len(ns)
+        if not (len(d_pts) == len(d_scalars) == nseg):
+            raise ValueError("d_pts, ns and d_scalars name the same segments")
+        P = (ctypes.c_void_p * nseg)(*[_ptr(p) if p is not None else None for p in d_pts])
+        S = (ctypes.c_void_p * nseg)(*[_ptr(s) if s is not None else None for s in d_scalars])
+        N = (ctypes.c_uint64 * nseg)(*ns)
+        if d_out is not None:
+            self._ck(self.lib.bpmi_msm_batch_dev_enqueue(self.ctx, nseg, P, N, S, n_vec, _ptr(d_out)))
+            return None
+        out = ctypes.create_string_buffer(max(64 * n_vec, 1))
+        self._ck(self.lib.bpmi_msm_batch_dev(self.ctx, nseg, P, N, S, n_vec, out))
+        return out.raw[:64 * n_vec]
+
+    def msm_batch_bytes(self, pts, scalars, n, n_vec):
+        """The same from host bytes, one segment (bpmi_msm_batch): pts n x 64 bytes, scalars n_vec rows of n x 32 bytes."""
+        out = ctypes.create_string_buffer(max(64 * n_vec, 1))
+        self._ck(self.lib.bpmi_msm_batch(self.ctx, pts, n, scalars, n_vec, out))
+        return out.raw[:64 * n_vec]
+
     def msm_geometry(self, n, pipelined=False):
         """What an MSM of n pairs runs as under the current options (bpmi_msm_geometry): a dict with the kernel family, window bits,
         windows (and how many are one bit wider), buckets, chunk length, slices and pairs per slice.  No GPU work."""

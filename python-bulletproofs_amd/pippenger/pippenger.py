@@ -49,6 +49,33 @@ class Pippenger:
             out = eng.msm_bytes(pack_points(gs), scalars, n)
         return Point.from_le64(out)
 
+    def multiexp_batch(self, gs, rows):
+        """[multiexp(gs, r) for r in rows] -- many exponent vectors over the same bases.  On secp256k1 it is ONE native call
+        (bpmi_msm_batch / bpmi_msm_batch_dev: block (vector, window) of one launch); any other group runs the loop.  Not in the
+        reference, whose callers loop over multiexp (src/pippenger/pippenger.py:22-61)."""
+        rows = list(rows)
+        n = gs.n if isinstance(gs, DevicePoints) else len(gs)
+        for r in rows:
+            if len(r) != n:
+                raise Exception("Different number of group elements and exponents")
+        if not rows:
+            return []
+        if n == 0:
+            return [self.G.unit for _ in rows]
+        if not (isinstance(self.G, EC) and self.G.curve is secp256k1):
+            return [self.multiexp(gs, r) for r in rows]
+        eng = _engine.default_engine()
+        scalars = b"".join(pack_scalars(r, self.order) for r in rows)
+        if isinstance(gs, DevicePoints):
+            d_sc = eng.upload(scalars)
+            try:
+                out = eng.msm_batch_dev([gs.buf], [n], [d_sc], len(rows))
+            finally:
+                d_sc.free()
+        else:
+            out = eng.msm_batch_bytes(pack_points(gs), scalars, n, len(rows))
+        return [Point.from_le64(out[64 * v: 64 * v + 64]) for v in range(len(rows))]
+
     def multiexp2(self, gs0, es0, gs1, es1):
         """(multiexp(gs0, es0), multiexp(gs1, es1)) for two independent sums; on secp256k1 they are
         overlapped on the engine's two lanes (bpmi_msm2).  Not in the reference: its callers compute
