@@ -56,6 +56,7 @@ extern "C" {
 typedef struct bpmi_ctx bpmi_ctx;
 typedef struct bpmi_ipa bpmi_ipa;
 typedef struct bpmi_rp_prover bpmi_rp_prover;
+typedef struct bpmi_ipa_batch_prover bpmi_ipa_batch_prover;
 
 /* ---- library / context ---------------------------------------------------- */
 int bpmi_version(void);
@@ -549,6 +550,49 @@ int bpmi_rp_prover_last_ms(const bpmi_rp_prover *pv, double ms[7]);
  * out: count x 64 B affine (x, y little-endian; the identity is 64 zero bytes).  count <= 2^24; count = 0 is BPMI_OK.  Shares the
  * prover's buffers: one call at a time per prover, like proving. */
 int bpmi_rp_prover_commit_batch(bpmi_rp_prover *pv, uint64_t count, const uint8_t *values, const uint8_t *gammas, uint8_t *out);
+
+/* ---- batched inner-product prover ------------------------------------------ */
+/* Many inner-product arguments over ONE generator set (g, h of n points each, one u), proved in one device call: a loop of
+ * `NIProver(g, h, u, P_p, c_p, a_p, b_p, group, seed_p).prove()` (src/innerproduct/inner_product_prover.py:11-45) or of
+ * `FastNIProver2(g, h, u, P_p, a_p, b_p, group, transcript_p).prove()` (:48-110), with the transcript of
+ * src/utils/transcript.py:13-33 and mod_hash of src/utils/utils.py:84-97 -- the same proofs byte for
+ * byte, every protocol step ONE launch over all proofs, every scalar multiplication a lookup in tables of the fixed generators, the
+ * Fiat-Shamir hashes on the device (the machinery of bpmi_rp_prove_batch's Protocol-2 phase).  What bpmi_ipa_verify_batch_dev consumes.
+ *   bpmi_ipa_batch_prover_create  (:20-27, :42-54) n: a power of two in [1, 1024] (longer vectors are the single-proof prover's, bpmi_ipa_create:
+ *                           one proof fills the chip there); g, h: n 64-byte points each; u: one.  Builds the tables of the 2n + 1
+ *                           bases (windows of "prover_table_bits" bits; default as for bpmi_rp_prover_create: 16 bits up to 128
+ *                           elements, 302 MB at n = 4, 4.4 GB at n = 64) and keeps them for the prover's lifetime; a table that does
+ *                           not fit the device is BPMI_E_NOMEM.  The points are checked to be on the curve (option "validate_points"
+ *                           >= 1): BPMI_E_ARG names the first bad one.  The identity, equal and opposite generators are legal.
+ *                           h_scale: NULL, or n scalars c_i in [0, q): the argument runs over the generators c_i h_i without
+ *                           computing them (the extension of bpmi_ipa_create_scaled and bpmi_ipa_verify_batch_dev).
+ *   bpmi_ipa_prove_batch    protocol 1 (:29-36): seeds[seed_off[p] .. seed_off[p+1]) is proof p's transcript seed; x_p =
+ *                           mod_hash(base64(seed_p) "&"); head[p] = u_new || P_new = x_p u || P_p + (x_p c_p) u (2 x 64 B affine);
+ *                           c: n_proofs x 32 B, or NULL for c_p = <a_p, b_p>; P: n_proofs x 64 B (checked under "validate_points"
+ *                           >= 1: BPMI_E_ARG names the index; the identity is legal).
+ *                           protocol 2 (:56-68, :94-110): seeds[..] is the `transcript` argument, appended after the "&" of the empty
+ *                           seed (it may be empty); c, P and head must be NULL -- the reference's prover never reads P there.
+ *                           a, b: n_proofs x n x 32 B little-endian in [0, q) -- checked, like c: BPMI_E_ARG names the first index
+ *                           that is not.  A seed has at most 65 535 bytes; seeds may be NULL when every seed is empty.
+ *                           Outputs: ab[p] = a || b (2 x 32 B); xs[p] = k x 32 B, k = log2 n; LR[p] = L_0 .. L_(k-1) R_0 .. R_(k-1),
+ *                           64 B affine each (the identity is 64 zero bytes); transcripts[tr_off[p] .. tr_off[p+1]) = the final
+ *                           digest text of the Protocol-2 argument (under protocol 1 it starts with "&" and the outer transcript
+ *                           base64(seed) "&" str(x) "&"); tr_off has n_proofs + 1 entries; cap >= n_proofs x
+ *                           bpmi_ipa_prove_batch_transcript_bytes (of the longest seed).  n = 1 has no rounds: xs and LR may be NULL.
+ *                           At most 2^20 proofs and 2^27 elements (n_proofs x n) per call.  A wrong protocol, NULL where an array is
+ *                           required or non-NULL where it must be NULL, a count beyond the caps, a seed that is too long, decreasing
+ *                           offsets and a cap that is too small are BPMI_E_ARG before anything is read or allocated; no output is
+ *                           written on any error.  n_proofs = 0 is BPMI_OK and touches nothing.  One call at a time per prover and ctx.
+ *   bpmi_ipa_batch_prover_last_ms  device milliseconds of the last batch: the transcripts' start and the head | the rounds | the copy to
+ *                           the host | the whole batch */
+int bpmi_ipa_batch_prover_create(bpmi_ctx *ctx, uint32_t n, const uint8_t *g, const uint8_t *h, const uint8_t u[64], const uint8_t *h_scale,
+                                 bpmi_ipa_batch_prover **out);
+void bpmi_ipa_batch_prover_destroy(bpmi_ipa_batch_prover *pv);
+uint64_t bpmi_ipa_prove_batch_transcript_bytes(const bpmi_ipa_batch_prover *pv, int protocol, uint64_t seed_len);
+int bpmi_ipa_prove_batch(bpmi_ipa_batch_prover *pv, int protocol, uint64_t n_proofs, const uint8_t *a, const uint8_t *b, const uint8_t *c, const uint8_t *P,
+                         const uint8_t *seeds, const uint64_t *seed_off, uint8_t *ab, uint8_t *xs, uint8_t *LR, uint8_t *head, uint8_t *transcripts,
+                         uint64_t cap, uint64_t *tr_off);
+int bpmi_ipa_batch_prover_last_ms(const bpmi_ipa_batch_prover *pv, double ms[4]);
 
 /* Page-locked host memory (hipHostMalloc) for buffers handed to the library repeatedly, e.g. the receive buffer of wire proofs. */
 int bpmi_host_alloc(bpmi_ctx *ctx, size_t bytes, void **out);

@@ -77,6 +77,11 @@ SIGNATURES = {
     "bpmi_rp_prove_batch": (_i, [_vp, _u64, _cp, _cp, _cp, _vp, _vp, _u64, _vp]),
     "bpmi_rp_prover_commit_batch": (_i, [_vp, _u64, _cp, _cp, _vp]),
     "bpmi_rp_prover_last_ms": (_i, [_vp, ctypes.POINTER(ctypes.c_double)]),
+    "bpmi_ipa_batch_prover_create": (_i, [_vp, ctypes.c_uint32, _cp, _cp, _cp, _cp, ctypes.POINTER(_vp)]),
+    "bpmi_ipa_batch_prover_destroy": (None, [_vp]),
+    "bpmi_ipa_prove_batch_transcript_bytes": (_u64, [_vp, _i, _u64]),
+    "bpmi_ipa_prove_batch": (_i, [_vp, _i, _u64, _cp, _cp, _cp, _cp, _cp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "bpmi_ipa_batch_prover_last_ms": (_i, [_vp, ctypes.POINTER(ctypes.c_double)]),
     "bpmi_host_alloc": (_i, [_vp, ctypes.c_size_t, ctypes.POINTER(_vp)]),
     "bpmi_host_free": (_i, [_vp, _vp]),
     "bpmi_ipa_destroy": (None, [_vp]),

@@ -50,6 +50,7 @@ using namespace bpmi;
 #include "msm_plan_host.hpp"
 #include "rp_batch_plan_host.hpp"
 #include "rp_prove_plan_host.hpp"
+#include "ipa_prove_plan_host.hpp"
 #include "ipa_batch_plan_host.hpp"
 #include "msm_batch_plan_host.hpp"
 #include "context.hpp"
@@ -68,6 +69,7 @@ using namespace bpmi;
 #include "rp_wire_v2_host.hpp"
 #include "rp_batch_kernels.hpp"
 #include "rp_prove_kernels.hpp"
+#include "ipa_prove_kernels.hpp"
 #include "h2c.hpp"
 #include "h2c_kernels.hpp"
 #include "h2c_host.hpp"
@@ -1019,3 +1021,4 @@ const char *bpmi_profile_stage_name(int stage) {
 }  // extern "C"
 
 #include "rp_prove_host.hpp"
+#include "ipa_prove_host.hpp"

@@ -51,6 +51,41 @@ static size_t b64_into(char *o, const uint8_t *p, size_t n) {
   return (size_t)(q - o);
 }
 
+// The fixed-base tables of nb bases (basepts: nb x 64 bytes on the host), shared by the batched provers: the window bases 2^(tw k) base_b
+// by the engine's batched multiplication, then the multiples level by level (rp_prove_kernels.hpp).  *d_base <- the bases in device
+// memory with `tail` spare bytes behind them (the caller's, to free); *table <- [nb][wt][bt] affine points (the caller's).  fn: the
+// entry point's name, for the messages.  On an error both may be set: the caller frees them as on success.
+static int build_tables(bpmi_ctx *ctx, const char *fn, const std::vector<uint8_t> &basepts, u32 nb, size_t tail, u32 tw, u32 wt, u32 bt, u32 **d_base_out, u32 **table) {
+  const size_t entries = (size_t)nb * wt * bt;
+  const u32 nbk = nb * wt;                           // (base, window) pairs
+  u32 *d_base = nullptr, *d_pts = nullptr, *d_sc = nullptr, *d_wb = nullptr;
+  hipError_t e = hipMalloc(&d_base, 64 * (size_t)nb + tail);
+  *d_base_out = d_base;
+  if (e == hipSuccess) e = hipMalloc(&d_pts, 64 * (size_t)nbk);
+  if (e == hipSuccess) e = hipMalloc(&d_sc, 32 * (size_t)nbk);
+  if (e == hipSuccess) e = hipMalloc(&d_wb, 64 * (size_t)nbk);
+  if (e == hipSuccess) e = hipMalloc(table, 64 * entries);
+  auto free_tmp = [&]() { if (d_pts) (void)hipFree(d_pts); if (d_sc) (void)hipFree(d_sc); if (d_wb) (void)hipFree(d_wb); };
+  if (e != hipSuccess) { free_tmp(); return fail(ctx, BPMI_E_NOMEM, std::string(fn) + ": " + hipGetErrorString(e)); }
+  e = hipMemcpyAsync(d_base, basepts.data(), basepts.size(), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);          // (basepts is pageable)
+  if (e != hipSuccess) { free_tmp(); return fail(ctx, BPMI_E_HIP, std::string(fn) + ": " + hipGetErrorString(e)); }
+  rpp::Tab T0 = {nullptr, tw, wt, bt};
+  hipLaunchKernelGGL(rpp::k_pv_window_scalars, dim3((nbk + 255) / 256), dim3(256), 0, ctx->stream, d_base, nb, T0, d_pts, d_sc);
+  int rc = bpmi_ec_mul_batch_dev(ctx, d_pts, d_sc, nbk, d_wb);
+  if (rc == BPMI_OK) {
+    hipLaunchKernelGGL(rpp::k_pv_table_seed, dim3((nbk + 255) / 256), dim3(256), 0, ctx->stream, d_wb, nbk, T0, *table);
+    for (u32 j = 0; j + 1 < tw; j++) {
+      const size_t threads = (size_t)nbk << j;
+      hipLaunchKernelGGL(rpp::k_pv_table_level, dim3((u32)((threads + 255) / 256)), dim3(256), 0, ctx->stream, nbk, T0, j, *table);
+    }
+    e = hipGetLastError();
+    if (e != hipSuccess) rc = fail(ctx, BPMI_E_HIP, std::string(fn) + ": " + hipGetErrorString(e));
+  }
+  free_tmp();
+  return rc;
+}
+
 }  // namespace rpp_host
 
 extern "C" {
@@ -131,35 +166,13 @@ static int rp_prover_create_impl(bpmi_ctx *ctx, uint32_t vbits, uint32_t m, cons
   // 11: 29.3 / 206 / 44, 12: 28.1 / 378 / 72, 13: 26.6 / 687 / 126 with round 5's builder; round 6's builder and 14 .. 16 bits:
   // profiles/r06_batch_prover_table_bits.txt)
   pv->tw = plan.tw; pv->wt = plan.wt; pv->bt = plan.bt;
-  const size_t entries = (size_t)nb * pv->wt * pv->bt;
-  const u32 nbk = nb * pv->wt;                       // (base, window) pairs
   std::vector<uint8_t> basepts(64 * (size_t)nb);
   memcpy(&basepts[0], g, 64); memcpy(&basepts[64], h, 64); memcpy(&basepts[128], u, 64);
   memcpy(&basepts[192], gs, 64 * (size_t)n); memcpy(&basepts[192 + 64 * (size_t)n], hs, 64 * (size_t)n);
-  u32 *d_base = nullptr, *d_pts = nullptr, *d_sc = nullptr, *d_wb = nullptr;
-  hipError_t e = hipMalloc(&d_base, 64 * (size_t)nb + 96);
-  if (e == hipSuccess) e = hipMalloc(&d_pts, 64 * (size_t)nbk);
-  if (e == hipSuccess) e = hipMalloc(&d_sc, 32 * (size_t)nbk);
-  if (e == hipSuccess) e = hipMalloc(&d_wb, 64 * (size_t)nbk);
-  if (e == hipSuccess) e = hipMalloc(&pv->table, 64 * entries);
-  auto free_tmp = [&]() { if (d_base) (void)hipFree(d_base); if (d_pts) (void)hipFree(d_pts); if (d_sc) (void)hipFree(d_sc); if (d_wb) (void)hipFree(d_wb); };
-  if (e != hipSuccess) { free_tmp(); return bail(fail(ctx, BPMI_E_NOMEM, std::string("bpmi_rp_prover_create: ") + hipGetErrorString(e))); }
-  e = hipMemcpyAsync(d_base, basepts.data(), basepts.size(), hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);          // (basepts is pageable and local)
-  if (e != hipSuccess) { free_tmp(); return bail(fail(ctx, BPMI_E_HIP, std::string("bpmi_rp_prover_create: ") + hipGetErrorString(e))); }
-  // the window bases 2^(tw k) base_b by the engine's batched multiplication, then the multiples level by level (rp_prove_kernels.hpp)
-  rpp::Tab T0 = {nullptr, pv->tw, pv->wt, pv->bt};
-  hipLaunchKernelGGL(rpp::k_pv_window_scalars, dim3((nbk + 255) / 256), dim3(256), 0, ctx->stream, d_base, nb, T0, d_pts, d_sc);
-  int rc = bpmi_ec_mul_batch_dev(ctx, d_pts, d_sc, nbk, d_wb);
-  if (rc == BPMI_OK) {
-    hipLaunchKernelGGL(rpp::k_pv_table_seed, dim3((nbk + 255) / 256), dim3(256), 0, ctx->stream, d_wb, nbk, T0, pv->table);
-    for (u32 j = 0; j + 1 < pv->tw; j++) {
-      const size_t threads = (size_t)nbk << j;
-      hipLaunchKernelGGL(rpp::k_pv_table_level, dim3((u32)((threads + 255) / 256)), dim3(256), 0, ctx->stream, nbk, T0, j, pv->table);
-    }
-    e = hipGetLastError();
-    if (e != hipSuccess) rc = fail(ctx, BPMI_E_HIP, std::string("bpmi_rp_prover_create: ") + hipGetErrorString(e));
-  }
+  u32 *d_base = nullptr;                             // the bases, and 96 bytes for x_ip and u_new
+  hipError_t e = hipSuccess;
+  int rc = rpp_host::build_tables(ctx, "bpmi_rp_prover_create", basepts, nb, 96, pv->tw, pv->wt, pv->bt, &d_base, &pv->table);
+  auto free_tmp = [&]() { if (d_base) (void)hipFree(d_base); };
   // u_new = x_ip u
   if (rc == BPMI_OK) {
     e = hipMemcpyAsync((char *)d_base + 64 * (size_t)nb, pv->x_ip.v, 32, hipMemcpyHostToDevice, ctx->stream);

@@ -31,8 +31,9 @@ struct RppPlan {
   std::vector<unsigned short> bases;
 };
 
-// (3 + 2 elems) bases x ceil(256 / w) windows x 2^(w-1) entries of 64 bytes
-static inline uint64_t rpp_table_bytes(u32 elems, u32 w) { return (uint64_t)(3 + 2 * elems) * ((256 + w - 1) / w) * ((uint64_t)1 << (w - 1)) * 64; }
+// nbases bases x ceil(256 / w) windows x 2^(w-1) entries of 64 bytes (the range prover: 3 + 2 elems bases; ipa_prove_plan_host.hpp: 1 + 2 elems)
+static inline uint64_t rpp_table_bytes_of(u32 nbases, u32 w) { return (uint64_t)nbases * ((256 + w - 1) / w) * ((uint64_t)1 << (w - 1)) * 64; }
+static inline uint64_t rpp_table_bytes(u32 elems, u32 w) { return rpp_table_bytes_of(3 + 2 * elems, w); }
 // Window bits under option "prover_table_bits" = 0.  Up to 128 elements: 16.  Above: the widest width whose table is no larger than
 // the largest one of those -- 128 elements at 16 bits, 8.7 GB (256 elements: 14 bits, 5.1 GB; 16 bits would be 69 GB at 1 024)
 static inline u32 rpp_default_table_bits(u32 elems) {
