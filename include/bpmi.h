@@ -103,6 +103,13 @@ int bpmi_sync(bpmi_ctx *ctx);
  *   "rounds"       where another MSM's kernels run beside an accumulation (the asynchronous pipeline, the slices of a large MSM, a synchronous
  *                  pair from 2^19 pairs) its chunk length is ceil(W n / (64 x 3072 x rounds)), at least 20: `rounds` rounds of three waves per
  *                  SIMD.  0 (default) 3; 1: rounds 2-5's one-round accumulation (86 entries at 2^20).  "pair_rounds" = 1 keeps one round for pairs
+ *   "accum_runs"   the bucket accumulation as ONE whole bucket run per thread, the non-empty buckets in order of their run length (k_accum_runs
+ *                  behind a counting sort of the buckets, csrc/msm_kernels.hpp) instead of chunks of equal length with a segmented scan behind:
+ *                  0 never, 1 (default) where the LDS sort runs with 16-bit windows on a whole MSM of 2^19 pairs or more, 2 wherever the LDS
+ *                  sort runs (tests).  The device decides per MSM: when some run is longer than the cap the chunked accumulation does the work
+ *                  (both are queued every time; the one that is not chosen returns at once).  Never with "glv"
+ *   "accum_runs_cap"  that cap: 0 (default) twice the mean run length ceil(n W / G) plus 64, which uniform scalars never reach and every skewed
+ *                  distribution passes; otherwise the cap itself, 1 .. 2^30 (tests force either side with it)
  *   "pair_sched"   1: a synchronous pair of MSMs of 2^19 pairs or more as both sorts, then the accumulations one after the other.  Measured
  *                  neutral (profiles/r06_C3_pair_sched_ab.txt); default 0
  *   "accum_stream" / "lane_priority" / "accum_chain"   round-6 experiments on WHERE the pipeline's accumulations are queued (a low-priority stream
@@ -214,6 +221,10 @@ int bpmi_msm_finish(bpmi_ctx *ctx, int slot, uint8_t out[64]);
  * [5] sorted entries per thread of the accumulation, [6] slices K, [7] pairs per slice (the other fields describe ONE slice).
  * The bucket additions of the call are K x W x (pairs per slice); bench.py prices its multiply-adds from this, not from a constant. */
 int bpmi_msm_geometry(bpmi_ctx *ctx, uint64_t n, int pipelined, uint32_t geom[8]);
+/* Tests: which accumulation the last bucket-pipeline MSM queued on lane `lane` (0 .. 2; synchronous calls use lane 0) ran.  Waits for the
+ * lane.  state[0] 1 when the accumulation by runs was planned (option "accum_runs"), [1] the device's flag: 1 = some run was longer than
+ * the cap and the chunked accumulation did the work, 0 = k_accum_runs did, [2] the runs it added (non-empty buckets; 0 with the flag up). */
+int bpmi_debug_msm_runs(bpmi_ctx *ctx, int lane, uint32_t state[3]);
 /* One MSM over up to three (points, scalars) arrays in different device buffers (BPMI_MAX_N pairs in total at most):
  * `multiexp(gs + hs + ..., a + b + ...)` without the list concatenation of src/utils/commitments.py:13. */
 int bpmi_msm_segs_dev(bpmi_ctx *ctx, uint32_t nseg, const void *const *d_pts, const void *const *d_scalars, const uint64_t *n, uint8_t out[64]);

@@ -11,6 +11,9 @@
 //                   sorts one partition per block and writes one contiguous range);
 //                   smaller n: k_digits_hist / k_scatter with global atomics
 //   k_scan_*        exclusive scans of the (coarse) histograms -> run offsets
+//   k_accum_runs    (16-bit windows from 2^19 pairs) every thread adds ONE whole bucket run, the buckets in order
+//                   of their run length (k_runs_hist / k_runs_scatter: a counting sort of the buckets); a
+//                   flag on the device hands MSMs with a long run to the next two kernels
 //   k_accum_l0      every thread adds exactly L sorted entries (perfectly balanced for
 //                   ANY digit distribution); runs that end inside a chunk go to their
 //                   bucket, the first/last run of a chunk become partial records
@@ -162,6 +165,8 @@ int bpmi_set_option(bpmi_ctx *ctx, const char *name, int64_t value) {
   if (!strcmp(name, "pair_sched")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "pair_sched must be 0 or 1"); ctx->opt_pair_sched = (int)value; return BPMI_OK; }
   if (!strcmp(name, "prover_wire_format")) { if (value != 2 && value != 3) return fail(ctx, BPMI_E_ARG, "prover_wire_format must be 2 or 3"); ctx->opt_prover_wire = (int)value; return BPMI_OK; }
   if (!strcmp(name, "prover_split")) { if (value < 0 || value > (1 << 20)) return fail(ctx, BPMI_E_ARG, "prover_split must be 0, 1 or the smallest half"); ctx->opt_prover_split = (int)value; return BPMI_OK; }
+  if (!strcmp(name, "accum_runs")) { if (value < 0 || value > 2) return fail(ctx, BPMI_E_ARG, "accum_runs must be 0, 1 or 2"); ctx->opt_accum_runs = (int)value; msm_graphs_clear(ctx); return BPMI_OK; }
+  if (!strcmp(name, "accum_runs_cap")) { if (value < 0 || value > (1 << 30)) return fail(ctx, BPMI_E_ARG, "accum_runs_cap must be 0 .. 2^30"); ctx->opt_accum_runs_cap = (int)value; msm_graphs_clear(ctx); return BPMI_OK; }
   if (!strcmp(name, "rounds")) { if (value < 0 || value > 16) return fail(ctx, BPMI_E_ARG, "rounds must be 0 .. 16"); ctx->opt_rounds = (int)value; msm_graphs_clear(ctx); return BPMI_OK; }
   if (!strcmp(name, "pair_rounds")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "pair_rounds must be 0 or 1"); ctx->opt_pair_rounds = (int)value; return BPMI_OK; }
   if (!strcmp(name, "accum_chain")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "accum_chain must be 0 or 1"); ctx->opt_accum_chain = (int)value; return BPMI_OK; }
@@ -331,6 +336,19 @@ int bpmi_msm_geometry(bpmi_ctx *ctx, uint64_t n, int pipelined, uint32_t geom[8]
   const MsmPlan pl = msm_pick_geometry(*ctx, mode, per, 0, 0);
   const MsmGeom &g = pl.g;
   geom[0] = pl.small ? 1u : (pl.mid ? 2u : 0u); geom[1] = g.c; geom[2] = g.W; geom[3] = g.top2; geom[4] = g.G; geom[5] = g.L; geom[6] = (uint32_t)K; geom[7] = (uint32_t)per;
+  return BPMI_OK;
+}
+// which accumulation the last bucket-pipeline MSM of `lane` ran (tests): waits for the lane, then reads the run table's two words
+int bpmi_debug_msm_runs(bpmi_ctx *ctx, int lane, uint32_t state[3]) {
+  if (!ctx || !state || lane < 0 || lane >= BPMI_LANES) return ctx ? fail(ctx, BPMI_E_ARG, "bad lane or null argument") : BPMI_E_ARG;
+  memset(state, 0, 3 * sizeof(uint32_t));
+  const Lane &l = ctx->lane[lane];
+  if (!l.stream || !l.run_flags) return BPMI_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipStreamSynchronize(l.stream));
+  uint32_t words[2];
+  HIPCHK(ctx, hipMemcpy(words, l.run_flags + RUN_FLAG_WORD, sizeof(words), hipMemcpyDeviceToHost));      // RUN_COUNT_WORD is the next one
+  state[0] = l.run_planned; state[1] = words[0]; state[2] = words[1];
   return BPMI_OK;
 }
 // Asynchronous pair: enqueue returns as soon as the MSM's kernels and its device->host copy are queued on

@@ -31,6 +31,8 @@ struct Lane {
   // whole GPU while the other lane's latency-bound tail (segmented scan, bucket reduction) and next sort run beside it
   hipEvent_t ev_accum = nullptr;
   hipEvent_t ev_sorted = nullptr;                // option accum_stream: this lane's sort is in
+  // the last bucket-pipeline MSM queued on this lane: was the accumulation by runs planned, and where its flag words are (bpmi_debug_msm_runs)
+  const u32 *run_flags = nullptr; u32 run_planned = 0;
 };
 struct bpmi_ctx : BpmiOptions {
   int device = 0;

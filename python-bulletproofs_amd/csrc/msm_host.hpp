@@ -142,6 +142,14 @@ static void msm_queue_sort_lds(bpmi_ctx *ctx, hipStream_t st, const Segs &segs, 
     if (!g.inblock) hipLaunchKernelGGL(k_fine_hist_heavy, dim3(nft), dim3(256), 0, st, g, w.P, w.coarse_off, w.dig, w.coarse_off + w.P, any_heavy, w.hist);
     hipLaunchKernelGGL(k_fine_sort_part, dim3(w.P), dim3(FINE_THREADS), 0, st, g, w.coarse_off, w.dig, w.hist, w.off, w.cursor, w.chunk_key, w.sidx, w.buckets);
     if (!g.inblock) hipLaunchKernelGGL(k_fine_scatter_heavy, dim3(nft), dim3(256), 0, st, g, w.P, w.coarse_off, w.dig, w.coarse_off + w.P, any_heavy, w.cursor, w.sidx);
+    if (g.runs) {
+      // the run table of k_accum_runs: the non-empty buckets by run length, in two regions the sort no longer needs; raises the flag that
+      // hands the MSM to k_accum_l0 when a run is longer than the cap
+      const u32 cap = msm_runs_cap(*ctx, g), nblk = msm_runs_blocks(g);
+      const RunTable rt = {w.run_order, w.run_counts, w.run_flags, msm_runs_bins(cap), cap};
+      hipLaunchKernelGGL(k_runs_hist, dim3(nblk), dim3(256), 0, st, g, w.off, rt);
+      hipLaunchKernelGGL(k_runs_scatter, dim3(nblk), dim3(256), 0, st, g, w.off, rt);
+    }
   }
   debug_sync(ctx, "ST_SCATTER", st);
 }
@@ -199,7 +207,11 @@ static int msm_queue_accumulate(bpmi_ctx *ctx, const MsmMode &mode, int lane, hi
   {
     StageTimer t(ctx, ST_ACCUM, st_acc);
     auto kern = glv ? (g.fuse ? k_accum_l0<true, true> : k_accum_l0<true, false>) : (g.fuse ? k_accum_l0<false, true> : k_accum_l0<false, false>);
-    hipLaunchKernelGGL(kern, dim3((w.nchunks + 255) / 256), dim3(256), 0, st_acc, segs, g, w.off, w.chunk_key, w.sidx, w.buckets, w.rec_key[0], w.rec_pt[0]);
+    // the accumulation by runs first (at most G runs; returns at once when the table kernels found a run over the cap), the chunked one behind it
+    // (returns at once otherwise): the flag on the device chooses, nothing waits for the host
+    const u32 *long_run = g.runs ? w.run_flags + RUN_FLAG_WORD : nullptr;
+    if (g.runs) hipLaunchKernelGGL(k_accum_runs, dim3((g.G + 255) / 256), dim3(256), 0, st_acc, segs, g, w.off, w.sidx, w.run_order, w.run_flags, w.buckets);
+    hipLaunchKernelGGL(kern, dim3((w.nchunks + 255) / 256), dim3(256), 0, st_acc, segs, g, w.off, w.chunk_key, w.sidx, w.buckets, w.rec_key[0], w.rec_pt[0], long_run);
   }
   if (own_acc) {
     HIPCHK(ctx, hipEventRecord(l.ev_accum, st_acc));
@@ -216,11 +228,12 @@ static void msm_queue_segscan(bpmi_ctx *ctx, hipStream_t st, const MsmGeom &g, c
     int level = 1, src = 0;
     // the ticket word of the last-block-done fusion (zeroed by the sort's memset; sort path 2 only, first level only)
     u32 *ticket = (w.P && ctx->opt_segfuse) ? w.coarse_hist + PART_MAX + 1 : nullptr;
+    const u32 *long_run = g.runs ? w.run_flags + RUN_FLAG_WORD : nullptr;       // (every level returns at once when k_accum_runs took the MSM)
     for (;;) {
       const u32 nb = (R + 255) / 256;
       if (nb > 128u || nb <= 1u) ticket = nullptr;      // (the kernel's own block count is at most this one: fewer entries than the bound)
       hipLaunchKernelGGL(k_segscan, dim3(nb), dim3(256), 0, st, g, w.off, level, w.rec_key[src], w.rec_pt[src],
-                         w.rec_key[src ^ 1], w.rec_pt[src ^ 1], w.buckets, ticket);
+                         w.rec_key[src ^ 1], w.rec_pt[src ^ 1], w.buckets, ticket, long_run);
       if (g_debug_sync) { fprintf(stderr, "[bpmi] segscan level %d nb %u R %u\n", level, nb, R); debug_sync(ctx, "segscan level", st); }
       if (nb <= 1 || ticket) break;
       R = 2 * nb;
@@ -331,6 +344,7 @@ static int msm_enqueue(bpmi_ctx *ctx, const MsmMode &mode, int lane, int slot, c
   } else if (pl.small) {
     if ((rc = msm_queue_small(ctx, st, pd, segs, g, w, E_dst))) return rc;
   } else {
+    ctx->lane[lane].run_planned = g.runs; ctx->lane[lane].run_flags = w.P ? w.run_flags : nullptr;
     if (!(phase == 2 && sort_ahead) && (rc = msm_queue_sort(ctx, st, segs, g, w))) return rc;
     if ((rc = msm_queue_accumulate(ctx, mode, lane, st, segs, g, w, pl.glv))) return rc;
     msm_queue_segscan(ctx, st, g, w);

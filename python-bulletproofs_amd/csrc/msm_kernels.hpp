@@ -614,8 +614,10 @@ __device__ __forceinline__ void xyzz_shfl_up(xyzz &r, const xyzz &a, int d) {
 // tiny launches).  Heavy buckets keep their log depth: 6 steps in the wave, then k_segscan over waves.
 template <bool GLV, bool FUSE> __global__ void __launch_bounds__(256) k_accum_l0(Segs segs, MsmGeom g, const u32 *__restrict__ off,
                                                   const u32 *__restrict__ chunk_key, const u32 *__restrict__ sidx,
-                                                  u32 *__restrict__ buckets, u32 *__restrict__ rec_key, u32 *__restrict__ rec_pt) {
+                                                  u32 *__restrict__ buckets, u32 *__restrict__ rec_key, u32 *__restrict__ rec_pt,
+                                                  const u32 *__restrict__ long_run) {
   __shared__ u32 s_head[FUSE ? 256 * LDS_STRIDE : 1];
+  if (long_run && !*long_run) return;            // the accumulation by runs is planned and took this MSM (k_accum_runs)
   const u32 E = off[g.G];
   const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   const u64 start = t * g.L;
@@ -758,7 +760,8 @@ __device__ __forceinline__ u32 records_at_level(u32 E, u32 L, u32 fuse, int leve
 // zeroed by the MSM's memset and left at nb.
 __global__ void __launch_bounds__(256) k_segscan(MsmGeom g, const u32 *__restrict__ off, int level,
                                                  const u32 *in_key, const u32 *in_pt,
-                                                 u32 *out_key, u32 *out_pt, u32 *__restrict__ buckets, u32 *ticket) {
+                                                 u32 *out_key, u32 *out_pt, u32 *__restrict__ buckets, u32 *ticket, const u32 *__restrict__ long_run) {
+  if (long_run && !*long_run) return;            // no partial records: k_accum_runs filled the buckets
   raise_priority(g.prio & PRIO_SCAN);
   __shared__ u32 s_key[256];
   __shared__ u32 s_val[256 * LDS_STRIDE];
@@ -823,6 +826,141 @@ __global__ void __launch_bounds__(256) k_segscan(MsmGeom g, const u32 *__restric
     R = 2u * nb; nb = 1; blk = 0; is_final = true;
     in_key = out_key; in_pt = out_pt;
   }
+}
+
+// ================= the accumulation by runs: one whole bucket per thread =================
+// k_accum_l0 cuts the sorted entries into chunks of equal length, so every lane of a wave meets its run boundaries on its own: at
+// n = 2^20 a lane starts a run in 1/32 + 1/29 of its iterations and SOME lane of 64 in 98.7 % of them -- the wave pays the flush, the
+// "accumulator is the identity" path and the boundary bookkeeping on practically every entry, and a general addition per thread in the
+// wave scan behind the loop.  Here thread t owns the whole run of bucket order[t], and order[] lists the non-empty buckets by run length,
+// longest first: the 64 runs of a wave are equally long (or differ by one entry where two length classes meet), all lanes start together
+// and store once.  No chunks, no partial records, no scan.  A thread adds its run alone, so this only pays while no run is much longer
+// than the others: the table kernels raise *long_run when one exceeds `cap` (msm_runs_cap), k_accum_runs then returns at once and
+// k_accum_l0 / k_segscan, which return at once otherwise, do the work.  The device decides, the host queues both every time.
+//
+// The run table, a counting sort of the buckets by run length (class = min(length, nbins - 1); ties, and the runs of the last class, in
+// bucket order to within 64 consecutive buckets):
+//   k_runs_hist     one block per RUN_SLICE buckets: LDS histogram of its buckets' classes -> the table of per-block counts; long_run
+//   k_runs_scatter  every block scans the table (longest class first, blocks in order) for the bases of its own classes, then ranks its
+//                   buckets: each wave owns a contiguous quarter of the slice and walks it in order, 64 buckets a step, so equal lengths
+//                   stay in bucket order to within a step; returns at once when long_run is up
+// No global atomic anywhere.  order[] lives in the sort's `cursor`, the counts in its `hist` (msm_layout).
+struct RunTable { u32 *order, *counts, *flags; u32 nbins, cap; };
+// the run lengths of keys k0 + lane, k0 + lane + stride, ...: every load issued before the first is used (a loop of dependent
+// load -> atomic -> store steps costs a memory latency per step with one wave per SIMD: profiles/accum_runs_table_kernel_forms.txt)
+template <u32 N> __device__ __forceinline__ void run_lengths(u32 (&len)[N], const u32 *__restrict__ off, u32 k0, u32 stride, u32 k1) {
+#pragma unroll
+  for (u32 k = 0; k < N; k++) { const u32 key = k0 + k * stride; len[k] = key < k1 ? off[key + 1] - off[key] : 0u; }
+}
+// counts[(nbins - 1 - class) * blocks + block]: in memory as in order[] -- longest class first, within a class block 0 first
+__global__ void __launch_bounds__(256) k_runs_hist(MsmGeom g, const u32 *__restrict__ off, RunTable rt) {
+  raise_priority(g.prio & PRIO_SORT);
+  __shared__ u32 bins[RUN_BINS];
+  for (u32 i = threadIdx.x; i < rt.nbins; i += 256u) bins[i] = 0;
+  __syncthreads();
+  const u32 k0 = blockIdx.x * RUN_SLICE, k1 = (k0 + RUN_SLICE < g.G) ? k0 + RUN_SLICE : g.G;
+  u32 len[RUN_SLICE / 256u];
+  run_lengths(len, off, k0 + threadIdx.x, 256u, k1);
+  bool longer = false;
+#pragma unroll
+  for (u32 k = 0; k < RUN_SLICE / 256u; k++) {
+    if (len[k]) atomicAdd(&bins[len[k] < rt.nbins ? len[k] : rt.nbins - 1u], 1u);
+    longer |= len[k] > rt.cap;
+  }
+  __syncthreads();
+  for (u32 i = threadIdx.x; i < rt.nbins; i += 256u) rt.counts[(rt.nbins - 1u - i) * gridDim.x + blockIdx.x] = bins[i];
+  if (longer) rt.flags[RUN_FLAG_WORD] = 1u;
+}
+__global__ void __launch_bounds__(256) k_runs_scatter(MsmGeom g, const u32 *__restrict__ off, RunTable rt) {
+  raise_priority(g.prio & PRIO_SORT);
+  __shared__ u32 s_base[RUN_BINS];            // position in order[] of this block's first run of every class
+  __shared__ u32 s_wave[4][RUN_BINS];         // ... of every wave's (first its count)
+  __shared__ u32 s_scan[256];
+  if (rt.flags[RUN_FLAG_WORD]) return;        // (k_runs_hist is complete: block-uniform) nobody will read order[]
+  const u32 tid = threadIdx.x, nblk = gridDim.x;
+  const u32 wave = tid >> 6, lane = tid & 63u;
+  const u32 k0 = blockIdx.x * RUN_SLICE + wave * (RUN_SLICE / 4u);
+  const u32 k1 = (k0 + RUN_SLICE / 4u < g.G) ? k0 + RUN_SLICE / 4u : g.G;
+  u32 len[RUN_SLICE / 256u];                  // this wave's quarter of the slice, 64 consecutive buckets a step
+  run_lengths(len, off, k0 + lane, 64u, k1);
+  // exclusive scan of the whole table, a contiguous piece per thread (a multiple of four words: 16-byte loads)
+  const u32 M = rt.nbins * nblk, per = ((M + 255u) / 256u + 3u) & ~3u;
+  const u32 i0 = tid * per < M ? tid * per : M, i1 = i0 + per < M ? i0 + per : M;
+  u32 sum = 0;
+  {
+    u32 i = i0;
+#pragma unroll 4
+    for (; i + 4u <= i1; i += 4u) { const uint4 v = *reinterpret_cast<const uint4 *>(rt.counts + i); sum += v.x + v.y + v.z + v.w; }
+    for (; i < i1; i++) sum += rt.counts[i];
+  }
+  s_scan[tid] = sum;
+  for (u32 i = tid; i < 4u * RUN_BINS; i += 256u) (&s_wave[0][0])[i] = 0;
+  __syncthreads();
+  for (u32 d = 1; d < 256u; d <<= 1) {
+    const u32 v = tid >= d ? s_scan[tid - d] : 0u;
+    __syncthreads();
+    s_scan[tid] += v;
+    __syncthreads();
+  }
+  // the bases of this block's own classes: the entries block + k * blocks of the table
+  {
+    u32 run = s_scan[tid] - sum, row = i0 / nblk, blk = i0 % nblk;
+    for (u32 i = i0; i < i1; i++) {
+      if (blk == blockIdx.x) s_base[rt.nbins - 1u - row] = run;
+      run += rt.counts[i];
+      if (++blk == nblk) { blk = 0; row++; }
+    }
+  }
+  if (blockIdx.x == 0 && tid == 255u) rt.flags[RUN_COUNT_WORD] = s_scan[255];
+  // the waves' own counts, then every wave's bases
+#pragma unroll
+  for (u32 k = 0; k < RUN_SLICE / 256u; k++)
+    if (len[k]) atomicAdd(&s_wave[wave][len[k] < rt.nbins ? len[k] : rt.nbins - 1u], 1u);
+  __syncthreads();
+  for (u32 cls = tid; cls < rt.nbins; cls += 256u) {
+    u32 b = s_base[cls];
+    for (u32 w = 0; w < 4u; w++) { const u32 c = s_wave[w][cls]; s_wave[w][cls] = b; b += c; }
+  }
+  __syncthreads();
+  // step after step every lane takes the next place of its class behind the wave's cursor.  (Within a step the LDS unit orders the lanes
+  // of a class; ranking them by lane in software is one round per class present, each a dependent LDS atomic: 187 us, profiles/accum_runs_table_kernel_forms.txt.
+  // The order of order[] decides which runs share a wave, never a result.)
+#pragma unroll
+  for (u32 k = 0; k < RUN_SLICE / 256u; k++)
+    if (len[k]) rt.order[atomicAdd(&s_wave[wave][len[k] < rt.nbins ? len[k] : rt.nbins - 1u], 1u)] = k0 + lane + k * 64u;
+}
+// Thread t adds the run of bucket order[t] and stores the bucket.  The loop is k_accum_l0's without its run boundaries: the point of entry
+// j + 1 and the index of entry j + 2 in flight while entry j is added.  Complete for any run: xyzz_madd_signed skips identity points, doubles
+// an equal point and returns to the identity (and goes on from it) when P meets -P.
+__global__ void __launch_bounds__(256) k_accum_runs(Segs segs, MsmGeom g, const u32 *__restrict__ off, const u32 *__restrict__ sidx,
+                                                    const u32 *__restrict__ order, const u32 *__restrict__ flags, u32 *__restrict__ buckets) {
+  if (flags[RUN_FLAG_WORD]) return;                 // a run longer than the cap: k_accum_l0's MSM
+  const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= flags[RUN_COUNT_WORD]) return;
+  const u32 b = order[t];
+  const u32 start = off[b], end = off[b + 1];
+  xyzz acc;
+  xyzz_set_inf(acc);
+  u32 e_next = sidx[start];
+  u32 e_next2 = (start + 1 < end) ? sidx[start + 1] : 0u;
+  u32 w_next[16];
+  load_entry_point<false>(w_next, segs, e_next & 0x7FFFFFFFu);
+  for (u32 j = start; j < end; j++) {
+    const u32 e = e_next;
+    affine P;
+    affine_from_words(P, w_next);
+    // (the limbs before the next loads overwrite the words: see k_accum_l0)
+    asm volatile("" : "+v"(P.x.v[0]), "+v"(P.x.v[1]), "+v"(P.x.v[2]), "+v"(P.x.v[3]), "+v"(P.x.v[4]), "+v"(P.x.v[5]), "+v"(P.x.v[6]),
+                 "+v"(P.x.v[7]), "+v"(P.x.v[8]), "+v"(P.y.v[0]), "+v"(P.y.v[1]), "+v"(P.y.v[2]), "+v"(P.y.v[3]), "+v"(P.y.v[4]),
+                 "+v"(P.y.v[5]), "+v"(P.y.v[6]), "+v"(P.y.v[7]), "+v"(P.y.v[8]));
+    if (j + 1 < end) {
+      e_next = e_next2;
+      if (j + 2 < end) e_next2 = sidx[j + 2];
+      load_entry_point<false>(w_next, segs, e_next & 0x7FFFFFFFu);
+    }
+    xyzz_madd_signed(acc, P, (e >> 31) != 0);
+  }
+  xyzz_store_g(buckets + (u64)b * XYZZ_WORDS, acc);
 }
 
 // block-wide tree sum of one XYZZ value per thread (256 threads); result valid in thread 0

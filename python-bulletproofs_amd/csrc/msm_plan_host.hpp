@@ -23,6 +23,8 @@ struct MsmGeom {
                // is 0, so the last window's digit never exceeds its 2^c and there is NO carry window and no short one (a window of a few
                // bits is one partition of n entries for the sort and a handful of giant buckets for the accumulation).  c = 15: 16 + 1
                // windows; c = 13: 10 + 9; c = 12: 17 + 4.  Keys of window w start at (w + max(0, w - (W - Wb))) B;  G = (W + Wb) B.  0: uniform
+  u32 runs;    // 1: the accumulation by runs is planned -- k_accum_runs adds one whole bucket per thread, buckets in order of their length, unless the
+               // device finds a run longer than the cap (msm_runs_cap); then k_accum_l0 and k_segscan, queued behind it every time, do the work
   u32 inblock; // 1 (n <= 2^17): k_fine_sort_part sorts a partition of ANY size itself (a heavy one without the LDS staging buffer);
                // the two tile kernels for heavy partitions are not launched
 };
@@ -45,7 +47,10 @@ struct MsmMode {
   bool free_run = false;   // ... chained, but NOT ordered (option accum_chain = 0: the lanes run free)
   bool beside = false;     // a synchronous pair of large MSMs: another MSM's kernels run beside this accumulation (msm_run_pair)
 };
-struct MsmPlan { MsmGeom g; bool mid, small, glv; };      // mid: the one-block-per-window kernel, small: the one-launch kernel, neither: the bucket pipeline
+struct MsmPlan { MsmGeom g; bool mid, small, glv; };
+// sort path 2 (the two-level LDS partition sort) takes a bucket-pipeline MSM when the bucket key has more than 8 bits and the packed entry
+// (8-bit lo | sign | 23-bit index) fits; path 1 (global atomics) otherwise.  The one place that says so: msm_layout's w.P and MsmGeom.runs read it.
+static inline bool msm_lds_sort(u32 c, u32 n) { return c >= 10u && n <= (1u << 23); }      // mid: the one-block-per-window kernel, small: the one-launch kernel, neither: the bucket pipeline
 
 // Window bits from the tools/tune_msm.py sweeps on MI355X (profiles/r01_tune_msm_after_sort_and_reduce_rewrites.txt).
 // Besides the usual bucket-count trade-off, windows whose TOP window holds only a few
@@ -171,8 +176,25 @@ static inline MsmPlan msm_pick_geometry(const BpmiOptions &o, const MsmMode &mod
   g.nv = (g.B <= 256u) ? 1u : 4u;                  // partial sums per window handed to the tail
   g.prio = o.opt_prio == 1 ? 15u : (o.opt_prio > 1 ? (u32)(o.opt_prio & 15) : 0u);      // (1 = every stage; 16 + mask = those stages)
   g.fuse = o.opt_fuse ? 1u : 0u;
+  // The accumulation by runs (k_accum_runs): the LDS sort's pipeline only (it reuses two of its regions, msm_layout), never GLV.  By default where
+  // the buckets are long and even enough for a wave of 64 equally long runs to beat 64 chunks with their boundaries: c = 16 from 2^19 pairs
+  // (32 entries per bucket at 2^20), whole MSMs only.  Option "accum_runs" = 2: wherever the LDS sort runs.
+  const bool lds_sort = !mid && !small && msm_lds_sort(g.c, g.n);                 // (msm_layout's w.P != 0 for the bucket pipeline)
+  g.runs = 0;
+  if (lds_sort && !glv && g.G >= 2048u && (o.opt_accum_runs == 2 || (o.opt_accum_runs == 1 && g.c == 16u && !wcount && n >= (1u << 19)))) g.runs = 1;
   return pl;
 }
+// The longest run the accumulation by runs takes: twice the mean run length ceil(n W / G) plus 64.  A thread adds its run alone, so the kernel
+// lasts as long as the longest one: uniform digits (Poisson around the mean) never reach the cap, and every skewed input -- equal scalars, bit
+// vectors, a few distinct values: one bucket with a large part of a window's n entries -- passes it by orders of magnitude.
+static inline u32 msm_runs_cap(const BpmiOptions &o, const MsmGeom &g) {
+  if (o.opt_accum_runs_cap > 0) return (u32)o.opt_accum_runs_cap;
+  const uint64_t mean = ((uint64_t)g.n * g.W + g.G - 1) / g.G;
+  return (u32)std::min<uint64_t>(2 * mean + 64, 1ull << 30);
+}
+// length classes of the run table for that cap (class = min(length, classes - 1)) and its blocks
+static inline u32 msm_runs_bins(u32 cap) { return std::min<u32>(cap, RUN_BINS - 1u) + 1u; }
+static inline u32 msm_runs_blocks(const MsmGeom &g) { return (g.G + RUN_SLICE - 1u) / RUN_SLICE; }
 
 struct MsmWs {
   u32 *glv_sub, *glv_bx;      // GLV: 2n x 16 B magnitudes, n x 32 B beta x
@@ -183,6 +205,7 @@ struct MsmWs {
   u32 P;          // partitions of sort path 2 (0 = path 1)
   u32 *rec_key[2], *rec_pt[2];
   u32 *D, *E, *F, *out;
+  u32 *run_order, *run_counts, *run_flags;     // the run table (MsmGeom.runs): in `cursor`, `hist` and the spare words of `coarse_hist`
   size_t total;
   u32 nscan_blocks, rec0_max, nchunks;
 };
@@ -199,9 +222,7 @@ static inline void msm_layout(const MsmGeom &g, MsmWs &w, char *base, bool glv =
   w.rec0_max = 2u * (g.fuse ? (w.nchunks + 63u) / 64u : w.nchunks);
   // second-level segscan buffer sizing relies on this: every level after the first has at most rec1_max records (R shrinks monotonically)
   const u32 rec1_max = 2 * ((w.rec0_max + 255) / 256);
-  // sort path 2 (LDS partition sort) when the bucket key has more than 8 bits and the
-  // packed entry (8-bit lo | sign | 23-bit index) fits; path 1 (global atomics) otherwise
-  w.P = (g.c >= 10 && g.n <= (1u << 23)) ? (g.G >> 8) : 0;
+  w.P = msm_lds_sort(g.c, g.n) ? (g.G >> 8) : 0;            // partitions of sort path 2; 0 = path 1
   w.hist = take(4ull * g.G);                 // path 1 only
   w.off = take(4ull * (g.G + 1));
   w.cursor = take(4ull * g.G);               // path 1 only
@@ -223,6 +244,9 @@ static inline void msm_layout(const MsmGeom &g, MsmWs &w, char *base, bool glv =
   w.E = take(4ull * XYZZ_WORDS * g.W * 4);
   w.F = take(4ull * XYZZ_WORDS * g.W * 64);       // k_digit_final_spread: 16 sums per (window, array)
   w.out = take(64);
+  // the run table is built when the sort is over, in two of its regions that are dead by then: order[] (at most G bucket keys) in `cursor`,
+  // the per-block counts (msm_runs_blocks x at most RUN_BINS words <= G from 2048 buckets) in `hist`
+  w.run_order = w.cursor; w.run_counts = w.hist; w.run_flags = w.coarse_hist;
   w.total = o;
 }
 

@@ -56,6 +56,12 @@ static inline Segs segs_init() {
 #define COARSE_HIST_WORDS (PART_MAX + 192)     // the partition counts, the any_heavy flag (+0), the tickets of the last-block fusions (+1, +2) and of
                                                // k_digit_final_spread (+8 .. +8 + 4 W), padded to whole 256-byte lines
 #define FINE_TILE 4096           // entries per tile of the sort's heavy-partition kernels
+// the run table of the accumulation by runs (k_runs_hist / k_runs_scatter / k_accum_runs, msm_kernels.hpp): its flag and count live in the spare
+// words of coarse_hist behind the tickets, zeroed by the sort's memset
+#define RUN_FLAG_WORD (PART_MAX + 3)     // long_run: some run is longer than the cap -> the chunked accumulation and the segmented scan do the work
+#define RUN_COUNT_WORD (PART_MAX + 4)    // nruns: non-empty buckets
+#define RUN_BINS 1024u           // length classes of the counting sort; runs of RUN_BINS - 1 entries or more share the last one (in bucket order)
+#define RUN_SLICE 4096u          // buckets per block of the two table kernels (128 blocks at 2^19 buckets, 16 buckets per thread); a multiple of 256
 #define SCAN_PER_THREAD 16
 #define SCAN_TILE (256 * SCAN_PER_THREAD)
 #define SMALL_C 8                // window bits of k_msm_small
@@ -139,6 +145,8 @@ struct BpmiOptions {
   int opt_accum_chain = 1;              // experiment: 0 = the asynchronous pipeline's accumulations are NOT ordered after each other (the lanes run free)
   int opt_accum_stream = 0;             // experiment: the chained pipeline's accumulations on one low-priority stream of their own (msm_host.hpp)
   int opt_lane_prio = 0;                // experiment: queue priority of lanes 1 / 2 created AFTER the option is set (0 default, -1 high, 1 low)
+  int opt_accum_runs = 1;               // the accumulation as one length-sorted bucket run per thread (k_accum_runs): 0 never, 1 where it pays (msm_pick_geometry), 2 wherever the LDS sort runs (tests)
+  int opt_accum_runs_cap = 0;           // ... the run length beyond which an MSM falls back to the chunked accumulation (0 = the rule, msm_runs_cap; tests force either side)
   // bulk hash to the curve (h2c_host.hpp)
   int opt_h2c_plain = 0;                // 1: one message per lane with a loop per lane (k_h2c_plain) at EVERY size, not only where a lane has one message anyway
   int opt_h2c_per_lane = 0;             // 1 .. 64: k_h2c_queue with that many messages per lane of a wave's span (0 = by the call's size, h2c_span)

@@ -177,6 +177,13 @@ class Engine:
         return {"kernel": ("pipeline", "small", "mid")[g[0]] if n else None, "window_bits": g[1], "windows": g[2], "wide_windows": g[3],
                 "buckets": g[4], "chunk": g[5], "slices": g[6], "pairs_per_slice": g[7]}
 
+    def msm_runs_state(self, lane=0):
+        """Which accumulation the last bucket-pipeline MSM of `lane` ran (bpmi_debug_msm_runs; tests): a dict with `planned` (the accumulation
+        by runs was planned), `long_run` (the device found a run over the cap: the chunked accumulation did the work) and `runs`."""
+        st = (ctypes.c_uint32 * 3)()
+        self._ck(self.lib.bpmi_debug_msm_runs(self.ctx, lane, st))
+        return {"planned": bool(st[0]), "long_run": bool(st[1]), "runs": st[2]}
+
     def ec_mul_batch_bytes(self, pts, scalars, n):
         out = ctypes.create_string_buffer(64 * n)
         self._ck(self.lib.bpmi_ec_mul_batch(self.ctx, pts, scalars, n, out))

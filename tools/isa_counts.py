@@ -7,6 +7,15 @@ separately).
 
     python tools/isa_counts.py                       # prints the JSON object
     python tools/isa_counts.py --write               # also writes profiles/r04_isa_counts.json and the ISA excerpt
+    python tools/isa_counts.py --loops [--write]     # the per-entry loops of k_accum_l0<false, true> and k_accum_runs, block by block
+                                                     # (--write: profiles/accum_loop_isa_ledger.json)
+
+--loops tallies the whole loop, not only the addition: the loop is the first outermost backward branch whose span holds a whole
+mixed addition (>= 900 v_mad_u64_u32); its basic blocks are listed in program order with their instruction, multiply-add and
+memory-instruction counts and with how they are entered (a block behind s_cbranch_execz costs nothing only when NO lane of the wave
+needs it).  The common path is every block of the loop but the doubling and the rare blocks outlined behind it: what a wave issues
+per entry when some lane needs each of the other paths.  What lies behind the loop is the epilogue (k_accum_l0: the wave scan with
+its general additions; k_accum_runs: one store).
 
 bench.py reads profiles/r04_isa_counts.json for `alu_roofline.frac_vs_raw_mad` (multiply-adds actually issued per
 second against the chip's raw v_mad_u64_u32 rate)."""
@@ -23,12 +32,90 @@ SRC = os.path.join(REPO, "python-bulletproofs_amd", "csrc", "bpmi.hip")
 INSTR = re.compile(r"^\s+((?:v_|s_|ds_|global_|buffer_|flat_|scratch_)\w+)")
 
 
+LABEL = re.compile(r"^(\.LBB\d+_\d+):")
+BRANCH = re.compile(r"^\s+(s_cbranch_\w+|s_branch)\s+(\.LBB\d+_\d+)")
+
+
+def loop_tally(kernel):
+    """The per-entry loop of an accumulation kernel and what follows it, as basic blocks in program order."""
+    blocks, cur, entered = [], None, "falls through"
+    for ln in kernel.splitlines():
+        m = LABEL.match(ln)
+        if m or cur is None:
+            cur = {"label": m.group(1) if m else "(entry)", "instructions": 0, "v_mad_u64_u32": 0, "memory_instructions": 0, "entered": entered, "branches": []}
+            blocks.append(cur)
+            entered = "falls through"
+            if m:
+                continue
+        mm = INSTR.match(ln)
+        if not mm:
+            continue
+        cur["instructions"] += 1
+        cur["v_mad_u64_u32"] += 1 if mm.group(1) == "v_mad_u64_u32" else 0
+        cur["memory_instructions"] += 1 if mm.group(1).startswith(("global_", "ds_", "buffer_", "flat_", "scratch_")) else 0
+        br = BRANCH.match(ln)
+        if br:
+            cur["branches"].append(br.group(1) + " " + br.group(2))
+            entered = "by branch only" if br.group(1) == "s_branch" else "falls through, skipped when " + br.group(1)
+    index = {b_["label"]: k for k, b_ in enumerate(blocks)}
+    targets = lambda b_: [index[t.split()[1]] for t in b_["branches"] if t.split()[1] in index]
+    # loops: [head, last block that branches back to head]; the per-entry loop is the first one that is in no other and holds an addition
+    spans = {}
+    for k, b_ in enumerate(blocks):
+        for t in targets(b_):
+            if t <= k:
+                spans[t] = max(spans.get(t, k), k)
+    mads = lambda lo, hi: sum(b_["v_mad_u64_u32"] for b_ in blocks[lo:hi + 1])
+    outer = [(lo, hi) for lo, hi in sorted(spans.items()) if mads(lo, hi) >= 900 and not any(l2 <= lo and hi <= h2 and (l2, h2) != (lo, hi) for l2, h2 in spans.items())]
+    lo, hi = outer[0]
+    # blocks the compiler laid out behind the loop that jump back into it (rare paths) are the loop's
+    end = hi
+    for k in range(hi + 1, len(blocks)):
+        into = [t for t in targets(blocks[k]) if lo <= t <= hi]
+        if not into:
+            break
+        if blocks[k]["branches"][-1].startswith("s_branch"):
+            end = k
+    body, tail = blocks[lo:end + 1], blocks[end + 1:]
+    count = lambda bs, key: sum(b_[key] for b_ in bs)
+    # the rare paths of the mixed addition: the doubling (acc == addend; the only other block with hundreds of multiply-adds besides the two of the
+    # main path, which are the first two in program order) and the blocks outlined behind the loop
+    heavy = [b_ for b_ in body if b_["v_mad_u64_u32"] >= 200]
+    rare = [b_["label"] for b_ in heavy[2:]] + [b_["label"] for b_ in blocks[hi + 1:end + 1]]
+    common = [b_ for b_ in body if b_["label"] not in rare]
+    fmt = lambda bs: [{k: v for k, v in b_.items()} for b_ in bs if b_["instructions"]]
+    return {"loop_head": blocks[lo]["label"],
+            "loop_instructions_every_block": count(body, "instructions"), "loop_v_mad_u64_u32_every_block": count(body, "v_mad_u64_u32"),
+            "loop_common_path_instructions": count(common, "instructions"), "loop_common_path_v_mad_u64_u32": count(common, "v_mad_u64_u32"),
+            "loop_common_path_memory_instructions": count(common, "memory_instructions"),
+            "mixed_addition_main_path_instructions": count(heavy[:2], "instructions"), "mixed_addition_main_path_v_mad_u64_u32": count(heavy[:2], "v_mad_u64_u32"),
+            "rare_blocks_not_in_common_path": rare, "loop_blocks": fmt(body),
+            "after_loop_instructions": count(tail, "instructions"), "after_loop_v_mad_u64_u32": count(tail, "v_mad_u64_u32"),
+            "after_loop_blocks_of_20_or_more": fmt([b_ for b_ in tail if b_["instructions"] >= 20]),
+            "vgprs": int(re.search(r"; NumVgprs: (\d+)", kernel).group(1)), "scratch_bytes": int(re.search(r"; ScratchSize: (\d+)", kernel).group(1)),
+            "lds_bytes": int(re.search(r"; LDSByteSize: (\d+)", kernel).group(1)), "occupancy_waves_per_simd": int(re.search(r"; Occupancy: (\d+)", kernel).group(1))}
+
+
+def loops(text):
+    out = {"how": "hipcc -O3 --offload-arch=gfx950 -S; the first outermost loop (backward branch) that holds >= 900 v_mad_u64_u32 is the per-entry loop, with the "
+                  "blocks laid out behind it that jump back into it; blocks in program order; 'skipped when s_cbranch_execz': executed by the whole wave as soon as ONE "
+                  "lane needs it; common path = every block but the doubling and the outlined ones (tools/isa_counts.py --loops)"}
+    for name, pat in (("k_accum_l0<false,true>", r"^_Z10k_accum_l0ILb0ELb1E.*?; Occupancy: \d+"), ("k_accum_runs", r"^_Z12k_accum_runs.*?; Occupancy: \d+")):
+        out[name] = loop_tally(re.search(pat, text, re.S | re.M).group(0))
+    print(json.dumps(out, indent=1))
+    if "--write" in sys.argv:
+        with open(os.path.join(REPO, "profiles", "accum_loop_isa_ledger.json"), "w") as f:
+            json.dump(out, f, indent=1)
+
+
 def main():
     with tempfile.TemporaryDirectory() as tmp:
         asm = os.path.join(tmp, "bpmi.s")
         subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-DBPMI_ISA_PROBE", "-S", "--cuda-device-only",
                                "-Wno-unused-command-line-argument", "-o", asm, SRC], stderr=subprocess.DEVNULL)
         text = open(asm).read()
+    if "--loops" in sys.argv:
+        return loops(text)
     m = re.search(r"^_Z10k_accum_l0ILb0E.*?; Occupancy: \d+", text, re.S | re.M)
     kernel = m.group(0)
     probe = re.search(r"^_Z16k_isa_probe_madd.*?; Occupancy: \d+", text, re.S | re.M).group(0)
