@@ -184,7 +184,27 @@ int bpmi_sync(bpmi_ctx *ctx);
  *                  256 MB; a larger batch runs as consecutive launches over row ranges
  *   "fold_wnaf"    the ladder of that 16-way fold: 2 (default) width-4 non-adjacent forms of the coefficients' GLV halves over affine
  *                  tables of 3P, 5P, 7P and of beta x (k_ec_multifold_w4g; 792 B of workspace per generator, kept by the ctx after the first fold),
- *                  1 of the whole coefficients (k_ec_multifold_w4), 0 the plain NAF ladder without tables (k_ec_multifold) */
+ *                  1 of the whole coefficients (k_ec_multifold_w4), 0 the plain NAF ladder without tables (k_ec_multifold)
+ *   "h2c_plain" / "h2c_per_lane"   the launch shapes of the bulk hash to the curve: see bpmi_ec_hash_batch below
+ *   "direct_result" 1 (default): the last kernel of an MSM writes its result into the slot's page-locked host buffer; 0: workspace + copy
+ *   "graphs"       1: an MSM's launch sequence is replayed as a HIP graph when the same call comes again; default 0
+ *   "hist_threads" / "hist_blocks"   launch shape of the sort's k_coarse_hist: threads per block 256, 512 or 1024, blocks up to 8 192 (0 = default)
+ *   "quad_final"   1 (default): the bucket reduction's finish with four-lane point additions (k_digit_final_quad); 0: one lane per point
+ *   "tail_thread"  1 (default): the host tail of the second MSM of a synchronous pair runs on the ctx's helper thread beside the first
+ *                  one's; 0: one after the other
+ *   "pair_chain"   1: a synchronous pair of large MSMs with their accumulate kernels chained as in the asynchronous pipeline (A/B; round 3
+ *                  measured it slower); default 0
+ *   "small_pair"   1 (default): a pair of small MSMs (bpmi_msm2, the L / R of an inner-product round) as one launch sequence on one
+ *                  stream; 0: on two lanes
+ *   "mid_min"      a pair of MSMs runs as one launch of k_msm_mid from this many pairs in the larger one (0 = default 1 536, -1 = never)
+ *   "mid_single_min"  a single MSM runs on k_msm_mid from this many pairs (0 = default 2 560, -1 = never)
+ *   "ipa_small_step" 1: short inner-product vectors run fold, coefficient tables and the next round's dots and scalars in one launch
+ *                  (k_ipa_small_step).  Measured slower (profiles/r04_C3_small_step_ab.txt); default 0, kept with its tests
+ *   "fold_shared"  1 (default): the product fold of a state without per-generator scales uses shared GLV halves, two terms per thread;
+ *                  0: per-lane products
+ *   "prover_split" bpmi_rp_prove_batch: 1 = a batch of 4 096 proofs or more as two halves on two lanes, N > 1 = from 2 N proofs.  Measured
+ *                  slower (profiles/r06_batch_prover_table_bits.txt); default 0
+ * What each option accepts, its message and what a set does beyond storing the value: one row each in csrc/options_host.hpp */
 int bpmi_set_option(bpmi_ctx *ctx, const char *name, int64_t value);
 
 /* ---- device buffers (so callers need no other GPU runtime) ------------------- */

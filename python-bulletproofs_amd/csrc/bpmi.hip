@@ -26,7 +26,8 @@
 //   tail            O(256) sequential doublings: window combine + to-affine
 //                   (host thread on 4x64-bit limbs, host_tail.hpp, or the one-lane device
 //                   kernel k_tail; same Horner chain)
-// This file: the C-ABI entry points.  The inner-product prover (the IPA state object, deferred generator folding) is ipa_host.hpp,
+// This file: the C-ABI entry points.  What every one of them relies on: the options (one table, options_host.hpp) and the on-curve check of
+// caller-supplied points (one object, point_check_host.hpp).  The inner-product prover (the IPA state object, deferred generator folding) is ipa_host.hpp,
 // included below where its section stood; the batch verifier of inner-product proofs is ipa_batch_host.hpp, behind it.
 // Kernels and host orchestration live in the *.hpp files included below (one translation unit).
 #include <hip/hip_runtime.h>
@@ -50,6 +51,7 @@ using namespace bpmi;
 #define BPMI_VERSION 100
 
 #include "shared_defs.hpp"
+#include "options_host.hpp"
 #include "msm_plan_host.hpp"
 #include "rp_batch_plan_host.hpp"
 #include "rp_prove_plan_host.hpp"
@@ -61,6 +63,7 @@ using namespace bpmi;
 #include "msm_kernels.hpp"
 #include "fold_ops_host.hpp"
 #include "point_kernels.hpp"
+#include "point_check_host.hpp"
 #include "svector_batch.hpp"
 #include "scalar_kernels.hpp"
 #include "host_tail.hpp"
@@ -153,75 +156,14 @@ int bpmi_sync(bpmi_ctx *ctx) {
   return BPMI_OK;
 }
 
+// the options and what each accepts: the table of options_host.hpp
 int bpmi_set_option(bpmi_ctx *ctx, const char *name, int64_t value) {
   if (!ctx || !name) return BPMI_E_ARG;
-  if (!strcmp(name, "window_bits")) { if (value != 0 && (value < 2 || value > 16)) return fail(ctx, BPMI_E_ARG, "window_bits must be 0 or 2..16"); ctx->opt_c = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "accum_stream")) { if (value < 0 || value > 2) return fail(ctx, BPMI_E_ARG, "accum_stream must be 0, 1 or 2"); ctx->opt_accum_stream = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "lane_priority")) { if (value < -1 || value > 1) return fail(ctx, BPMI_E_ARG, "lane_priority must be -1, 0 or 1"); ctx->opt_lane_prio = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "h2c_plain")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "h2c_plain must be 0 or 1"); ctx->opt_h2c_plain = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "msm_batch_route")) { if (value < 0 || value > 3) return fail(ctx, BPMI_E_ARG, "msm_batch_route must be 0 .. 3"); ctx->opt_msm_batch_route = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "msm_batch_vecs")) { if (value < 0 || value > (1 << 20)) return fail(ctx, BPMI_E_ARG, "msm_batch_vecs must be 0 .. 2^20"); ctx->opt_msm_batch_vecs = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "h2c_per_lane")) { if (value < 0 || value > 64) return fail(ctx, BPMI_E_ARG, "h2c_per_lane must be 0 .. 64"); ctx->opt_h2c_per_lane = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "pair_sched")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "pair_sched must be 0 or 1"); ctx->opt_pair_sched = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "prover_wire_format")) { if (value != 2 && value != 3) return fail(ctx, BPMI_E_ARG, "prover_wire_format must be 2 or 3"); ctx->opt_prover_wire = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "prover_split")) { if (value < 0 || value > (1 << 20)) return fail(ctx, BPMI_E_ARG, "prover_split must be 0, 1 or the smallest half"); ctx->opt_prover_split = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "accum_runs")) { if (value < 0 || value > 2) return fail(ctx, BPMI_E_ARG, "accum_runs must be 0, 1 or 2"); ctx->opt_accum_runs = (int)value; msm_graphs_clear(ctx); return BPMI_OK; }
-  if (!strcmp(name, "accum_runs_cap")) { if (value < 0 || value > (1 << 30)) return fail(ctx, BPMI_E_ARG, "accum_runs_cap must be 0 .. 2^30"); ctx->opt_accum_runs_cap = (int)value; msm_graphs_clear(ctx); return BPMI_OK; }
-  if (!strcmp(name, "rounds")) { if (value < 0 || value > 16) return fail(ctx, BPMI_E_ARG, "rounds must be 0 .. 16"); ctx->opt_rounds = (int)value; msm_graphs_clear(ctx); return BPMI_OK; }
-  if (!strcmp(name, "pair_rounds")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "pair_rounds must be 0 or 1"); ctx->opt_pair_rounds = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "accum_chain")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "accum_chain must be 0 or 1"); ctx->opt_accum_chain = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "slice_n")) { if (value < -1 || value > (1 << 23) || (value > 0 && value < (1 << 16))) return fail(ctx, BPMI_E_ARG, "slice_n must be -1, 0 or 2^16 .. 2^23"); ctx->opt_slice_n = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "slice_min")) { if (value < 0 || value > (1 << 23)) return fail(ctx, BPMI_E_ARG, "slice_min must be 0 .. 2^23"); ctx->opt_slice_min = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "mid_parts")) { if (value < 0 || value > 4) return fail(ctx, BPMI_E_ARG, "mid_parts must be 0 .. 4"); ctx->opt_mid_parts = (int)value; msm_graphs_clear(ctx); return BPMI_OK; }
-  if (!strcmp(name, "mixed_windows")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "mixed_windows must be 0 or 1"); ctx->opt_mixed = (int)value; msm_graphs_clear(ctx); return BPMI_OK; }
-  if (!strcmp(name, "top_window_unsigned")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "top_window_unsigned must be 0 or 1"); ctx->opt_top2 = (int)value; msm_graphs_clear(ctx); return BPMI_OK; }
-  if (!strcmp(name, "prover_job_lanes")) { if (value != 0 && value != 16 && value != 64) return fail(ctx, BPMI_E_ARG, "prover_job_lanes must be 0, 16 or 64"); ctx->opt_prover_job_lanes = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "prover_table_bits")) { if (value != 0 && (value < 4 || value > 16)) return fail(ctx, BPMI_E_ARG, "prover_table_bits must be 0 or 4..16"); ctx->opt_prover_tw = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "ipa_fixed_generators")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "ipa_fixed_generators must be 0 or 1"); ctx->opt_ipa_fixed = (int)value; ctx->fold_key_g = ctx->fold_key_h = nullptr; return BPMI_OK; }
-  if (!strcmp(name, "validate_points")) { if (value < 0 || value > 2) return fail(ctx, BPMI_E_ARG, "validate_points must be 0, 1 or 2"); ctx->opt_validate = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "hist_scan_fused")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "hist_scan_fused must be 0 or 1"); ctx->opt_histscan = (int)value; msm_graphs_clear(ctx); return BPMI_OK; }
-  if (!strcmp(name, "reduce_fit")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "reduce_fit must be 0 or 1"); ctx->opt_reduce_fit = (int)value; msm_graphs_clear(ctx); return BPMI_OK; }
-  if (!strcmp(name, "final_spread")) { if (value < 0 || value > 3) return fail(ctx, BPMI_E_ARG, "final_spread must be 0 .. 3"); ctx->opt_final_spread = (int)value; msm_graphs_clear(ctx); return BPMI_OK; }
-  if (!strcmp(name, "sort_inblock")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "sort_inblock must be 0 or 1"); ctx->opt_inblock = (int)value; msm_graphs_clear(ctx); return BPMI_OK; }
-  if (!strcmp(name, "segscan_fused")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "segscan_fused must be 0 or 1"); ctx->opt_segfuse = (int)value; msm_graphs_clear(ctx); return BPMI_OK; }
-  if (!strcmp(name, "priority")) { if (value < 0 || value > 31 || (value > 1 && value < 16)) return fail(ctx, BPMI_E_ARG, "priority must be 0, 1 or 16 + a mask of stages"); ctx->opt_prio = (int)value; msm_graphs_clear(ctx); return BPMI_OK; }
-  if (!strcmp(name, "hist_threads")) { if (value != 0 && value != 256 && value != 512 && value != 1024) return fail(ctx, BPMI_E_ARG, "hist_threads must be 0, 256, 512 or 1024"); ctx->opt_hist_threads = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "hist_blocks")) { if (value < 0 || value > 8192) return fail(ctx, BPMI_E_ARG, "hist_blocks must be in [0, 8192]"); ctx->opt_hist_blocks = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "direct_result")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "direct_result must be 0 or 1"); ctx->opt_direct = (int)value; msm_graphs_clear(ctx); return BPMI_OK; }
-  if (!strcmp(name, "graphs")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "graphs must be 0 or 1"); ctx->opt_graph = (int)value; if (!value) msm_graphs_clear(ctx); return BPMI_OK; }
-  if (!strcmp(name, "tail_thread")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "tail_thread must be 0 or 1"); ctx->opt_tail_thread = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "pair_chain")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "pair_chain must be 0 or 1"); ctx->opt_pair_chain = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "mid_min")) { if (value < -1 || value > MID_NMAX) return fail(ctx, BPMI_E_ARG, "mid_min must be -1 .. 8448"); ctx->opt_mid_min = (int)value; msm_graphs_clear(ctx); return BPMI_OK; }
-  if (!strcmp(name, "mid_single_min")) { if (value < -1 || value > MID_NMAX) return fail(ctx, BPMI_E_ARG, "mid_single_min must be -1 .. 8448"); ctx->opt_mid_single = (int)value; msm_graphs_clear(ctx); return BPMI_OK; }
-  if (!strcmp(name, "small_pair")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "small_pair must be 0 or 1"); ctx->opt_pair1 = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "fused_scan")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "fused_scan must be 0 or 1"); ctx->opt_fuse = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "quad_final")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "quad_final must be 0 or 1"); ctx->opt_quad = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "spin_wait")) { if (value < 0 || value > 10000000) return fail(ctx, BPMI_E_ARG, "spin_wait must be in [0, 10^7]"); ctx->opt_spin_wait = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "mul_batch_glv")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "mul_batch_glv must be 0 or 1"); ctx->opt_mulb = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "tail")) { if (value < 0 || value > 2) return fail(ctx, BPMI_E_ARG, "tail must be 0, 1 or 2"); ctx->opt_tail = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "small_n")) { if (value < -1 || value > (1 << 16)) return fail(ctx, BPMI_E_ARG, "small_n must be -1 .. 65536"); ctx->opt_small = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "split")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "split must be 0 or 1"); ctx->opt_split = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "async_lanes")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "async_lanes must be 0 or 1"); ctx->opt_async_lanes = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "rp_only_role")) { if (value < -1 || value > 3) return fail(ctx, BPMI_E_ARG, "rp_only_role must be in [-1, 3]"); ctx->opt_rp_only_role = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "glv")) { if (value < -1 || value > 1) return fail(ctx, BPMI_E_ARG, "glv must be -1, 0 or 1"); ctx->opt_glv = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "rp_priority")) { if (value < 0 || value > 2) return fail(ctx, BPMI_E_ARG, "rp_priority must be 0, 1 or 2"); ctx->opt_rp_prio = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "rp_slices")) { if (value < 0 || value > 4) return fail(ctx, BPMI_E_ARG, "rp_slices must be 0 .. 4"); ctx->opt_rp_slices = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "rp_overlap")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "rp_overlap must be 0 or 1"); ctx->opt_rp_overlap = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "rp_rows")) { if (value < 0) return fail(ctx, BPMI_E_ARG, "rp_rows must be >= 0"); ctx->opt_rp_rows = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "rp_lanes")) {
-    if (value != 0 && (value < 1 || value > 64 || (value & (value - 1)))) return fail(ctx, BPMI_E_ARG, "rp_lanes must be 0 or a power of two <= 64");
-    ctx->opt_rp_lanes = (int)value;
-    return BPMI_OK;
-  }
-  if (!strcmp(name, "pair_phases")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "pair_phases must be 0 or 1"); ctx->opt_pair_phases = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "fold_wnaf")) { if (value < 0 || value > 2) return fail(ctx, BPMI_E_ARG, "fold_wnaf must be 0, 1 or 2"); ctx->opt_fold_wnaf = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "reduce_epl")) { if (value < 0 || value > 64) return fail(ctx, BPMI_E_ARG, "reduce_epl must be 0..64"); ctx->opt_epl = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "chunk")) { if (value < 0 || value > 4096) return fail(ctx, BPMI_E_ARG, "chunk must be 0..4096"); ctx->opt_chunk = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "ipa_small_step")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "ipa_small_step must be 0 or 1"); ctx->opt_ipa_step = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "fold_shared")) { if (value < 0 || value > 1) return fail(ctx, BPMI_E_ARG, "fold_shared must be 0 or 1"); ctx->opt_fold_shared = (int)value; return BPMI_OK; }
-  if (!strcmp(name, "ipa_small_m")) { if (value < 0 || (value & (value - 1))) return fail(ctx, BPMI_E_ARG, "ipa_small_m must be 0 (default), 1 (never) or a power of two"); ctx->opt_ipa_small = value; return BPMI_OK; }
-  if (!strcmp(name, "ipa_big_m")) { if (value < 0 || (value & (value - 1))) return fail(ctx, BPMI_E_ARG, "ipa_big_m must be 0 or a power of two"); ctx->opt_ipa_big = value; return BPMI_OK; }
-  return fail(ctx, BPMI_E_ARG, std::string("unknown option ") + name);
+  const OptionSet r = option_set(*ctx, name, value);
+  if (r.rc) return fail(ctx, r.rc, r.msg);
+  if (r.fx == OPT_FX_GRAPHS || (r.fx == OPT_FX_GRAPHS_IF_ZERO && !value)) msm_graphs_clear(ctx);
+  if (r.fx == OPT_FX_FOLD_KEYS) ctx->fold_key_g = ctx->fold_key_h = nullptr;
+  return BPMI_OK;
 }
 
 int bpmi_malloc(bpmi_ctx *ctx, size_t bytes, void **dptr) {
@@ -252,47 +194,6 @@ int bpmi_download(bpmi_ctx *ctx, void *host, const void *dptr, size_t bytes) {
   return BPMI_OK;
 }
 
-// ---- on-curve check of caller-supplied points (option "validate_points") --------------------------------------------------
-// The reference can never hand an off-curve point to multiexp: fastecdsa's Point constructor rejects it (reached from
-// /root/reference/src/utils/utils.py:119-131), and ec.py keeps that check for Python callers.  A C caller hands in raw bytes, so
-// the entry points that take HOST pointers check them here (level 1, the default; level 2: the synchronous _dev entry points as
-// well; 0: never): the identity (64 zero bytes) or x, y < p with y^2 = x^3 + 7.  Large arrays: k_ec_validate queued behind the
-// upload, its verdict (the smallest bad index) copied to a page-locked word that is read after the call's own synchronisation --
-// no extra wait; the call then fails with BPMI_E_ARG and writes NO result.  A few points: checked on the host.
-#define VALIDATE_HOST_MAX 64u
-static int validate_begin(bpmi_ctx *ctx, hipStream_t st) {
-  if (!ctx->vflag) {
-    HIPCHK(ctx, hipHostMalloc((void **)&ctx->vflag, 64, hipHostMallocDefault));
-    HIPCHK(ctx, hipMalloc((void **)&ctx->vflag_dev, 256));
-  }
-  *ctx->vflag = 0xFFFFFFFFu;
-  HIPCHK(ctx, hipMemsetAsync(ctx->vflag_dev, 0xFF, 4, st));
-  return BPMI_OK;
-}
-// array `which` (0 .. 3) of the call: d_pts[0 .. n) on the device
-static void validate_enqueue(bpmi_ctx *ctx, const void *d_pts, uint64_t n, u32 which, hipStream_t st) {
-  if (!n) return;
-  hipLaunchKernelGGL(k_ec_validate, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, (const u32 *)d_pts, (u32)n, which << 28, ctx->vflag_dev);
-}
-static int validate_fetch(bpmi_ctx *ctx, hipStream_t st) {
-  HIPCHK(ctx, hipMemcpyAsync(ctx->vflag, ctx->vflag_dev, 4, hipMemcpyDeviceToHost, st));
-  return BPMI_OK;
-}
-// after the stream has been synchronised: names[which] = what the bad array is called in the message
-static int validate_end(bpmi_ctx *ctx, const char *fn, const char *const *names) {
-  const u32 v = *ctx->vflag;
-  if (v == 0xFFFFFFFFu) return BPMI_OK;
-  return fail(ctx, BPMI_E_ARG, std::string(fn) + ": " + names[v >> 28] + "[" + std::to_string(v & 0x0FFFFFFFu) + "] is not a point of the curve");
-}
-static int validate_host(bpmi_ctx *ctx, const uint8_t *pts, uint64_t n, const char *fn, const char *name) {
-  for (uint64_t i = 0; i < n; i++) {
-    u32 w[16];
-    memcpy(w, pts + 64 * i, 64);
-    if (!wire_point_valid(w)) return fail(ctx, BPMI_E_ARG, std::string(fn) + ": " + name + "[" + std::to_string(i) + "] is not a point of the curve");
-  }
-  return BPMI_OK;
-}
-
 // ---- MSM ------------------------------------------------------------------------------
 static int msm_dev_impl(bpmi_ctx *ctx, const void *d_pts, const void *d_scalars, uint64_t n, uint8_t out[64]);
 int bpmi_msm_dev(bpmi_ctx *ctx, const void *d_pts, const void *d_scalars, uint64_t n, uint8_t out[64]) {
@@ -300,15 +201,13 @@ int bpmi_msm_dev(bpmi_ctx *ctx, const void *d_pts, const void *d_scalars, uint64
   if (n > BPMI_MAX_N) return fail(ctx, BPMI_E_ARG, "n exceeds BPMI_MAX_N");
   if (ctx->opt_validate < 2 || n == 0) return msm_dev_impl(ctx, d_pts, d_scalars, n, out);
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  int rc = validate_begin(ctx, ctx->stream);
-  if (rc) return rc;
-  validate_enqueue(ctx, d_pts, n, 0, ctx->stream);
-  rc = validate_fetch(ctx, ctx->stream);
+  PointCheck pc(ctx, "bpmi_msm_dev", ctx->stream, true);
+  pc.queue(d_pts, n, "d_pts");
+  int rc = pc.fetch();
   if (rc) return rc;
   rc = msm_dev_impl(ctx, d_pts, d_scalars, n, out);
   if (rc) return rc;
-  static const char *const names[] = {"d_pts"};
-  rc = validate_end(ctx, "bpmi_msm_dev", names);
+  rc = pc.verdict();
   if (rc) memset(out, 0, 64);
   return rc;
 }
@@ -414,18 +313,13 @@ int bpmi_msm(bpmi_ctx *ctx, const uint8_t *pts, const uint8_t *scalars, uint64_t
   char *ds = dp + align_up(64 * n, 256);
   HIPCHK(ctx, h2d(ctx, dp, pts, 64 * n, ctx->stream));
   HIPCHK(ctx, h2d(ctx, ds, scalars, 32 * n, ctx->stream));
-  const bool check = ctx->opt_validate >= 1;
-  if (check) {
-    rc = validate_begin(ctx, ctx->stream);
-    if (rc) return rc;
-    validate_enqueue(ctx, dp, n, 0, ctx->stream);
-    rc = validate_fetch(ctx, ctx->stream);
-    if (rc) return rc;
-  }
+  PointCheck pc(ctx, "bpmi_msm", ctx->stream, ctx->opt_validate >= 1);
+  pc.queue(dp, n, "pts");
+  rc = pc.fetch();
+  if (rc) return rc;
   rc = msm_dev_impl(ctx, dp, ds, n, out);
-  if (rc || !check) return rc;
-  static const char *const names[] = {"pts"};
-  rc = validate_end(ctx, "bpmi_msm", names);
+  if (rc) return rc;
+  rc = pc.verdict();
   if (rc) memset(out, 0, 64);
   return rc;
 }
@@ -446,19 +340,14 @@ int bpmi_msm2(bpmi_ctx *ctx, const uint8_t *pts0, const uint8_t *sc0, uint64_t n
   Segs a = segs_init(), b = segs_init();
   a.pts[0] = (const u32 *)d; a.sc[0] = (const u32 *)(d + o_s0); a.n[0] = (u32)n0; a.total = (u32)n0;
   b.pts[0] = (const u32 *)(d + o_p1); b.sc[0] = (const u32 *)(d + o_s1); b.n[0] = (u32)n1; b.total = (u32)n1;
-  const bool check = ctx->opt_validate >= 1 && (n0 || n1);
-  if (check) {
-    rc = validate_begin(ctx, ctx->stream);
-    if (rc) return rc;
-    validate_enqueue(ctx, d, n0, 0, ctx->stream);
-    validate_enqueue(ctx, d + o_p1, n1, 1, ctx->stream);
-    rc = validate_fetch(ctx, ctx->stream);
-    if (rc) return rc;
-  }
+  PointCheck pc(ctx, "bpmi_msm2", ctx->stream, ctx->opt_validate >= 1);
+  pc.queue(d, n0, "pts0");
+  pc.queue(d + o_p1, n1, "pts1");
+  rc = pc.fetch();
+  if (rc) return rc;
   rc = msm_run_pair(ctx, a, out0, b, out1);
-  if (rc || !check) return rc;
-  static const char *const names[] = {"pts0", "pts1"};
-  rc = validate_end(ctx, "bpmi_msm2", names);
+  if (rc) return rc;
+  rc = pc.verdict();
   if (rc) { memset(out0, 0, 64); memset(out1, 0, 64); }
   return rc;
 }
@@ -505,20 +394,15 @@ int bpmi_ec_mul_batch(bpmi_ctx *ctx, const uint8_t *pts, const uint8_t *scalars,
   char *dp = (char *)ctx->stage_in, *ds = dp + align_up(64 * n, 256), *dout = ds + align_up(32 * n, 256);
   HIPCHK(ctx, h2d(ctx, dp, pts, 64 * n, ctx->stream));
   HIPCHK(ctx, h2d(ctx, ds, scalars, 32 * n, ctx->stream));
-  const bool check = ctx->opt_validate >= 1;
-  if (check) {
-    rc = validate_begin(ctx, ctx->stream);
-    if (rc) return rc;
-    validate_enqueue(ctx, dp, n, 0, ctx->stream);
-    rc = validate_fetch(ctx, ctx->stream);
-    if (rc) return rc;
-  }
+  PointCheck pc(ctx, "bpmi_ec_mul_batch", ctx->stream, ctx->opt_validate >= 1);
+  pc.queue(dp, n, "pts");
+  rc = pc.fetch();
+  if (rc) return rc;
   rc = bpmi_ec_mul_batch_dev(ctx, dp, ds, n, dout);
   if (rc) return rc;
-  if (check) {                                   // the verdict before anything is written to the caller's buffer
+  if (pc.on) {                                   // the verdict before anything is written to the caller's buffer
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    static const char *const names[] = {"pts"};
-    rc = validate_end(ctx, "bpmi_ec_mul_batch", names);
+    rc = pc.verdict();
     if (rc) return rc;
   }
   HIPCHK(ctx, hipMemcpyAsync(out, dout, 64 * n, hipMemcpyDeviceToHost, ctx->stream));
@@ -565,21 +449,16 @@ int bpmi_ec_lincomb2_batch(bpmi_ctx *ctx, const uint8_t *p1, const uint8_t *p2, 
   char *d1 = (char *)ctx->stage_in, *d2 = d1 + align_up(64 * n, 256), *dout = d2 + align_up(64 * n, 256);
   HIPCHK(ctx, h2d(ctx, d1, p1, 64 * n, ctx->stream));
   HIPCHK(ctx, h2d(ctx, d2, p2, 64 * n, ctx->stream));
-  const bool check = ctx->opt_validate >= 1;
-  if (check) {
-    rc = validate_begin(ctx, ctx->stream);
-    if (rc) return rc;
-    validate_enqueue(ctx, d1, n, 0, ctx->stream);
-    validate_enqueue(ctx, d2, n, 1, ctx->stream);
-    rc = validate_fetch(ctx, ctx->stream);
-    if (rc) return rc;
-  }
+  PointCheck pc(ctx, "bpmi_ec_lincomb2_batch", ctx->stream, ctx->opt_validate >= 1);
+  pc.queue(d1, n, "p1");
+  pc.queue(d2, n, "p2");
+  rc = pc.fetch();
+  if (rc) return rc;
   rc = bpmi_ec_lincomb2_batch_dev(ctx, d1, d2, k1, k2, n, dout);
   if (rc) return rc;
-  if (check) {
+  if (pc.on) {
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    static const char *const names[] = {"p1", "p2"};
-    rc = validate_end(ctx, "bpmi_ec_lincomb2_batch", names);
+    rc = pc.verdict();
     if (rc) return rc;
   }
   HIPCHK(ctx, hipMemcpyAsync(out, dout, 64 * n, hipMemcpyDeviceToHost, ctx->stream));
@@ -596,15 +475,11 @@ int bpmi_ec_sum(bpmi_ctx *ctx, const uint8_t *pts, uint64_t n, uint8_t out[64]) 
   char *dp = (char *)ctx->stage_in, *dout = dp + align_up(64 * n, 256);
   HIPCHK(ctx, h2d(ctx, dp, pts, 64 * n, ctx->stream));
   // (the per-GPU partial results a sharded caller folds here are the library's own outputs; a few points: checked on the host)
-  const bool check = ctx->opt_validate >= 1;
-  if (check && n <= VALIDATE_HOST_MAX) { rc = validate_host(ctx, pts, n, "bpmi_ec_sum", "pts"); if (rc) { memset(out, 0, 64); return rc; } }
-  else if (check) {
-    rc = validate_begin(ctx, ctx->stream);
-    if (rc) return rc;
-    validate_enqueue(ctx, dp, n, 0, ctx->stream);
-    rc = validate_fetch(ctx, ctx->stream);
-    if (rc) return rc;
-  }
+  PointCheck pc(ctx, "bpmi_ec_sum", ctx->stream, ctx->opt_validate >= 1);
+  if (n <= VALIDATE_HOST_MAX) { rc = pc.host(pts, n, "pts"); if (rc) { memset(out, 0, 64); return rc; } }
+  else pc.queue(dp, n, "pts");
+  rc = pc.fetch();
+  if (rc) return rc;
   {
     StageTimer t(ctx, ST_MISC);
     hipLaunchKernelGGL(k_ec_sum, dim3(1), dim3(256), 0, ctx->stream, (const u32 *)dp, (u32)n, (u32 *)dout);
@@ -612,11 +487,8 @@ int bpmi_ec_sum(bpmi_ctx *ctx, const uint8_t *pts, uint64_t n, uint8_t out[64]) 
   uint8_t tmp[64];
   HIPCHK(ctx, hipMemcpyAsync(tmp, dout, 64, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  if (check && n > VALIDATE_HOST_MAX) {
-    static const char *const names[] = {"pts"};
-    rc = validate_end(ctx, "bpmi_ec_sum", names);
-    if (rc) { memset(out, 0, 64); return rc; }             // as bpmi_msm: a refused call leaves the identity's bytes, never a stale value
-  }
+  rc = pc.verdict();
+  if (rc) { memset(out, 0, 64); return rc; }               // as bpmi_msm: a refused call leaves the identity's bytes, never a stale value
   memcpy(out, tmp, 64);
   return BPMI_OK;
 }
@@ -885,10 +757,10 @@ int bpmi_ipa_verify_dev(bpmi_ctx *ctx, const void *d_g, const void *d_h, const v
   SvecLayout L;
   int rc = svector_layout(ctx, n, k, o_es + 32 * n_extra, L);
   if (rc) return rc;
-  const bool check_host = ctx->opt_validate >= 1 && n_extra && n_extra <= VALIDATE_HOST_MAX;
-  const bool check_dev = ctx->opt_validate >= 2 || (ctx->opt_validate >= 1 && n_extra > VALIDATE_HOST_MAX);
-  if (check_host) { rc = validate_host(ctx, extra_pts, n_extra, "bpmi_ipa_verify_dev", "extra_pts"); if (rc) return rc; }
-  if (check_dev) { rc = validate_begin(ctx, ctx->stream); if (rc) return rc; }
+  // a few extra points are checked on the host, many by the kernel; the generators from level 2
+  PointCheck pc(ctx, "bpmi_ipa_verify_dev", ctx->stream, ctx->opt_validate >= 1);
+  const bool extra_on_host = n_extra <= VALIDATE_HOST_MAX;
+  if (extra_on_host) { rc = pc.host(extra_pts, n_extra, "extra_pts"); if (rc) return rc; }
   rc = svector_launch(ctx, L, d_hscale, n, xs, xinvs, a, b);
   if (rc) return rc;
   u32 *d_sa = L.sa, *d_sb = L.sb;
@@ -902,16 +774,13 @@ int bpmi_ipa_verify_dev(bpmi_ctx *ctx, const void *d_g, const void *d_h, const v
   s.pts[1] = (const u32 *)d_h; s.sc[1] = d_sb; s.n[1] = (u32)n;
   s.pts[2] = (const u32 *)d_ex; s.sc[2] = (const u32 *)(d_ex + o_es); s.n[2] = (u32)n_extra;
   s.total = (u32)(2 * n + n_extra);
-  if (check_dev) {
-    if (ctx->opt_validate >= 2) { validate_enqueue(ctx, d_g, n, 0, ctx->stream); validate_enqueue(ctx, d_h, n, 1, ctx->stream); }
-    if (n_extra > VALIDATE_HOST_MAX) validate_enqueue(ctx, d_ex, n_extra, 2, ctx->stream);
-    rc = validate_fetch(ctx, ctx->stream);
-    if (rc) return rc;
-  }
+  if (ctx->opt_validate >= 2) { pc.queue(d_g, n, "d_g"); pc.queue(d_h, n, "d_h"); }
+  if (!extra_on_host) pc.queue(d_ex, n_extra, "extra_pts");
+  rc = pc.fetch();
+  if (rc) return rc;
   rc = msm_run(ctx, s, out);
-  if (rc || !check_dev) return rc;
-  static const char *const names[] = {"d_g", "d_h", "extra_pts"};
-  rc = validate_end(ctx, "bpmi_ipa_verify_dev", names);
+  if (rc) return rc;
+  rc = pc.verdict();
   if (rc) memset(out, 0xFF, 64);                // (never the identity, which a verifier reads as "valid")
   return rc;
 }

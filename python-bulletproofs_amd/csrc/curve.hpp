@@ -283,7 +283,7 @@ BPMI_HD void xyzz_load(xyzz &a, const u32 *src) {
 // window value = sum_v 2^(off[v]) E[v], off ascending, off[0] = 0
 // Is the 64-byte wire point (x, y: 8 little-endian words each) the identity (all zero) or a point of y^2 = x^3 + 7 with x, y < p?
 // What fastecdsa's Point constructor checks for the reference (reached from /root/reference/src/utils/utils.py:119-131); the C-ABI
-// checks it for callers that hand in raw bytes (bpmi.hip validate_*).  Host and device.
+// checks it for callers that hand in raw bytes (PointCheck, point_check_host.hpp).  Host and device.
 BPMI_HD bool wire_point_valid(const u32 w[16]) {
   u32 any = 0;
 #pragma unroll

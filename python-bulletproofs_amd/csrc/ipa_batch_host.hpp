@@ -74,13 +74,12 @@ int bpmi_ipa_verify_batch_dev(bpmi_ctx *ctx, const void *d_g, const void *d_h, c
   HIPCHK(ctx, hipSetDevice(ctx->device));
   // points are checked as in bpmi_ipa_verify_dev: a few extra points on the host, many (and, at level 2, the generators) by a kernel
   // whose verdict is read after the MSM's own synchronisation; a refused call leaves 0xFF.. in `out`, never the identity
-  const bool check_host = ctx->opt_validate >= 1 && n_extra && n_extra <= VALIDATE_HOST_MAX;
-  const bool check_dev = ctx->opt_validate >= 2 || (ctx->opt_validate >= 1 && n_extra > VALIDATE_HOST_MAX);
+  PointCheck pc(ctx, fn, ctx->stream, ctx->opt_validate >= 1);
+  const bool extra_on_host = n_extra <= VALIDATE_HOST_MAX;
   int rc;
-  if (check_host) { rc = validate_host(ctx, extra_pts, n_extra, fn, "extra_pts"); if (rc) { memset(out, 0xFF, 64); return rc; } }
+  if (extra_on_host) { rc = pc.host(extra_pts, n_extra, "extra_pts"); if (rc) { memset(out, 0xFF, 64); return rc; } }
   rc = ensure_stage_in(ctx, pl.total_bytes + 512);
   if (rc) return rc;
-  if (check_dev) { rc = validate_begin(ctx, ctx->stream); if (rc) return rc; }
   rc = ipab_svector_sum(ctx, pl, d_hscale, xs, xinvs, a, b, weights);
   if (rc) return rc;
   char *base = (char *)ctx->stage_in;
@@ -93,16 +92,13 @@ int bpmi_ipa_verify_batch_dev(bpmi_ctx *ctx, const void *d_g, const void *d_h, c
   s.pts[1] = (const u32 *)d_h; s.sc[1] = (const u32 *)(base + pl.o_sb); s.n[1] = (u32)n;
   s.pts[2] = (const u32 *)(base + pl.o_expt); s.sc[2] = (const u32 *)(base + pl.o_exsc); s.n[2] = (u32)n_extra;
   s.total = (u32)pl.msm_pairs;
-  if (check_dev) {
-    if (ctx->opt_validate >= 2) { validate_enqueue(ctx, d_g, n, 0, ctx->stream); validate_enqueue(ctx, d_h, n, 1, ctx->stream); }
-    if (n_extra > VALIDATE_HOST_MAX) validate_enqueue(ctx, base + pl.o_expt, n_extra, 2, ctx->stream);
-    rc = validate_fetch(ctx, ctx->stream);
-    if (rc) return rc;
-  }
+  if (ctx->opt_validate >= 2) { pc.queue(d_g, n, "d_g"); pc.queue(d_h, n, "d_h"); }
+  if (!extra_on_host) pc.queue(base + pl.o_expt, n_extra, "extra_pts");
+  rc = pc.fetch();
+  if (rc) return rc;
   rc = msm_run(ctx, s, out);                    // one MSM over the three segments, sliced as any large MSM is (msm_host.hpp)
-  if (rc || !check_dev) return rc;
-  static const char *const names[] = {"d_g", "d_h", "extra_pts"};
-  rc = validate_end(ctx, fn, names);
+  if (rc) return rc;
+  rc = pc.verdict();
   if (rc) memset(out, 0xFF, 64);
   return rc;
 }

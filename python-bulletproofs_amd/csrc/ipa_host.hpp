@@ -102,12 +102,9 @@ static int ipa_create_from(bpmi_ctx *ctx, bool on_device, const void *g, const v
   int rc = ipa_alloc(ctx, n, &st);
   if (rc) return rc;
   hipStream_t s = ctx->stream;
-  const bool check = !on_device && ctx->opt_validate >= 1;
-  if (check) {
-    rc = validate_host(ctx, u, 1, "bpmi_ipa_create", "u");
-    if (rc == BPMI_OK) rc = validate_begin(ctx, s);
-    if (rc) { ipa_free(st); return rc; }
-  }
+  PointCheck pc(ctx, "bpmi_ipa_create", s, !on_device && ctx->opt_validate >= 1);
+  rc = pc.host(u, 1, "u");
+  if (rc) { ipa_free(st); return rc; }
   auto copy = [&](void *dst, const void *src, size_t bytes) {
     return on_device ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s) : h2d(ctx, dst, src, bytes, s);
   };
@@ -116,18 +113,15 @@ static int ipa_create_from(bpmi_ctx *ctx, bool on_device, const void *g, const v
   if (e == hipSuccess) e = copy(st->a, a, 32 * n);
   if (e == hipSuccess) e = copy(st->b, b, 32 * n);
   if (e == hipSuccess) e = h2d(ctx, st->u, u, 64, s);
-  if (e == hipSuccess && check) {
-    validate_enqueue(ctx, st->g, n, 0, s);
-    validate_enqueue(ctx, st->h, n, 1, s);
-    e = hipMemcpyAsync(ctx->vflag, ctx->vflag_dev, 4, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) {
+    pc.queue(st->g, n, "g");
+    pc.queue(st->h, n, "h");
+    rc = pc.fetch();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e != hipSuccess) { ipa_free(st); return fail(ctx, BPMI_E_HIP, std::string("ipa_create copy: ") + hipGetErrorString(e)); }
-  if (check) {
-    static const char *const names[] = {"g", "h"};
-    rc = validate_end(ctx, "bpmi_ipa_create", names);
-    if (rc) { ipa_free(st); return rc; }
-  }
+  if (rc == BPMI_OK) rc = pc.verdict();
+  if (rc) { ipa_free(st); return rc; }
   if (on_device) { st->src_g = g; st->src_h = h; }
   *out = st;
   return BPMI_OK;

@@ -42,10 +42,11 @@ static int ipa_batch_prover_create_impl(bpmi_ctx *ctx, uint32_t n, const uint8_t
   if (h_scale) for (u32 j = 0; j < n; j++)
     if (!rp_scalar_reduced(h_scale + 32 * (size_t)j)) return fail(ctx, BPMI_E_ARG, "bpmi_ipa_batch_prover_create: h_scale[" + std::to_string(j) + "] is not below the group order");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (ctx->opt_validate >= 1) {
-    int vrc = validate_host(ctx, u, 1, "bpmi_ipa_batch_prover_create", "u");
-    if (!vrc) vrc = validate_host(ctx, g, n, "bpmi_ipa_batch_prover_create", "g");
-    if (!vrc) vrc = validate_host(ctx, h, n, "bpmi_ipa_batch_prover_create", "h");
+  {
+    const PointCheck pc(ctx, "bpmi_ipa_batch_prover_create", ctx->stream, ctx->opt_validate >= 1);
+    int vrc = pc.host(u, 1, "u");
+    if (!vrc) vrc = pc.host(g, n, "g");
+    if (!vrc) vrc = pc.host(h, n, "h");
     if (vrc) return vrc;
   }
   bpmi_ipa_batch_prover *pv = new bpmi_ipa_batch_prover();
@@ -167,12 +168,8 @@ static int ipa_prove_batch_impl(bpmi_ipa_batch_prover *pv, int protocol, uint64_
   if (Pst) memcpy(hp + o_Pin, Pst, 64ull * P);
   hipStream_t st = ctx->stream;
   HIPCHK(ctx, hipMemcpyAsync(d, hp, in_bytes, hipMemcpyHostToDevice, st));
-  const bool check = protocol == 1 && ctx->opt_validate >= 1;
-  if (check) {
-    int rc = validate_begin(ctx, st);
-    if (rc) return rc;
-    validate_enqueue(ctx, d + o_Pin, P, 0, st);
-  }
+  PointCheck pc(ctx, "bpmi_ipa_prove_batch", st, protocol == 1 && ctx->opt_validate >= 1);
+  pc.queue(d + o_Pin, P, "P");
   ipp::Batch B;
   memset(&B, 0, sizeof(B));
   B.P = P; B.n = n; B.k = k; B.proto = (u32)protocol;
@@ -219,17 +216,13 @@ static int ipa_prove_batch_impl(bpmi_ipa_batch_prover *pv, int protocol, uint64_
   }
   (void)hipEventRecord(ev[2], st);
   hipError_t e = hipGetLastError();
-  if (e == hipSuccess && check) { int rc = validate_fetch(ctx, st); if (rc) return rc; }
+  if (e == hipSuccess) { int rc = pc.fetch(); if (rc) return rc; }
   // the proofs leave through the prover's page-locked buffer, in one copy
   if (e == hipSuccess) e = hipMemcpyAsync(hp, d + o_out, out_bytes, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipEventRecord(ev[3], st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) return fail(ctx, BPMI_E_HIP, std::string("bpmi_ipa_prove_batch: ") + hipGetErrorString(e));
-  if (check) {
-    static const char *const names[] = {"P"};
-    int rc = validate_end(ctx, "bpmi_ipa_prove_batch", names);
-    if (rc) return rc;                                   // (no output is written)
-  }
+  if (int rc = pc.verdict()) return rc;                  // (no output is written)
   const char *ho = hp - o_out;                           // ho + o_x: array x in the staging buffer
   memcpy(ab, ho + o_ab, 64ull * P);
   if (k) { memcpy(xs, ho + o_xs, 32ull * P * k); memcpy(LR, ho + o_lr, 128ull * P * k); }

@@ -107,19 +107,14 @@ int bpmi_msm_batch_dev(bpmi_ctx *ctx, uint32_t nseg, const void *const *d_pts, c
   if (rc || n_vec == 0) return rc;
   if ((rc = msmb_check_state(ctx))) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  const bool check = ctx->opt_validate >= 2 && pl.total > 0;
-  const char *names[3] = {"d_pts[0]", "d_pts[1]", "d_pts[2]"};
-  if (check) {
-    static const char *const all[3] = {"d_pts[0]", "d_pts[1]", "d_pts[2]"};
-    rc = validate_begin(ctx, ctx->stream);
-    if (rc) return rc;
-    for (u32 k = 0; k < A.nsegs; k++) { validate_enqueue(ctx, A.segs.pts[k], A.segs.n[k], k, ctx->stream); names[k] = all[A.which[k]]; }
-    rc = validate_fetch(ctx, ctx->stream);
-    if (rc) return rc;
-  }
+  static const char *const names[3] = {"d_pts[0]", "d_pts[1]", "d_pts[2]"};      // by the caller's segment number, A.which
+  PointCheck pc(ctx, "bpmi_msm_batch_dev", ctx->stream, ctx->opt_validate >= 2);
+  for (u32 k = 0; k < A.nsegs; k++) pc.queue(A.segs.pts[k], A.segs.n[k], names[A.which[k]]);
+  rc = pc.fetch();
+  if (rc) return rc;
   rc = msmb_run_host(ctx, pl, A, out);
-  if (rc || !check) return rc;
-  rc = validate_end(ctx, "bpmi_msm_batch_dev", names);
+  if (rc) return rc;
+  rc = pc.verdict();
   if (rc) memset(out, 0, 64 * (size_t)n_vec);
   return rc;
 }
@@ -165,22 +160,17 @@ int bpmi_msm_batch(bpmi_ctx *ctx, const uint8_t *pts, uint64_t n, const uint8_t 
   char *dp = (char *)ctx->stage_in, *ds = dp + o_sc;
   HIPCHK(ctx, h2d(ctx, dp, pts, 64 * n, ctx->stream));
   HIPCHK(ctx, h2d(ctx, ds, scalars, sc_bytes, ctx->stream));
-  const bool check = ctx->opt_validate >= 1;
-  if (check) {
-    rc = validate_begin(ctx, ctx->stream);
-    if (rc) return rc;
-    validate_enqueue(ctx, dp, n, 0, ctx->stream);
-    rc = validate_fetch(ctx, ctx->stream);
-    if (rc) return rc;
-  }
+  PointCheck pc(ctx, "bpmi_msm_batch", ctx->stream, ctx->opt_validate >= 1);
+  pc.queue(dp, n, "pts");
+  rc = pc.fetch();
+  if (rc) return rc;
   const void *const P[1] = {dp}, *const S[1] = {ds};
   MsmBatchPlan pl;
   MsmBatchArgs A;
   rc = msmb_check(ctx, 1, P, ns, S, n_vec, out, true, pl, A);
   if (rc == BPMI_OK) rc = msmb_run_host(ctx, pl, A, out);
-  if (rc || !check) return rc;
-  static const char *const names[] = {"pts"};
-  rc = validate_end(ctx, "bpmi_msm_batch", names);
+  if (rc) return rc;
+  rc = pc.verdict();
   if (rc) memset(out, 0, 64 * (size_t)n_vec);
   return rc;
 }

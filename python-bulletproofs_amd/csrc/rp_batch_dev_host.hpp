@@ -321,20 +321,12 @@ static int rp_batch_dims(bpmi_ctx *ctx, uint32_t n_gens, uint32_t m, uint64_t n_
   return BPMI_OK;
 }
 // commitments: the first nv points / scalars of the per-proof arrays; their on-curve check (and the generators', from validate = 2)
-// is queued behind the upload.  `check`: the caller ends with validate_end
-static int rp_upload_commitments(bpmi_ctx *ctx, const uint8_t *v_points, void *d_points, const void *d_gens, const RpBatchDims &d, bool &check) {
-  const uint64_t nv = d.nv;
-  HIPCHK(ctx, h2d(ctx, d_points, v_points, 64 * nv, ctx->stream));
-  check = ctx->opt_validate >= 1;
-  if (check) {
-    int vrc = validate_begin(ctx, ctx->stream);
-    if (vrc) return vrc;
-    validate_enqueue(ctx, d_points, nv, 0, ctx->stream);
-    if (ctx->opt_validate >= 2) validate_enqueue(ctx, d_gens, d.nshared, 1, ctx->stream);
-    vrc = validate_fetch(ctx, ctx->stream);
-    if (vrc) return vrc;
-  }
-  return BPMI_OK;
+// is queued behind the upload, in the caller's PointCheck: the caller reads pc.verdict() after its last wait
+static int rp_upload_commitments(bpmi_ctx *ctx, const uint8_t *v_points, void *d_points, const void *d_gens, const RpBatchDims &d, PointCheck &pc) {
+  HIPCHK(ctx, h2d(ctx, d_points, v_points, 64 * d.nv, ctx->stream));
+  pc.queue(d_points, d.nv, "v_points");
+  if (ctx->opt_validate >= 2) pc.queue(d_gens, d.nshared, "d_gens");
+  return pc.fetch();
 }
 // the index k_rp_roles and the decoding left at p (~0: none)
 static int64_t rp_first_bad_at(const void *p) {
@@ -389,8 +381,8 @@ int bpmi_rp_batch_verify_dev(bpmi_ctx *ctx, uint32_t n_gens, uint32_t values_per
   if (rc) return rc;
   const uint64_t nv = d.nv, npts = d.npts;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  bool check;
-  rc = rp_upload_commitments(ctx, v_points, d_points, d_gens, d, check);
+  PointCheck pc(ctx, "bpmi_rp_batch_verify_dev", ctx->stream, ctx->opt_validate >= 1);
+  rc = rp_upload_commitments(ctx, v_points, d_points, d_gens, d, pc);
   if (rc) return rc;
   RpQueued Q;
   rc = rp_prepare_enqueue(ctx, n_gens, values_per_proof, n_proofs, blobs, blobs_len, blob_off, weights, seed, d_scalars, (char *)d_scalars + 32 * nv,
@@ -411,11 +403,8 @@ int bpmi_rp_batch_verify_dev(bpmi_ctx *ctx, uint32_t n_gens, uint32_t values_per
   rc = msm_run(ctx, s, out);                      // waits for the MSM (ctx stream: behind everything queued above)
   rc = rp_wait_lanes(ctx, rc);
   if (rc) return rc;
-  if (check) {
-    static const char *const names[] = {"v_points", "d_gens"};
-    rc = validate_end(ctx, "bpmi_rp_batch_verify_dev", names);
-    if (rc) { memset(out, 0xFF, 64); return rc; }                  // (never the identity)
-  }
+  rc = pc.verdict();
+  if (rc) { memset(out, 0xFF, 64); return rc; }                    // (never the identity)
   *first_bad = rp_first_bad_at(ctx->pin);
   rc = rp_finish_verdict(ctx, blobs, blobs_len, blob_off, first_bad);
   if (rc) memset(out, 0xFF, 64);
@@ -495,8 +484,8 @@ int bpmi_rp_batch_group_values_dev(bpmi_ctx *ctx, uint32_t n_gens, uint32_t valu
   const size_t vals_bytes = 64 * (size_t)G.ngroups;
   rc = ensure_pin(ctx, std::max<size_t>(32 * (size_t)(5 + 2 * n_gens) + 64, vals_bytes + n_proofs + 64));
   if (rc) return rc;
-  bool check;
-  rc = rp_upload_commitments(ctx, v_points, d_points, d_gens, d, check);
+  PointCheck pc(ctx, "bpmi_rp_batch_group_values_dev", ctx->stream, ctx->opt_validate >= 1);
+  rc = rp_upload_commitments(ctx, v_points, d_points, d_gens, d, pc);
   if (rc) return rc;
   RpQueued Q;
   rc = rp_prepare_enqueue(ctx, n_gens, m, n_proofs, blobs, blobs_len, blob_off, weights, seed, d_scalars, (char *)d_scalars + 32 * nv, (char *)d_points + 64 * nv, Q, &G);
@@ -518,11 +507,8 @@ int bpmi_rp_batch_group_values_dev(bpmi_ctx *ctx, uint32_t n_gens, uint32_t valu
     rc = rp_run_group_msms(ctx, G, d, m, n_proofs, d_gens, d_points, d_scalars, values);
     if (rc) { memset(values, 0xFF, vals_bytes); return rc; }
   }
-  if (check) {
-    static const char *const names[] = {"v_points", "d_gens"};
-    rc = validate_end(ctx, "bpmi_rp_batch_group_values_dev", names);
-    if (rc) { memset(values, 0xFF, vals_bytes); return rc; }
-  }
+  rc = pc.verdict();
+  if (rc) { memset(values, 0xFF, vals_bytes); return rc; }
   int64_t first_flagged = -1;
   for (uint64_t i = 0; i < n_proofs && first_flagged < 0; i++) if (status[i]) first_flagged = (int64_t)i;
   rc = rp_mixed_formats(ctx, blobs, blobs_len, blob_off, first_flagged);

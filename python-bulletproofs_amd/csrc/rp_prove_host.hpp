@@ -129,12 +129,13 @@ static int rp_prover_create_impl(bpmi_ctx *ctx, uint32_t vbits, uint32_t m, cons
   if (plan.err) return fail(ctx, plan.err, plan.msg);
   const uint32_t nbits = plan.n;                         // elements of a proof's vectors
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (ctx->opt_validate >= 1) {
-    int vrc = validate_host(ctx, g, 1, "bpmi_rp_prover_create", "g");
-    if (!vrc) vrc = validate_host(ctx, h, 1, "bpmi_rp_prover_create", "h");
-    if (!vrc) vrc = validate_host(ctx, u, 1, "bpmi_rp_prover_create", "u");
-    if (!vrc) vrc = validate_host(ctx, gs, nbits, "bpmi_rp_prover_create", "gs");
-    if (!vrc) vrc = validate_host(ctx, hs, nbits, "bpmi_rp_prover_create", "hs");
+  {
+    const PointCheck pc(ctx, "bpmi_rp_prover_create", ctx->stream, ctx->opt_validate >= 1);
+    int vrc = pc.host(g, 1, "g");
+    if (!vrc) vrc = pc.host(h, 1, "h");
+    if (!vrc) vrc = pc.host(u, 1, "u");
+    if (!vrc) vrc = pc.host(gs, nbits, "gs");
+    if (!vrc) vrc = pc.host(hs, nbits, "hs");
     if (vrc) return vrc;
   }
   bpmi_rp_prover *pv = new bpmi_rp_prover();

@@ -330,9 +330,12 @@ static void test_host_pool() {
 static void test_msm_plan() {
   static const uint64_t edges[] = {1, 2, 1023, 1024, 2559, 2560, 4608, 4609, 5631, 5632, 8448, 8449, 10239, 10240, 15359, 15360, 18999, 19000, 1u << 15,
                                    (1u << 17) - 1, 1u << 17, (1u << 17) + 1, 184999, 185000, 1u << 19, 1u << 20, 1u << 23};
-  static const int32_t sets[][2] = {{0, 0}, {0, 2}, {0, 3}, {0, 4}, {0, 5}, {0, 6}, {0, 7}, {0, 8}, {0, 9}, {0, 10}, {0, 11}, {0, 12}, {0, 13}, {0, 14}, {0, 15}, {0, 16},
-                                    {1, 0}, {2, 0}, {3, 1}, {4, 1}, {4, 2}, {4, 3}, {4, 4}, {5, -1}, {6, -1}, {7, 1}, {7, 4}, {7, 16}, {7, 64}, {8, 0},
-                                    {9, 1}, {9, 86}, {9, 4096}, {10, 1}, {10, 3}, {10, 16}, {11, 0}};          // (index into PLAN_OPTION, value)
+  const int32_t wb = option_row("window_bits"), mp = option_row("mid_parts"), epl = option_row("reduce_epl"), ch = option_row("chunk"), rn = option_row("rounds");
+  const int32_t sets[][2] = {{wb, 0}, {wb, 2}, {wb, 3}, {wb, 4}, {wb, 5}, {wb, 6}, {wb, 7}, {wb, 8}, {wb, 9}, {wb, 10}, {wb, 11}, {wb, 12}, {wb, 13}, {wb, 14}, {wb, 15}, {wb, 16},
+                             {option_row("mixed_windows"), 0}, {option_row("top_window_unsigned"), 0}, {option_row("glv"), 1}, {mp, 1}, {mp, 2}, {mp, 3}, {mp, 4},
+                             {option_row("small_n"), -1}, {option_row("mid_single_min"), -1}, {epl, 1}, {epl, 4}, {epl, 16}, {epl, 64}, {option_row("reduce_fit"), 0},
+                             {ch, 1}, {ch, 86}, {ch, 4096}, {rn, 1}, {rn, 3}, {rn, 16}, {option_row("fused_scan"), 0}};          // (row of the option, value)
+  for (const auto &kv : sets) CHECK(kv[0] >= 0);
   std::vector<uint64_t> sizes(edges, edges + sizeof(edges) / sizeof(edges[0]));
   for (int i = 0; i < 200; i++) sizes.push_back(1 + rnd() % (1ull << (1 + rnd() % 23)));
   for (const auto &kv : sets)
@@ -360,7 +363,9 @@ static void test_msm_plan() {
         }
     }
   static const uint32_t totals[] = {(1u << 20) - 1, 1u << 20, 1703936, 1703937, 1u << 21, (1u << 21) + 1, 1u << 23, (1u << 23) + 1, (1u << 24) + 1};
-  static const int32_t slice_sets[][2] = {{14, 0}, {14, 1 << 16}, {14, 1 << 22}, {14, -1}};
+  const int32_t sn = option_row("slice_n");
+  CHECK(sn >= 0);
+  const int32_t slice_sets[][2] = {{sn, 0}, {sn, 1 << 16}, {sn, 1 << 22}, {sn, -1}};
   for (const auto &kv : slice_sets)
     for (uint32_t total : totals)
       for (int nsegs = 1; nsegs <= 3; nsegs++) {
@@ -404,8 +409,9 @@ static void test_rp_plan() {
   Buf table(8 * (Ptab + 1)), blobs((size_t)blobs_len), out(8 * RP_PLAN_WORDS), msg(64);
   memcpy(table.p, t.data(), table.n);
   if (blobs.n >= t[0] + 5 && damage < 2) { memcpy(blobs.p + t[0], "BPRP", 4); blobs.p[t[0] + 4] = (uint8_t)('0' + fmt); }
-  const int32_t kv[10] = {0, (int32_t)(rnd() % 3 ? 0 : 1 + rnd() % 100), 1, (int32_t)(rnd() % 2 ? 0 : 1 << (rnd() % 7)), 2, (int32_t)(rnd() % 5), 3, (int32_t)(rnd() % 2),
-                          4, (int32_t)(rnd() % 3)};
+  const int32_t kv[10] = {option_row("rp_rows"), (int32_t)(rnd() % 3 ? 0 : 1 + rnd() % 100), option_row("rp_lanes"), (int32_t)(rnd() % 2 ? 0 : 1 << (rnd() % 7)),
+                          option_row("rp_slices"), (int32_t)(rnd() % 5), option_row("rp_overlap"), (int32_t)(rnd() % 2), option_row("rp_priority"), (int32_t)(rnd() % 3)};
+  for (int i = 0; i < 5; i++) CHECK(kv[2 * i] >= 0);
   const uint64_t group = rnd() % 2 ? 0 : (rnd() % 3 ? 1 + rnd() % 9 : P + rnd() % 3);
   const int weights = (int)(rnd() % 2);
   uint64_t *w = (uint64_t *)out.p;

@@ -301,6 +301,8 @@ void t_host_tail(const uint8_t *pts, const uint8_t *zs, u32 W, u32 c, u32 nv, co
   for (int k = 0; k < 4; k++) { to.off[k] = off[k]; to.top_off[k] = top_off[k]; }
   bpmi_host::tail_combine(out, E.data(), W, c, to);
 }
+// the row of a bpmi_set_option name in the table of csrc/options_host.hpp (-1: none): what the kv pairs below address an option by
+int32_t t_option_row(const char *name) { return option_row(name); }
 // the MSM planner (csrc/msm_plan_host.hpp) as flat arrays: msm_plan_flat.hpp says what is where
 uint32_t t_msm_plan(const int32_t *kv, int nkv, uint64_t n, uint32_t w0, uint32_t wcount, uint32_t mode_bits, uint32_t *geom, uint64_t *layout, uint32_t *reduce) {
   return plan_flat(kv, nkv, n, w0, wcount, mode_bits, geom, layout, reduce);

@@ -5,18 +5,7 @@
 #include <stddef.h>
 
 #include "msm_plan_host.hpp"
-
-// options by index, in the order tests/test_msm_plan_cpu.py names them (OPTIONS there); anything not listed keeps the default of BpmiOptions
-static int BpmiOptions::*const PLAN_OPTION[] = {
-  &BpmiOptions::opt_c, &BpmiOptions::opt_mixed, &BpmiOptions::opt_top2, &BpmiOptions::opt_glv, &BpmiOptions::opt_mid_parts, &BpmiOptions::opt_small,
-  &BpmiOptions::opt_mid_single, &BpmiOptions::opt_epl, &BpmiOptions::opt_reduce_fit, &BpmiOptions::opt_chunk, &BpmiOptions::opt_rounds, &BpmiOptions::opt_fuse,
-  &BpmiOptions::opt_inblock, &BpmiOptions::opt_prio, &BpmiOptions::opt_slice_n, &BpmiOptions::opt_slice_min, &BpmiOptions::opt_split};
-#define PLAN_NOPTIONS ((int)(sizeof(PLAN_OPTION) / sizeof(PLAN_OPTION[0])))
-static inline BpmiOptions plan_options(const int32_t *kv, int nkv) {      // kv: (index, value) pairs
-  BpmiOptions o;
-  for (int i = 0; i < nkv; i++) if (kv[2 * i] >= 0 && kv[2 * i] < PLAN_NOPTIONS) o.*PLAN_OPTION[kv[2 * i]] = kv[2 * i + 1];
-  return o;
-}
+#include "options_flat.hpp"        // kv: (row of the option's name, value) pairs
 static inline MsmMode plan_mode(uint32_t bits) {          // 1 chained, 2 free_run, 4 beside
   MsmMode m;
   m.chained = bits & 1u; m.free_run = bits & 2u; m.beside = bits & 4u;

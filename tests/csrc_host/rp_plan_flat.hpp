@@ -5,11 +5,7 @@
 #include <stddef.h>
 
 #include "rp_batch_plan_host.hpp"
-
-// options by index, in the order tests/test_rp_plan_cpu.py names them (OPTIONS there); anything not listed keeps the default of BpmiOptions
-static int BpmiOptions::*const RP_PLAN_OPTION[] = {&BpmiOptions::opt_rp_rows, &BpmiOptions::opt_rp_lanes, &BpmiOptions::opt_rp_slices, &BpmiOptions::opt_rp_overlap,
-                                                   &BpmiOptions::opt_rp_prio};
-#define RP_PLAN_NOPTIONS ((int)(sizeof(RP_PLAN_OPTION) / sizeof(RP_PLAN_OPTION[0])))
+#include "options_flat.hpp"        // kv: (row of the option's name, value) pairs
 
 #define RP_PLAN_NREGIONS 11      // contrib ctx shared T lens | gsum gfin verdict ptflag E vals
 // err | P m k per ncols nslots fmt0 v2 rp_prio maxlen W | o_off o_w o_st stage_bytes | 11 x (off, bytes) | o_bad o_fin need | cell_row out_row rows
@@ -19,8 +15,7 @@ static int BpmiOptions::*const RP_PLAN_OPTION[] = {&BpmiOptions::opt_rp_rows, &B
 // the plan of one call as RP_PLAN_WORDS words; returns the error code (then only out[0] is set and msg holds the text, cut to msg_cap - 1 characters)
 static inline int rp_plan_flat(const int32_t *kv, int nkv, uint32_t n_gens, uint32_t m, uint64_t n_proofs, const uint8_t *blobs, uint64_t blobs_len,
                                const uint64_t *blob_off, int has_weights, uint64_t group, uint64_t *out, char *msg, size_t msg_cap) {
-  BpmiOptions o;
-  for (int i = 0; i < nkv; i++) if (kv[2 * i] >= 0 && kv[2 * i] < RP_PLAN_NOPTIONS) o.*RP_PLAN_OPTION[kv[2 * i]] = kv[2 * i + 1];
+  const BpmiOptions o = plan_options(kv, nkv);
   const RpPlan p = rp_prepare_plan(o, n_gens, m, n_proofs, blobs, blobs_len, blob_off, has_weights != 0, group);
   for (int i = 0; i < RP_PLAN_WORDS; i++) out[i] = 0;
   if (msg_cap) msg[0] = 0;

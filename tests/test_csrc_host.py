@@ -37,7 +37,20 @@ def load_shim():
     L.t_host_f_op.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]
     L.t_host_tail.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
                               ctypes.c_char_p]
+    L.t_option_row.restype = ctypes.c_int32
+    L.t_option_row.argtypes = [ctypes.c_char_p]
     return L
+
+
+def option_kv(L, opts):
+    """{bpmi_set_option name: value} as the (row, value) pairs the shim's planners take: an option is addressed by the row of its name in
+    the table of python-bulletproofs_amd/csrc/options_host.hpp."""
+    flat = []
+    for name, value in opts.items():
+        row = L.t_option_row(name.encode())
+        assert row >= 0, "no option %r" % name
+        flat += [row, value]
+    return (ctypes.c_int32 * max(len(flat), 1))(*flat), len(flat) // 2
 
 
 @pytest.fixture(scope="module")

@@ -150,3 +150,30 @@ def test_async_pair_state_machine(gp):
     assert lib.bpmi_msm_segs_dev(ctx, 0, None, None, None, out) == 0 and out.raw == bytes(64)
     d_p.free()
     d_s.free()
+
+
+def test_set_option_takes_and_refuses_what_the_case_list_says(gp):
+    """bpmi_set_option against tests/option_cases.py -- every option at its default, its accepted edges and the nearest refused values:
+    the return code and bpmi_last_error.  On a context of its own, every default restored at once; a refused value leaves the message of
+    that option, an unknown name its own text."""
+    from bulletproofs_amd.engine import Engine
+    from option_cases import CASES, UNKNOWN
+    eng = Engine()
+    lib, ctx = eng.lib, eng.ctx
+    try:
+        for name, default, good, bad, msg, _ in CASES:
+            for v in [default] + good:
+                assert lib.bpmi_set_option(ctx, name.encode(), v) == 0, (name, v, lib.bpmi_last_error(ctx))
+                assert lib.bpmi_set_option(ctx, name.encode(), default) == 0, (name, default)
+            for v in bad:
+                assert lib.bpmi_set_option(ctx, name.encode(), v) == -3, (name, v)
+                assert lib.bpmi_last_error(ctx).decode() == msg, (name, v)
+        for name in UNKNOWN:
+            assert lib.bpmi_set_option(ctx, name.encode(), 0) == -3 and lib.bpmi_last_error(ctx).decode() == "unknown option " + name
+        assert lib.bpmi_set_option(ctx, None, 0) == -3 and lib.bpmi_set_option(None, b"chunk", 0) == -3
+        # the context still works under its restored defaults
+        out = ctypes.create_string_buffer(b"\x55" * 64, 64)
+        pts, sc = cbind.pack_points(gp.rand_points(3, 5)[0]), cbind.pack_scalars([1, 2, 3])
+        assert lib.bpmi_msm(ctx, pts, sc, 3, out) == 0 and out.raw == cbind.msm_bytes(pts, sc, 3)
+    finally:
+        eng.close()

@@ -333,6 +333,29 @@ def test_argument_errors_of_the_batch_entry_points(gp):
         bad[64 + 32] ^= 1
         rc, msg, out = call(ep=bytes(bad))
         assert rc == -3 and "extra_pts[1]" in msg and "bpmi_ipa_verify_batch_dev" in msg and out != bytes(64)
+        # 65 extra points, the smallest count the kernel checks instead of the host: the same refusal.  From level 2 the generators are
+        # checked too, and of several bad arrays the first in the order d_g, d_h, extra_pts is named
+        text, refused = "bpmi_ipa_verify_batch_dev: %s is not a point of the curve", b"\xff" * 64
+
+        def flipped(blob, i):
+            b = bytearray(blob)
+            b[64 * i + 32] ^= 1
+            return bytes(b)
+        g_bytes, h_bytes = cbind.pack_points(pts[:n]), cbind.pack_points(pts[n: 2 * n])
+        ex65, es65 = cbind.pack_points(gp.rand_points(65, 12)[0]), pack(list(range(1, 66)))
+        rc, _, out = call(ep=ex65, es=es65, ne=65)
+        assert rc == 0 and out not in (bytes(64), refused)
+        assert call(ep=flipped(ex65, 64), es=es65, ne=65) == (-3, text % "extra_pts[64]", refused)
+        d_g.upload(flipped(g_bytes, 3))
+        assert call()[0] == 0                                                  # level 1: device pointers are the caller's responsibility
+        eng.set_option("validate_points", 2)
+        assert call(ep=flipped(ex65, 64), es=es65, ne=65) == (-3, text % "d_g[3]", refused)
+        d_g.upload(g_bytes)
+        d_h.upload(flipped(h_bytes, 2))
+        assert call() == (-3, text % "d_h[2]", refused)
+        d_h.upload(h_bytes)
+        assert call()[0] == 0
+        eng.set_option("validate_points", 1)
         sa, sb = ctypes.create_string_buffer(32 * n), ctypes.create_string_buffer(32 * n)
         assert lib.bpmi_sc_svector_sum(ctx, k, 0, xs, xi, one, one, one, None, sa, sb) == -3 and "2^16 proofs" in lib.bpmi_last_error(ctx).decode()
         assert lib.bpmi_sc_svector_sum(ctx, 23, 1, xs, xi, one, one, one, None, sa, sb) == -3 and "k <= 22" in lib.bpmi_last_error(ctx).decode()
@@ -341,5 +364,6 @@ def test_argument_errors_of_the_batch_entry_points(gp):
         assert lib.bpmi_sc_svector_sum(None, k, 1, xs, xi, one, one, one, None, sa, sb) == -3
         assert lib.bpmi_sc_svector_sum(ctx, k, 1, xs, xi, one, one, one, None, sa, sb) == 0
     finally:
+        eng.set_option("validate_points", 1)
         d_g.free()
         d_h.free()

@@ -150,7 +150,7 @@ def test_wire_decoders_every_alias_and_tiny_y_case_in_one_batch(eng, wire, fmt):
 
 
 # ---- 3. wire_point_valid: the host loop and k_ec_validate ---------------------------------------------------------------------------
-HOST_MAX = 64                                    # csrc/bpmi.hip VALIDATE_HOST_MAX: bpmi_ec_sum checks up to 64 points on the host
+HOST_MAX = 64                                    # csrc/point_check_host.hpp VALIDATE_HOST_MAX: bpmi_ec_sum checks up to 64 points on the host
 
 
 @pytest.fixture(scope="module")

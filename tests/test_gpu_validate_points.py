@@ -118,8 +118,55 @@ def test_other_host_pointer_entry_points(gp):
     assert lib.bpmi_rp_prover_create(ctx, 8, u, bad, u, gs, hs, ctypes.byref(pv)) == -3 and b"h[0]" in lib.bpmi_last_error(ctx)
 
 
+def _replace(blob, i, point):
+    return blob[: 64 * i] + point + blob[64 * (i + 1):]
+
+
+def test_ipa_verify_dev_names_the_bad_array(gp):
+    """bpmi_ipa_verify_dev: up to 64 extra points are checked on the host, before `out` is touched; more by the kernel, and the refused call
+    leaves 0xFF.. (never the identity); the generators only from level 2, and of several bad arrays the first in the order d_g, d_h,
+    extra_pts is the one named."""
+    eng = gp.engine()
+    lib, ctx = eng.lib, eng.ctx
+    n, k = 4, 2
+    pts, _ = gp.rand_points(2 * n + 65, 13)
+    g, h, ex = cbind.pack_points(pts[:n]), cbind.pack_points(pts[n: 2 * n]), cbind.pack_points(pts[2 * n:])
+    bad = _bad_points()[0]
+    xs, xi = cbind.pack_scalars([3, 5]), cbind.pack_scalars([pow(3, -1, Q), pow(5, -1, Q)])
+    one, es = cbind.pack_scalars([1]), cbind.pack_scalars(list(range(1, 66)))
+    d_g, d_h = eng.upload(g), eng.upload(h)
+    fill, refused = b"\x55" * 64, b"\xff" * 64
+
+    def call(ep, ne):
+        out = ctypes.create_string_buffer(fill, 64)
+        rc = lib.bpmi_ipa_verify_dev(ctx, d_g.ptr, d_h.ptr, None, n, xs, xi, k, one, one, ep, es, ne, out)
+        return rc, lib.bpmi_last_error(ctx).decode(), out.raw
+
+    text = "bpmi_ipa_verify_dev: %s is not a point of the curve"
+    try:
+        for ne in (3, 65):                                                     # well-formed calls (of an invalid statement) on both paths
+            rc, _, out = call(ex, ne)
+            assert rc == 0 and out not in (fill, refused)
+        assert call(_replace(ex, 1, bad), 3) == (-3, text % "extra_pts[1]", fill)          # the host path: `out` keeps its fill pattern
+        assert call(_replace(ex, 64, bad), 65) == (-3, text % "extra_pts[64]", refused)      # 65: the smallest count that takes the kernel
+        d_g.upload(_replace(g, 3, bad))
+        assert call(ex, 3)[0] == 0                                             # level 1: device pointers are the caller's responsibility
+        eng.set_option("validate_points", 2)
+        assert call(_replace(ex, 64, bad), 65) == (-3, text % "d_g[3]", refused)             # two bad arrays: the one queued first
+        d_g.upload(g)
+        d_h.upload(_replace(h, 2, bad))
+        assert call(ex, 3) == (-3, text % "d_h[2]", refused)
+        d_h.upload(h)
+        rc, _, out = call(ex, 65)
+        assert rc == 0 and out not in (fill, refused)
+    finally:
+        eng.set_option("validate_points", 1)
+        d_g.free(); d_h.free()
+
+
 def test_batch_verifier_rejects_an_off_curve_commitment(gp):
-    """bpmi_rp_batch_verify_dev: a commitment that is not a point is an ARGUMENT error with its index -- neither a verdict nor a value."""
+    """bpmi_rp_batch_verify_dev and bpmi_rp_batch_group_values_dev: a commitment that is not a point is an ARGUMENT error with its index --
+    neither a verdict nor a value; from level 2 so is a generator."""
     from bulletproofs_amd.engine import EngineError
     from bulletproofs_amd.rangeproofs import BatchRangeProver, BatchRangeVerifier
     from bulletproofs_amd.utils import ModP, commitment
@@ -139,4 +186,36 @@ def test_batch_verifier_rejects_an_off_curve_commitment(gp):
     assert bv.partial_wire(Vb, blobs) == bytes(64)
     with pytest.raises(EngineError, match=r"v_points\[23\] is not a point of the curve"):
         bv.partial_wire(Vb[: 64 * 23] + _bad_points()[0] + Vb[64 * 24:], blobs)
+    assert bv.partial_wire(Vb, blobs) == bytes(64)
+
+    # the values of groups of 8 proofs: the same refusal, and every value is left as 0xFF..
+    eng = gp.engine()
+    bad, group, ngroups = _bad_points()[0], 8, 5
+
+    def group_values(Vs):
+        import ctypes as C
+        _, cnt, m, src, nbytes, offs, weights, seed, vbytes, d_pts, d_scs = bv._wire_call("group_values_wire", Vs, blobs, None)
+        values, status = C.create_string_buffer(b"\x55" * (64 * ngroups), 64 * ngroups), C.create_string_buffer(cnt)
+        rc = eng.lib.bpmi_rp_batch_group_values_dev(eng.ctx, n, m, cnt, src, nbytes, C.cast(offs, C.c_void_p), weights, seed, vbytes, bv._d_shared_pts.ptr,
+                                                    d_pts.ptr, d_scs.ptr, group, C.cast(values, C.c_void_p), C.cast(status, C.c_void_p))
+        return rc, eng.lib.bpmi_last_error(eng.ctx).decode(), values.raw
+
+    text = "bpmi_rp_batch_%s_dev: %s is not a point of the curve"
+    refused = b"\xff" * (64 * ngroups)
+    assert group_values(Vb)[::2] == (0, bytes(64 * ngroups))
+    assert group_values(_replace(Vb, 23, bad)) == (-3, text % ("group_values", "v_points[23]"), refused)
+    # level 2: the generators (g, h, u, gs, hs in device memory) are checked too, behind the commitments
+    shared = bv._shared_pts
+    try:
+        eng.set_option("validate_points", 2)
+        assert bv.partial_wire(Vb, blobs) == bytes(64)
+        bv._d_shared_pts.upload(_replace(shared, 5, bad))
+        with pytest.raises(EngineError, match=r"bpmi_rp_batch_verify_dev: d_gens\[5\] is not a point of the curve"):
+            bv.partial_wire(Vb, blobs)
+        assert group_values(Vb) == (-3, text % ("group_values", "d_gens[5]"), refused)
+        with pytest.raises(EngineError, match=r"bpmi_rp_batch_verify_dev: v_points\[23\] is not a point of the curve"):
+            bv.partial_wire(_replace(Vb, 23, bad), blobs)
+    finally:
+        eng.set_option("validate_points", 1)
+        bv._d_shared_pts.upload(shared)
     assert bv.partial_wire(Vb, blobs) == bytes(64)

@@ -8,11 +8,8 @@ import random
 
 import pytest
 
-from test_csrc_host import shim  # noqa: F401  (the fixture that builds and loads the shim)
+from test_csrc_host import option_kv, shim  # noqa: F401  (the fixture that builds and loads the shim; options go by their bpmi_set_option names)
 
-# the options the plan reads, by their bpmi_set_option names, in the order of PLAN_OPTION (tests/csrc_host/msm_plan_flat.hpp)
-OPTIONS = ["window_bits", "mixed_windows", "top_window_unsigned", "glv", "mid_parts", "small_n", "mid_single_min", "reduce_epl", "reduce_fit",
-           "chunk", "rounds", "fused_scan", "sort_inblock", "priority", "slice_n", "slice_min", "split"]
 GEOM = ["n", "c", "W", "w0", "B", "G", "L", "nv", "prio", "fuse", "top2", "inblock", "mid", "small", "glv", "mid_parts"]
 REGIONS = ["glv_sub", "glv_bx", "glv_neg", "hist", "off", "cursor", "bsum", "coarse_hist", "coarse_off", "coarse_cursor", "dig", "sidx", "dig16", "negs",
            "chunk_key", "buckets", "rec_key0", "rec_pt0", "rec_key1", "rec_pt1", "D", "E", "F", "out"]
@@ -37,13 +34,6 @@ OPTION_SETS = ([{}] + [{"window_bits": c} for c in range(2, 17)] + [{"mixed_wind
 GROUP_SETS = [{}, {"window_bits": 8}, {"window_bits": 13}, {"window_bits": 16}, {"mixed_windows": 0}]
 
 
-def _kv(opts):
-    flat = []
-    for k, v in opts.items():
-        flat += [OPTIONS.index(k), v]
-    return (ctypes.c_int32 * max(len(flat), 1))(*flat), len(flat) // 2
-
-
 def bind(L):
     L.t_msm_plan.restype = ctypes.c_uint32
     L.t_msm_plan.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
@@ -54,7 +44,7 @@ def bind(L):
 
 def raw_plan(L, opts, n, mode=0, w0=0, wcount=0):
     """(window bits of n, geom words, layout words, reduce words) exactly as the shim returns them."""
-    kv, nkv = _kv(opts)
+    kv, nkv = option_kv(L, opts)
     geom, layout, reduce = (ctypes.c_uint32 * len(GEOM))(), (ctypes.c_uint64 * 30)(), (ctypes.c_uint32 * REDUCE_WORDS)()
     c = L.t_msm_plan(kv, nkv, n, w0, wcount, mode, geom, layout, reduce)
     return c, list(geom), list(layout), list(reduce)
@@ -75,7 +65,7 @@ def plan(L, opts, n, mode=0, w0=0, wcount=0):
 
 def slices(L, opts, nseg, cap=4096):
     """K and the K segs_slice results (total, n[3], pts[3], sc[3]) for segments of nseg pairs at made-up, never-read addresses."""
-    kv, nkv = _kv(opts)
+    kv, nkv = option_kv(L, opts)
     pts = [(i + 1) << 44 for i in range(3)]
     sc = [((i + 1) << 44) + (1 << 43) for i in range(3)]
     out = (ctypes.c_uint64 * (10 * cap))()

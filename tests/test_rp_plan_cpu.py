@@ -10,10 +10,8 @@ import itertools
 import random
 
 from conftest import load_golden
-from test_csrc_host import shim  # noqa: F401  (the fixture that builds and loads the shim)
+from test_csrc_host import option_kv, shim  # noqa: F401  (the fixture that builds and loads the shim; options go by their bpmi_set_option names)
 
-# the options the plan reads, by their bpmi_set_option names, in the order of RP_PLAN_OPTION (tests/csrc_host/rp_plan_flat.hpp)
-OPTIONS = ["rp_rows", "rp_lanes", "rp_slices", "rp_overlap", "rp_priority"]
 SHAPE = ["P", "m", "k", "per", "ncols", "nslots", "fmt0", "v2", "rp_prio", "maxlen", "W", "o_off", "o_w", "o_st", "stage_bytes"]
 REGIONS = ["contrib", "ctx", "shared", "T", "lens"]
 GROUP_REGIONS = ["gsum", "gfin", "verdict", "ptflag", "E", "vals"]
@@ -68,11 +66,9 @@ def offset_table(P, fmt):
 
 def raw_plan(L, opts, n_gens, m, P, blobs, blobs_len, table, weights=False, group=0):
     """(error code, message, the RP_PLAN_WORDS words) exactly as the shim returns them; blobs: bytes, or None for a null pointer."""
-    flat = []
-    for k, v in opts.items():
-        flat += [OPTIONS.index(k), v]
+    kv, nkv = option_kv(L, opts)
     out, msg = (ctypes.c_uint64 * WORDS)(), ctypes.create_string_buffer(128)
-    rc = L.t_rp_plan((ctypes.c_int32 * max(len(flat), 1))(*flat), len(flat) // 2, n_gens, m, P, blobs, blobs_len, table, int(weights), group, out, msg, 128)
+    rc = L.t_rp_plan(kv, nkv, n_gens, m, P, blobs, blobs_len, table, int(weights), group, out, msg, 128)
     return rc, msg.value.decode(), list(out)
 
 
