@@ -625,6 +625,66 @@ int bpmi_ipa_prove_batch(bpmi_ipa_batch_prover *pv, int protocol, uint64_t n_pro
                          uint64_t cap, uint64_t *tr_off);
 int bpmi_ipa_batch_prover_last_ms(const bpmi_ipa_batch_prover *pv, double ms[4]);
 
+/* ---- batch verifier of PACKED inner-product proofs ---------------------------------------- */
+/* What bpmi_ipa_prove_batch writes, verified without leaving native code: the Fiat-Shamir re-hash, the byte-level checks and the
+ * weighted scalars of every proof run per proof (host twin: csrc/ipa_packed_host.hpp; kernels: csrc/ipa_packed_kernels.hpp), then
+ * the batch is the one MSM of bpmi_ipa_verify_batch_dev.  No new wire format: for n = 2^k the input is, per call,
+ *   ab           n_proofs x 64 B        a || b, little-endian
+ *   xs           n_proofs x k x 32 B    the challenges, little-endian                           (NULL allowed at k = 0)
+ *   LR           n_proofs x 2k x 64 B   L_0 .. L_(k-1) R_0 .. R_(k-1), affine; the identity is 64 zero bytes   (NULL allowed at k = 0)
+ *   transcripts, tr_off (n_proofs + 1)  proof p's inner (Protocol-2) transcript text is transcripts[tr_off[p] .. tr_off[p+1])
+ *   start        n_proofs x uint32, or NULL: Proof2.start_transcript; NULL = 1 for every proof (the empty prefix).  Protocol 2 only
+ *   u            protocol 2: n_proofs x 64 B; protocol 1: 64 B (the statements' one u)
+ *   P            n_proofs x 64 B
+ *   c, head      protocol 1: n_proofs x 32 B claimed inner products, n_proofs x 128 B u_new || P_new; NULL under protocol 2
+ * Under protocol 1 the transcript is the inner one as the prover writes it, "&" base64(seed) "&" str(x) "&" rounds..: the rounds
+ * begin at item 3 and Verifier1's challenge is item 2.
+ * A packed proof is VALID exactly when the Proof2 / Proof1 object with the same bytes passes Verifier2.verify
+ * (/root/reference/src/innerproduct/inner_product_verifier.py:104-147) / Verifier1.verify (:44-58; its transcript = items 1-2 of
+ * the inner one plus "&", start_transcript = 3), with four conventions of this ABI on top: a, b, c and xs[j] are below q; a point
+ * is the identity or on the curve; a decimal item is canonical (what str(int) prints); a transcript of more than 2^17 bytes is
+ * invalid (the longest the prover writes, from a 65 535-byte seed at k = 22, is shorter).
+ * Outputs of the preparation, per proof p:
+ *   record        16k + 24 words: k pairs (x_j, x_j^-1), then a, b, w_p -- what the s-vector sum of bpmi_ipa_verify_batch_dev reads;
+ *                 ONE inversion per proof
+ *   extra pairs   protocol 2, 2k + 2:  points [u_p, L_0.., R_0.., P_p]               scalars [w a b, -w x_j^2, -w x_j^-2, -w]
+ *                 protocol 1, 2k + 4:  points [u_new, L.., R.., P_new, P_p, u]       scalars [w a b + r2, -w x_j^2, -w x_j^-2, r1 - w, -r1,
+ *                 -(r1 c + r2) x]: Verifier2's equation over (u_new, P_new) under w, P_new = P + x c u (:51) under r1, u_new = x u
+ *                 (:52) under r2
+ *   status        bit 0: a byte-level check failed -- a value >= q; a short or malformed transcript; an L / R item that is not
+ *                 base64(SEC1(point)) ("AA==" for the identity) (:114-115); an x item that is not the canonical decimal of xs[j] or not
+ *                 the re-hash of its prefix (:116-125); protocol 1: item 2 is not mod_hash(item 1 "&") (:36-42)
+ *                 bit 1: a point of the proof (LR, P, head, a per-proof u) is neither the identity nor on the curve; checked under
+ *                 "validate_points" >= 1 (always by the host twin); at 0 the result is unspecified but never out of bounds
+ *                 A flagged proof contributes NOTHING: zero record, zero scalars, identity points.
+ * Weights: explicit, little-endian, reduced mod q -- one per proof (w) under protocol 2, three (w, r1, r2) under protocol 1 -- or
+ * NULL with a 32-byte seed: then weight t of proof p is SHA-256(seed || LE64(p) || t) cut to 248 bits, 0 replaced by 1, as in
+ * bpmi_rp_batch_prepare.  They must be unpredictable to whoever made the proofs.
+ * BPMI_E_ARG before anything is read or allocated: a protocol other than 1 or 2; NULL where an array is required or non-NULL where
+ * it must be NULL; decreasing tr_off; more than 4 GiB of transcripts; the bounds of bpmi_ipa_verify_batch_dev (k <= 22, 1 .. 2^16
+ * proofs, n_proofs x n <= 2^32, the half tables, 2^22 extra pairs); protocol 1: a u that is not on the curve.  n_proofs = 0 is
+ * BPMI_OK and touches nothing.
+ *   bpmi_ipa_batch_prepare       HOST code on `threads` threads, no ctx (its message: bpmi_last_error(NULL)); records, extra_pts,
+ *                                extra_scalars, status in host memory
+ *   bpmi_ipa_batch_prepare_dev   the same bytes (tests/test_gpu_ipa_packed.py) by the kernels, into device memory; status to the host
+ *   bpmi_ipa_verify_batch_packed_dev   upload, preparation, s-vector sum and the one MSM over [g | h | extra] in one call:
+ *                                out = the weighted combination over the unflagged proofs; the batch is valid iff every status is
+ *                                0 and out is 64 zero bytes (up to the 1/q soundness error).  d_g, d_h (, d_hscale): as in
+ *                                bpmi_ipa_verify_batch_dev; the generators are checked at "validate_points" = 2; a call refused for
+ *                                a point leaves 0xFF.. in out.  n_proofs = 0 writes the identity.  One call at a time per ctx. */
+int bpmi_ipa_batch_prepare(uint32_t k, int protocol, uint64_t n_proofs, const uint8_t *ab, const uint8_t *xs, const uint8_t *LR, const uint8_t *transcripts,
+                           const uint64_t *tr_off, const uint32_t *start, const uint8_t *u, const uint8_t *P, const uint8_t *c, const uint8_t *head,
+                           const uint8_t *weights, const uint8_t *seed, int threads, uint8_t *records, uint8_t *extra_pts, uint8_t *extra_scalars,
+                           uint8_t *status);
+int bpmi_ipa_batch_prepare_dev(bpmi_ctx *ctx, uint32_t k, int protocol, uint64_t n_proofs, const uint8_t *ab, const uint8_t *xs, const uint8_t *LR,
+                               const uint8_t *transcripts, const uint64_t *tr_off, const uint32_t *start, const uint8_t *u, const uint8_t *P, const uint8_t *c,
+                               const uint8_t *head, const uint8_t *weights, const uint8_t *seed, void *d_records, void *d_extra_pts, void *d_extra_scalars,
+                               uint8_t *status);
+int bpmi_ipa_verify_batch_packed_dev(bpmi_ctx *ctx, const void *d_g, const void *d_h, const void *d_hscale, uint64_t n, int protocol, uint64_t n_proofs,
+                                     const uint8_t *ab, const uint8_t *xs, const uint8_t *LR, const uint8_t *transcripts, const uint64_t *tr_off,
+                                     const uint32_t *start, const uint8_t *u, const uint8_t *P, const uint8_t *c, const uint8_t *head, const uint8_t *weights,
+                                     const uint8_t *seed, uint8_t out[64], uint8_t *status);
+
 /* Page-locked host memory (hipHostMalloc) for buffers handed to the library repeatedly, e.g. the receive buffer of wire proofs. */
 int bpmi_host_alloc(bpmi_ctx *ctx, size_t bytes, void **out);
 int bpmi_host_free(bpmi_ctx *ctx, void *p);

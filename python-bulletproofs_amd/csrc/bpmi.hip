@@ -57,6 +57,7 @@ using namespace bpmi;
 #include "rp_prove_plan_host.hpp"
 #include "ipa_prove_plan_host.hpp"
 #include "ipa_batch_plan_host.hpp"
+#include "ipa_packed_plan_host.hpp"
 #include "msm_batch_plan_host.hpp"
 #include "context.hpp"
 #include "device_util.hpp"
@@ -69,11 +70,13 @@ using namespace bpmi;
 #include "host_tail.hpp"
 #include "msm_host.hpp"
 #include "rp_batch_host.hpp"
+#include "ipa_packed_host.hpp"
 #include "host_pool.hpp"
 #include "rp_algebra_host.hpp"
 #include "transcript_host.hpp"
 #include "rp_wire_v2_host.hpp"
 #include "rp_batch_kernels.hpp"
+#include "ipa_packed_kernels.hpp"
 #include "rp_prove_kernels.hpp"
 #include "ipa_prove_kernels.hpp"
 #include "h2c.hpp"
@@ -789,6 +792,7 @@ int bpmi_ipa_verify_dev(bpmi_ctx *ctx, const void *d_g, const void *d_h, const v
 
 #include "ipa_host.hpp"
 #include "ipa_batch_host.hpp"
+#include "ipa_packed_dev_host.hpp"
 #include "msm_batch_host.hpp"
 #include "rp_batch_dev_host.hpp"
 

@@ -8,20 +8,11 @@
 
 extern "C" {
 
-// the proofs' records (k pairs (x_j, x_j^-1), then a, b, w) into the workspace, then the three launches that leave SA and SB there
-static int ipab_svector_sum(bpmi_ctx *ctx, const IpabPlan &pl, const void *d_scale, const uint8_t *xs, const uint8_t *xinvs, const uint8_t *a,
-                            const uint8_t *b, const uint8_t *weights) {
+// the three launches that leave SA and SB in the workspace, from the proofs' records (k pairs (x_j, x_j^-1), then a, b, w) that are
+// in the workspace already: uploaded by ipab_svector_sum, or written there by the preparation kernels (ipa_packed_dev_host.hpp)
+static int ipab_svector_launches(bpmi_ctx *ctx, const IpabPlan &pl, const void *d_scale) {
   char *base = (char *)ctx->stage_in;
   const u32 k = pl.k;
-  const size_t rec_bytes = 4 * (size_t)pl.rec_words;
-  std::vector<uint8_t> recs(rec_bytes * pl.n_proofs);
-  for (uint64_t p = 0; p < pl.n_proofs; p++) {
-    uint8_t *r = &recs[rec_bytes * p];
-    for (u32 j = 0; j < k; j++) { memcpy(r + 64 * j, xs + 32 * (p * k + j), 32); memcpy(r + 64 * j + 32, xinvs + 32 * (p * k + j), 32); }
-    memcpy(r + 64 * k, a + 32 * p, 32); memcpy(r + 64 * k + 32, b + 32 * p, 32); memcpy(r + 64 * k + 64, weights + 32 * p, 32);
-  }
-  HIPCHK(ctx, h2d(ctx, base + pl.o_rec, recs.data(), recs.size(), ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));          // recs is owned by this frame
   u32 *sa = (u32 *)(base + pl.o_sa), *sb = (u32 *)(base + pl.o_sb), *part = (u32 *)(base + pl.o_part);
   const u32 *tabs = (const u32 *)(base + pl.o_tab);
   const u32 n = (u32)pl.n, P = (u32)pl.n_proofs, ntab = (u32)pl.tab_entries;
@@ -40,6 +31,23 @@ static int ipab_svector_sum(bpmi_ctx *ctx, const IpabPlan &pl, const void *d_sca
   }
   HIPCHK(ctx, hipGetLastError());
   return BPMI_OK;
+}
+
+// the proofs' records assembled on the host and uploaded, then the launches
+static int ipab_svector_sum(bpmi_ctx *ctx, const IpabPlan &pl, const void *d_scale, const uint8_t *xs, const uint8_t *xinvs, const uint8_t *a,
+                            const uint8_t *b, const uint8_t *weights) {
+  char *base = (char *)ctx->stage_in;
+  const u32 k = pl.k;
+  const size_t rec_bytes = 4 * (size_t)pl.rec_words;
+  std::vector<uint8_t> recs(rec_bytes * pl.n_proofs);
+  for (uint64_t p = 0; p < pl.n_proofs; p++) {
+    uint8_t *r = &recs[rec_bytes * p];
+    for (u32 j = 0; j < k; j++) { memcpy(r + 64 * j, xs + 32 * (p * k + j), 32); memcpy(r + 64 * j + 32, xinvs + 32 * (p * k + j), 32); }
+    memcpy(r + 64 * k, a + 32 * p, 32); memcpy(r + 64 * k + 32, b + 32 * p, 32); memcpy(r + 64 * k + 64, weights + 32 * p, 32);
+  }
+  HIPCHK(ctx, h2d(ctx, base + pl.o_rec, recs.data(), recs.size(), ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));          // recs is owned by this frame
+  return ipab_svector_launches(ctx, pl, d_scale);
 }
 
 int bpmi_sc_svector_sum(bpmi_ctx *ctx, uint32_t k, uint64_t n_proofs, const uint8_t *xs, const uint8_t *xinvs, const uint8_t *a, const uint8_t *b,

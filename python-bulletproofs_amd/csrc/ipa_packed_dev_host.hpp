@@ -1,0 +1,153 @@
+// ipa_packed_dev_host.hpp -- part of libbpmi (included by bpmi.hip; one translation unit).  HOST code.
+// The batch verifier of PACKED inner-product proofs (what bpmi_ipa_prove_batch writes): bpmi_ipa_batch_prepare (the host twin,
+// ipa_packed_host.hpp), bpmi_ipa_batch_prepare_dev (the kernels of ipa_packed_kernels.hpp) and bpmi_ipa_verify_batch_packed_dev:
+// upload, preparation kernels, the s-vector launches of ipa_batch_host.hpp from the records the kernels left in the workspace, and
+// the one MSM over [g | h | extra] -- no host loop over proofs.  Plan and argument errors: ipa_packed_plan_host.hpp.
+#pragma once
+
+extern "C" {
+
+static IpaPackedIn ipap_in(const uint8_t *ab, const uint8_t *xs, const uint8_t *LR, const uint8_t *transcripts, const uint64_t *tr_off, const uint32_t *start,
+                           const uint8_t *u, const uint8_t *P, const uint8_t *c, const uint8_t *head, const uint8_t *weights, const uint8_t *seed) {
+  IpaPackedIn in;
+  in.ab = ab; in.xs = xs; in.LR = LR; in.transcripts = transcripts; in.tr_off = tr_off; in.start = start;
+  in.u = u; in.P = P; in.c = c; in.head = head; in.weights = weights; in.seed = seed;
+  return in;
+}
+
+int bpmi_ipa_batch_prepare(uint32_t k, int protocol, uint64_t n_proofs, const uint8_t *ab, const uint8_t *xs, const uint8_t *LR, const uint8_t *transcripts,
+                           const uint64_t *tr_off, const uint32_t *start, const uint8_t *u, const uint8_t *P, const uint8_t *c, const uint8_t *head,
+                           const uint8_t *weights, const uint8_t *seed, int threads, uint8_t *records, uint8_t *extra_pts, uint8_t *extra_scalars,
+                           uint8_t *status) {
+  static const std::string fn = "bpmi_ipa_batch_prepare: ";
+  if (n_proofs == 0) return BPMI_OK;
+  if (!records || !extra_pts || !extra_scalars || !status) return fail(nullptr, BPMI_E_ARG, fn + "null argument");
+  const IpaPackedIn in = ipap_in(ab, xs, LR, transcripts, tr_off, start, u, P, c, head, weights, seed);
+  const IpapPlan pl = ipa_packed_plan(BpmiOptions(), k, protocol, n_proofs, in, 0);
+  if (pl.err) return fail(nullptr, pl.err, fn + pl.msg);
+  if (protocol == 1 && !ipap::point_ok(u)) return fail(nullptr, BPMI_E_ARG, fn + "u[0] is not a point of the curve");
+  try {
+    ipap::prepare_all(k, protocol, n_proofs, in, threads, records, extra_pts, extra_scalars, status);
+  } catch (const std::exception &) {
+    return fail(nullptr, BPMI_E_NOMEM, fn + "out of host memory");
+  }
+  return BPMI_OK;
+}
+
+// upload the packed arrays into their regions and run the preparation kernels; records, extra points and extra scalars go to the
+// given device arrays (the workspace regions of pl.base, or the caller's), the status bytes to the region of the plan
+static int ipap_run(bpmi_ctx *ctx, const IpapPlan &pl, const IpaPackedIn &in, u32 *d_records, u32 *d_expts, u32 *d_exsc) {
+  char *base = (char *)ctx->stage_in;
+  hipStream_t st = ctx->stream;
+  const u32 k = pl.base.k;
+  const uint64_t P = pl.base.n_proofs;
+  auto up = [&](uint64_t off, const void *src, uint64_t bytes) { return bytes ? h2d(ctx, base + off, src, bytes, st) : hipSuccess; };
+  HIPCHK(ctx, up(pl.o_ab, in.ab, pl.b_ab));
+  HIPCHK(ctx, up(pl.o_xs, in.xs, pl.b_xs));
+  HIPCHK(ctx, up(pl.o_lr, in.LR, pl.b_lr));
+  HIPCHK(ctx, up(pl.o_tr, in.transcripts + in.tr_off[0], pl.tr_bytes));
+  HIPCHK(ctx, up(pl.o_troff, in.tr_off, pl.b_troff));
+  HIPCHK(ctx, up(pl.o_start, in.start, pl.b_start));
+  HIPCHK(ctx, up(pl.o_u, in.u, pl.b_u));
+  HIPCHK(ctx, up(pl.o_P, in.P, pl.b_P));
+  HIPCHK(ctx, up(pl.o_c, in.c, pl.b_c));
+  HIPCHK(ctx, up(pl.o_head, in.head, pl.b_head));
+  HIPCHK(ctx, up(pl.o_w, in.weights, pl.b_w));
+  ipad::Params q;
+  memset(&q, 0, sizeof(q));
+  q.tr_off = (const u64 *)(base + pl.o_troff);
+  q.start = in.start ? (const u32 *)(base + pl.o_start) : nullptr;
+  q.ab = (const uint8_t *)base + pl.o_ab; q.xs = (const uint8_t *)base + pl.o_xs; q.LR = (const uint8_t *)base + pl.o_lr;
+  q.u = (const uint8_t *)base + pl.o_u; q.P = (const uint8_t *)base + pl.o_P; q.c = (const uint8_t *)base + pl.o_c; q.head = (const uint8_t *)base + pl.o_head;
+  q.weights = in.weights ? (const uint8_t *)base + pl.o_w : nullptr;
+  if (!in.weights)
+    for (int i = 0; i < 8; i++) q.seed[i] = ((u32)in.seed[4 * i] << 24) | ((u32)in.seed[4 * i + 1] << 16) | ((u32)in.seed[4 * i + 2] << 8) | in.seed[4 * i + 3];
+  q.k = k; q.protocol = (u32)pl.protocol; q.Pall = (u32)P; q.validate = ctx->opt_validate >= 1 ? 1u : 0u;
+  q.records = d_records; q.extra_sc = d_exsc; q.roles = (uint8_t *)base + pl.o_roles;
+  q.T = (const u64 *)(base + pl.o_T);
+  {
+    StageTimer t(ctx, ST_RPPREP);
+    for (uint64_t first = 0; first < P; first += pl.rows) {
+      const u32 cnt = (u32)(P - first < pl.rows ? P - first : pl.rows);
+      q.first = first; q.P_launch = cnt; q.Tstride = cnt;
+      hipLaunchKernelGGL(ipad::k_ipap_transpose, dim3((cnt + 63) / 64, (pl.W + 63) / 64), dim3(256), 0, st, (const uint8_t *)base + pl.o_tr, q.tr_off + first,
+                         in.tr_off[0], cnt, pl.W, (u32)IPAP_MAX_TRANSCRIPT, (u64 *)(base + pl.o_T));
+      hipLaunchKernelGGL(ipad::k_ipap_roles, dim3(IPAP_ROLES * ((cnt + 63) / 64)), dim3(64), (size_t)k * 9 * 64 * 4, st, q);
+    }
+    const uint64_t pairs_all = P * pl.pairs;
+    hipLaunchKernelGGL(ipad::k_ipap_finish, dim3((u32)((pairs_all + 255) / 256)), dim3(256), 0, st, q, pl.pairs, d_expts, (uint8_t *)base + pl.o_status);
+  }
+  HIPCHK(ctx, hipGetLastError());
+  return BPMI_OK;
+}
+
+int bpmi_ipa_batch_prepare_dev(bpmi_ctx *ctx, uint32_t k, int protocol, uint64_t n_proofs, const uint8_t *ab, const uint8_t *xs, const uint8_t *LR,
+                               const uint8_t *transcripts, const uint64_t *tr_off, const uint32_t *start, const uint8_t *u, const uint8_t *P, const uint8_t *c,
+                               const uint8_t *head, const uint8_t *weights, const uint8_t *seed, void *d_records, void *d_extra_pts, void *d_extra_scalars,
+                               uint8_t *status) {
+  static const char *const fn = "bpmi_ipa_batch_prepare_dev";
+  if (!ctx) return BPMI_E_ARG;
+  if (n_proofs == 0) return BPMI_OK;
+  if (!d_records || !d_extra_pts || !d_extra_scalars || !status) return fail(ctx, BPMI_E_ARG, std::string(fn) + ": null argument");
+  const IpaPackedIn in = ipap_in(ab, xs, LR, transcripts, tr_off, start, u, P, c, head, weights, seed);
+  const IpapPlan pl = ipa_packed_plan(*ctx, k, protocol, n_proofs, in, 0);
+  if (pl.err) return fail(ctx, pl.err, std::string(fn) + ": " + pl.msg);
+  PointCheck pc(ctx, fn, ctx->stream, ctx->opt_validate >= 1);
+  int rc = protocol == 1 ? pc.host(u, 1, "u") : BPMI_OK;
+  if (rc) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  rc = ensure_stage_in(ctx, pl.total_bytes + 512);
+  if (rc) return rc;
+  rc = ipap_run(ctx, pl, in, (u32 *)d_records, (u32 *)d_extra_pts, (u32 *)d_extra_scalars);
+  if (rc) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(status, (char *)ctx->stage_in + pl.o_status, n_proofs, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return BPMI_OK;
+}
+
+int bpmi_ipa_verify_batch_packed_dev(bpmi_ctx *ctx, const void *d_g, const void *d_h, const void *d_hscale, uint64_t n, int protocol, uint64_t n_proofs,
+                                     const uint8_t *ab, const uint8_t *xs, const uint8_t *LR, const uint8_t *transcripts, const uint64_t *tr_off,
+                                     const uint32_t *start, const uint8_t *u, const uint8_t *P, const uint8_t *c, const uint8_t *head, const uint8_t *weights,
+                                     const uint8_t *seed, uint8_t out[64], uint8_t *status) {
+  static const char *const fn = "bpmi_ipa_verify_batch_packed_dev";
+  if (!ctx) return BPMI_E_ARG;
+  if (!out) return fail(ctx, BPMI_E_ARG, std::string(fn) + ": null argument");
+  if (n_proofs == 0) { memset(out, 0, 64); return BPMI_OK; }
+  if (!d_g || !d_h || !status) return fail(ctx, BPMI_E_ARG, std::string(fn) + ": null argument");
+  u32 k;
+  if (!log2_exact(n, k) || k > IPAB_K_MAX) return fail(ctx, BPMI_E_ARG, std::string(fn) + ": n must be 2^k, k <= 22");
+  const IpaPackedIn in = ipap_in(ab, xs, LR, transcripts, tr_off, start, u, P, c, head, weights, seed);
+  const IpapPlan pl = ipa_packed_plan(*ctx, k, protocol, n_proofs, in, d_hscale ? 1 : 0);
+  if (pl.err) return fail(ctx, pl.err, std::string(fn) + ": " + pl.msg);
+  // the proofs' points are the preparation's to check (status bit 1); the shared u of Protocol 1 here, the generators at level 2
+  // by a kernel whose verdict is read after the MSM's own synchronisation; a refused call leaves 0xFF.. in `out`
+  PointCheck pc(ctx, fn, ctx->stream, ctx->opt_validate >= 1);
+  int rc = protocol == 1 ? pc.host(u, 1, "u") : BPMI_OK;
+  if (rc) { memset(out, 0xFF, 64); return rc; }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  rc = ensure_stage_in(ctx, pl.total_bytes + 512);
+  if (rc) return rc;
+  char *base = (char *)ctx->stage_in;
+  const IpabPlan &bp = pl.base;
+  rc = ipap_run(ctx, pl, in, (u32 *)(base + bp.o_rec), (u32 *)(base + bp.o_expt), (u32 *)(base + bp.o_exsc));
+  if (rc) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(status, base + pl.o_status, n_proofs, hipMemcpyDeviceToHost, ctx->stream));
+  rc = ipab_svector_launches(ctx, bp, d_hscale);
+  if (rc) return rc;
+  Segs s = segs_init();
+  s.pts[0] = (const u32 *)d_g; s.sc[0] = (const u32 *)(base + bp.o_sa); s.n[0] = (u32)n;
+  s.pts[1] = (const u32 *)d_h; s.sc[1] = (const u32 *)(base + bp.o_sb); s.n[1] = (u32)n;
+  s.pts[2] = (const u32 *)(base + bp.o_expt); s.sc[2] = (const u32 *)(base + bp.o_exsc); s.n[2] = (u32)bp.n_extra;
+  s.total = (u32)bp.msm_pairs;
+  if (ctx->opt_validate >= 2) { pc.queue(d_g, n, "d_g"); pc.queue(d_h, n, "d_h"); }
+  rc = pc.fetch();
+  if (rc) return rc;
+  rc = msm_run(ctx, s, out);                    // one MSM over the three segments, sliced as any large MSM is (msm_host.hpp)
+  if (rc) return rc;
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  rc = pc.verdict();
+  if (rc) memset(out, 0xFF, 64);
+  return rc;
+}
+
+}  // extern "C"

@@ -296,6 +296,31 @@ class Engine:
                                                     xs, xinvs, k, a, b, weights, extra_pts, extra_scalars, n_extra, out))
         return out.raw
 
+    # ---- packed inner-product proofs (what bpmi_ipa_prove_batch writes) ----
+    def ipa_batch_prepare_dev(self, k, protocol, count, ab, xs, lr, transcripts, starts, u, P, c=None, head=None, weights=None, seed=None):
+        """(records, extra_pts, extra_scalars, status) of bpmi_ipa_batch_prepare_dev as bytes: the per-proof preparation of the packed
+        batch verifier by the device kernels; argument forms as ipa_batch_prepare_host."""
+        pairs = count * (2 * k + (4 if protocol == 1 else 2))
+        d_rec, d_pts, d_sc = self.alloc(max((64 * k + 96) * count, 16)), self.alloc(max(64 * pairs, 16)), self.alloc(max(32 * pairs, 16))
+        status = ctypes.create_string_buffer(max(count, 1))
+        try:
+            self._ck(self.lib.bpmi_ipa_batch_prepare_dev(self.ctx, k, protocol, count, *packed_proof_args(count, ab, xs, lr, transcripts, starts, u, P, c, head),
+                                                         weights, seed, d_rec.ptr, d_pts.ptr, d_sc.ptr, ctypes.cast(status, ctypes.c_void_p)))
+            return d_rec.download((64 * k + 96) * count), d_pts.download(64 * pairs), d_sc.download(32 * pairs), status.raw[:count]
+        finally:
+            for d in (d_rec, d_pts, d_sc):
+                d.free()
+
+    def ipa_verify_batch_packed_dev(self, d_g, d_h, n, protocol, count, ab, xs, lr, transcripts, starts, u, P, c=None, head=None, weights=None, seed=None,
+                                    d_hscale=None):
+        """(out, status) of bpmi_ipa_verify_batch_packed_dev: the 64-byte value of the weighted combination over the unflagged proofs
+        (identity = all of them verify) and one status byte per proof (0 = passed the byte-level and on-curve checks)."""
+        out, status = ctypes.create_string_buffer(64), ctypes.create_string_buffer(max(count, 1))
+        self._ck(self.lib.bpmi_ipa_verify_batch_packed_dev(self.ctx, _ptr(d_g), _ptr(d_h), None if d_hscale is None else _ptr(d_hscale), n, protocol, count,
+                                                           *packed_proof_args(count, ab, xs, lr, transcripts, starts, u, P, c, head), weights, seed,
+                                                           ctypes.cast(out, ctypes.c_void_p), ctypes.cast(status, ctypes.c_void_p)))
+        return out.raw, status.raw[:count]
+
     # ---- IPA prover state ----
     def ipa_create(self, g, h, a, b, n, u, h_scale=None):
         st = ctypes.c_void_p()
@@ -404,6 +429,39 @@ def _pack_messages(msgs, offsets):
 
 def sc_bytes(k):
     return (int(k) % Q).to_bytes(32, "little")
+
+
+def packed_proof_args(count, ab, xs, lr, transcripts, starts, u, P, c=None, head=None):
+    """The packed-proof arguments of the bpmi_ipa_batch_prepare family (include/bpmi.h), in its order: ab, xs, LR, transcripts,
+    tr_off, start, u, P, c, head.  transcripts: a list of `count` byte strings, or (joined bytes, count + 1 offsets); starts: None
+    or `count` integers; empty xs / lr / c / head go as NULL.  The C arrays are kept alive by the returned tuple."""
+    if isinstance(transcripts, tuple):
+        joined, offs = transcripts
+        tr_off = offs if isinstance(offs, ctypes.Array) else (ctypes.c_uint64 * len(offs))(*offs)
+        joined = bytes(joined)
+    else:
+        joined, tr_off, _ = _pack_messages(list(transcripts), None)
+    if len(tr_off) != count + 1:
+        raise ValueError("one transcript per proof")
+    start = None if starts is None else (ctypes.c_uint32 * count)(*starts)
+    opt = lambda b: bytes(b) if b else None
+    return (bytes(ab), opt(xs), opt(lr), joined, tr_off, start, bytes(u), bytes(P), opt(c), opt(head))
+
+
+def ipa_batch_prepare_host(k, protocol, count, ab, xs, lr, transcripts, starts, u, P, c=None, head=None, weights=None, seed=None, threads=4):
+    """(records, extra_pts, extra_scalars, status) of bpmi_ipa_batch_prepare as bytes: the per-proof preparation of the packed batch
+    verifier in native HOST code (no GPU, no Engine).  Argument forms: packed_proof_args; weights: packed scalars (1 per proof under
+    Protocol 2, 3 under Protocol 1) or None with a 32-byte seed."""
+    lib = _native.load()
+    pairs = count * (2 * k + (4 if protocol == 1 else 2))
+    rec, pts, sc = (ctypes.create_string_buffer(max(nb, 1)) for nb in ((64 * k + 96) * count, 64 * pairs, 32 * pairs))
+    status = ctypes.create_string_buffer(max(count, 1))
+    vp = lambda b: ctypes.cast(b, ctypes.c_void_p)
+    rc = lib.bpmi_ipa_batch_prepare(k, protocol, count, *packed_proof_args(count, ab, xs, lr, transcripts, starts, u, P, c, head), weights, seed, threads,
+                                    vp(rec), vp(pts), vp(sc), vp(status))
+    if rc != 0:
+        raise EngineError("libbpmi error %d: %s" % (rc, lib.bpmi_last_error(None).decode()))
+    return rec.raw[: (64 * k + 96) * count], pts.raw[: 64 * pairs], sc.raw[: 32 * pairs], status.raw[:count]
 
 
 _default = None

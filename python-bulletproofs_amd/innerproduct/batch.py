@@ -6,7 +6,12 @@ Verifier2's check is one point equation per proof.  Multiplied by a random weigh
 all proofs collapse to 2n pairs -- their scalars are sums of weighted s-vectors, computed on the device -- so B proofs cost
 one MSM of 2n + B (2 log n + 2) pairs instead of B MSMs of 2n.  The weights MUST be unpredictable to whoever made the
 proofs: two invalid proofs whose errors are e and -e pass `verify(weights=[1, 1])`, and with any known weights a pair of
-errors can be scaled to cancel.  `verify()` draws them from `secrets`."""
+errors can be scaled to cancel.  `verify()` draws them from `secrets`.
+
+Two ways in.  Proof OBJECTS: `add` / `add_proof1` re-derive each transcript in Python and `verify()` runs the MSM.  PACKED proofs --
+the arrays BatchInnerProductProver.prove2_packed / prove1_packed return: `verify_packed2` / `verify_packed1` hand them to ONE native
+call (bpmi_ipa_verify_batch_packed_dev) that re-hashes, compares, inverts and weights every proof on the device, one lane per proof,
+and runs the same MSM; the weights come from a fresh 32-byte seed per call, and the note above applies unchanged."""
 import secrets
 
 from .. import engine as _engine
@@ -15,6 +20,7 @@ from ..utils.utils import mod_hash
 from .inner_product_verifier import Verifier2
 
 Q = secp256k1.q
+CALL_MAX = 1 << 16             # proofs per native call (IPAB_PROOFS_MAX, csrc/ipa_batch_plan_host.hpp)
 
 
 def locate_by_bisection(count, subset_is_valid):
@@ -176,6 +182,109 @@ class BatchInnerProductVerifier:
         bad = [i for i, it in enumerate(self._items) if not it.valid]
         found = locate_by_bisection(len(good), lambda sub: self._probe([good[j] for j in sub], [self._weight() for _ in sub]))
         return sorted(bad + [good[j] for j in found])
+
+
+    # ---- packed proofs: what BatchInnerProductProver.prove2_packed / prove1_packed return ---------------------------------------
+    # The whole verification is native (bpmi_ipa_verify_batch_packed_dev; csrc/ipa_packed_kernels.hpp): the transcripts are re-hashed,
+    # the items compared, the challenges inverted and the weighted scalars formed on the device, one lane per proof, and the batch
+    # is the same one MSM.  Nothing is queued: a call verifies what it is given.  Measured (profiles/r12_ipa_verify_packed.txt): 36-60x
+    # faster than add() + verify() over 1 024 proofs of 64 .. 1 024 elements, 2.1x at 16 proofs of 64; SLOWER at one proof (0.39 ms
+    # against 0.22) and at three proofs of 4 elements (0.31 against 0.24): three launches of single-wave chains and the uploads are
+    # its floor, so add() + verify() stays the right path below a handful of proofs.
+    def _packed_rows(self, protocol, u, Ps, cs, ab, xs, lr, head, transcripts, starts):
+        to_bytes = lambda v: bytes(v) if isinstance(v, (bytes, bytearray, memoryview)) else pack_points(v)
+        count = len(transcripts)
+        rows = {"ab": bytes(ab), "xs": bytes(xs), "lr": bytes(lr), "P": to_bytes(Ps), "trs": list(transcripts),
+                "starts": None if starts is None else [int(s) for s in starts]}
+        if protocol == 1:
+            rows["u"] = u if isinstance(u, (bytes, bytearray)) else u.to_le64()
+            rows["c"] = bytes(cs) if isinstance(cs, (bytes, bytearray, memoryview)) else pack_scalars(cs, Q)
+            rows["head"] = bytes(head)
+        else:
+            rows["u"], rows["c"], rows["head"] = to_bytes(u), b"", b""
+        k = self.k
+        sizes = {"ab": 64, "xs": 32 * k, "lr": 128 * k, "P": 64, "c": 32 if protocol == 1 else 0, "head": 128 if protocol == 1 else 0}
+        if protocol == 2:
+            sizes["u"] = 64
+        for name, per in sizes.items():
+            if len(rows[name]) != per * count:
+                raise ValueError("%s: %d bytes per proof, one row per transcript" % (name, per))
+        if (protocol == 1 and len(rows["u"]) != 64) or (rows["starts"] is not None and len(rows["starts"]) != count):
+            raise ValueError("u is one point under Protocol 1; one start per proof")
+        return rows, sizes, count
+
+    def _packed_call(self, protocol, rows, sizes, idx, weights):
+        """(out, status) of one native call over the rows idx (a range or a sorted list; at most 2^16)."""
+        if isinstance(idx, range) and idx.step == 1:
+            cut = lambda name: rows[name][sizes[name] * idx.start: sizes[name] * idx.stop]
+        else:
+            cut = lambda name: b"".join(rows[name][sizes[name] * i: sizes[name] * (i + 1)] for i in idx)
+        u = rows["u"] if protocol == 1 else cut("u")
+        starts = None if rows["starts"] is None else [rows["starts"][i] for i in idx]
+        seed = None if weights is not None else secrets.token_bytes(32)
+        return self.engine.ipa_verify_batch_packed_dev(self._d[0], self._d[1], self.n, protocol, len(idx), cut("ab"), cut("xs"), cut("lr"),
+                                                       [rows["trs"][i] for i in idx], starts, u, cut("P"), cut("c"), cut("head"), weights, seed, self._d_scale)
+
+    def _weights_bytes(self, protocol, weights, count):
+        if weights is None:
+            return None
+        flat = [int(w) % Q for row in weights for w in (row if isinstance(row, (tuple, list)) else (row,))]
+        if len(flat) != (3 if protocol == 1 else 1) * count:
+            raise ValueError("one weight per proof under Protocol 2, three (w, r1, r2) under Protocol 1")
+        return pack_scalars(flat, Q)
+
+    def _verify_packed(self, protocol, rows, sizes, count, weights):
+        per = 32 * (3 if protocol == 1 else 1)
+        wb = self._weights_bytes(protocol, weights, count)
+        for lo in range(0, count, CALL_MAX):               # consecutive calls of at most 2^16 proofs; valid iff every call is
+            hi = min(lo + CALL_MAX, count)
+            out, status = self._packed_call(protocol, rows, sizes, range(lo, hi), None if wb is None else wb[per * lo: per * hi])
+            if out != bytes(64) or status != bytes(hi - lo):
+                return False
+        return True
+
+    def _locate_packed(self, protocol, rows, sizes, count):
+        flagged = []
+        for lo in range(0, count, CALL_MAX):
+            hi = min(lo + CALL_MAX, count)
+            _, status = self._packed_call(protocol, rows, sizes, range(lo, hi), None)
+            flagged += [lo + i for i, s in enumerate(status) if s]
+        marked = set(flagged)
+        rest = [i for i in range(count) if i not in marked]
+
+        def probe(sub):
+            for lo in range(0, len(sub), CALL_MAX):
+                out, status = self._packed_call(protocol, rows, sizes, [rest[j] for j in sub[lo: lo + CALL_MAX]], None)
+                if out != bytes(64) or any(status):
+                    return False
+            return True
+        return sorted(flagged + [rest[j] for j in locate_by_bisection(len(rest), probe)])
+
+    def verify_packed2(self, us, Ps, ab, xs, lr, transcripts, starts=None, weights=None):
+        """True iff every Protocol-2 proof of the packed batch (ab, xs, lr, transcripts: what prove2_packed returns) is valid for its
+        statement (us[i], Ps[i]) -- points or packed bytes, 64 per proof.  starts: Proof2.start_transcript per proof (None: 1, the
+        empty prefix).  Random weights come from a fresh 32-byte seed of `secrets` per native call (the soundness note of this
+        module applies unchanged); weights: one integer per proof instead, for tests.  A batch above 2^16 proofs runs as consecutive
+        calls."""
+        rows, sizes, count = self._packed_rows(2, us, Ps, None, ab, xs, lr, None, transcripts, starts)
+        return self._verify_packed(2, rows, sizes, count, weights)
+
+    def verify_packed1(self, u, Ps, cs, ab, xs, lr, head, transcripts, weights=None):
+        """True iff every Protocol-1 proof of the packed batch (ab, xs, lr, head, transcripts: what prove1_packed returns) is valid
+        for its statement (u, Ps[i], cs[i]).  weights: three integers (w, r1, r2) per proof instead of the random ones, for tests."""
+        rows, sizes, count = self._packed_rows(1, u, Ps, cs, ab, xs, lr, head, transcripts, None)
+        return self._verify_packed(1, rows, sizes, count, weights)
+
+    def locate_packed2(self, us, Ps, ab, xs, lr, transcripts, starts=None):
+        """The sorted indices of the invalid proofs of a packed Protocol-2 batch: those the status bytes flag, and the rest found by
+        locate_by_bisection, every probe one native call over the gathered rows of the subset under fresh weights."""
+        rows, sizes, count = self._packed_rows(2, us, Ps, None, ab, xs, lr, None, transcripts, starts)
+        return self._locate_packed(2, rows, sizes, count)
+
+    def locate_packed1(self, u, Ps, cs, ab, xs, lr, head, transcripts):
+        """locate_packed2 for a packed Protocol-1 batch."""
+        rows, sizes, count = self._packed_rows(1, u, Ps, cs, ab, xs, lr, head, transcripts, None)
+        return self._locate_packed(1, rows, sizes, count)
 
 
 def batch_verify_inner_products(g, h, statements, h_scale=None, engine=None, rng=None):
