@@ -537,6 +537,32 @@ int bpmi_rp_batch_verify_dev(bpmi_ctx *ctx, uint32_t n_gens, uint32_t values_per
 int bpmi_rp_batch_group_values_dev(bpmi_ctx *ctx, uint32_t n_gens, uint32_t values_per_proof, uint64_t n_proofs, const uint8_t *blobs, uint64_t blobs_len,
                                    const uint64_t *blob_off, const uint8_t *weights, const uint8_t *seed, const uint8_t *v_points, const void *d_gens,
                                    void *d_points, void *d_scalars, uint64_t group, uint8_t *values, uint8_t *status);
+/* Range proofs of DIFFERENT sizes in one call and ONE MSM (replaces a loop of RangeVerifier.verify / AggregRangeVerifier.verify over
+ * proofs of different sizes: src/rangeproofs/rangeproof_verifier.py:55-99, src/rangeproofs/rangeproof_aggreg_verifier.py:55-108).  A CLASS is a run of proofs with the same (n_gens, values_per_proof) and one wire format; class c
+ * uses gs[0..n_c) and hs[0..n_c) of the one list g, h, u, gs[0..N), hs[0..N), N = n_gens_max >= every class's n_gens (what
+ * AggregNIRangeProver proofs of m values over the first 64 m generators are).  Every equation of every proof is linear in the generators,
+ * so the classes' shared coefficients are summed prefix by prefix and the whole call is one combination.  Proofs are numbered CLASS-MAJOR
+ * over the whole call (class 0's first): that global index selects a proof's weights and is what *first_bad reports.
+ *   classes   n_classes (1 .. 64) of bpmi_rp_class: blobs / blobs_len / blob_off as for bpmi_rp_batch_verify_dev (classes may differ in wire
+ *             format from each other), v_points HOST n_proofs x values_per_proof x 64 B
+ *   weights   4 per proof by GLOBAL index, or NULL with a seed: proof i takes SHA-256(seed || LE64(i) || t), i the GLOBAL index
+ *   d_gens    DEVICE (3 + 2 n_gens_max) x 64 B: g, h, u, gs[0..N), hs[0..N)
+ *   d_points / d_scalars  DEVICE scratch for sum_c n_proofs_c (m_c + 6 + 2 k_c) pairs: the classes' blocks back to back, each laid out as
+ *             the single-class call lays out its one block ([commitments | proof points])
+ * out = the 64-byte value of the ONE combination over [shared generators | every class's commitments and proof points]: the identity
+ * exactly when every equation of every proof holds.  *first_bad = the smallest global index of a proof that fails a byte-level check or has
+ * an invalid point, or -1; when it is >= 0 `out` means nothing.  A well-formed proof of another wire format at a class's first flagged
+ * index is BPMI_E_ARG ("mixed wire formats", naming the class).  Argument errors (BPMI_E_ARG, decided before anything is read, allocated
+ * or uploaded): a null argument, n_classes outside [1, 64], a class the single-class call refuses or with n_gens > n_gens_max (the message
+ * names the class), more than 2^23 points in the MSM.  A commitment that is not a point of the curve is refused with its index among the
+ * call's commitments, class-major.  One call at a time per ctx. */
+typedef struct bpmi_rp_class {
+  uint32_t n_gens, values_per_proof; uint64_t n_proofs;
+  const uint8_t *blobs; uint64_t blobs_len; const uint64_t *blob_off;
+  const uint8_t *v_points;
+} bpmi_rp_class;
+int bpmi_rp_batch_verify_mixed_dev(bpmi_ctx *ctx, uint32_t n_classes, const bpmi_rp_class *classes, uint32_t n_gens_max, const uint8_t *weights,
+                                   const uint8_t *seed, const void *d_gens, void *d_points, void *d_scalars, uint8_t out[64], int64_t *first_bad);
 /* ---- a BATCH of single-value range proofs, proved on the device in one call (csrc/rp_prove_kernels.hpp, rp_prove_host.hpp) -------------
  * Replaces a LOOP of NIRangeProver(v, n, g, h, gs, hs, gamma, u, group, seed).prove() (/root/reference/src/rangeproofs/
  * rangeproof_prover.py:35-91) with NIProver.prove / FastNIProver2.prove inside (/root/reference/src/innerproduct/

@@ -71,6 +71,7 @@ SIGNATURES = {
     "bpmi_rp_batch_prepare_dev": (_i, [_vp, ctypes.c_uint32, ctypes.c_uint32, _u64, _vp, _u64, _vp, _cp, _cp, _vp, _vp, _vp, _cp, _vp]),
     "bpmi_rp_batch_verify_dev": (_i, [_vp, ctypes.c_uint32, ctypes.c_uint32, _u64, _vp, _u64, _vp, _cp, _cp, _vp, _vp, _vp, _vp, _cp, _vp]),      # (v_points: bytes or a page-locked address)
     "bpmi_rp_batch_group_values_dev": (_i, [_vp, ctypes.c_uint32, ctypes.c_uint32, _u64, _vp, _u64, _vp, _cp, _cp, _vp, _vp, _vp, _vp, _u64, _vp, _vp]),
+    "bpmi_rp_batch_verify_mixed_dev": (_i, [_vp, ctypes.c_uint32, _vp, ctypes.c_uint32, _cp, _cp, _vp, _vp, _vp, _cp, _vp]),      # (classes: an array of RpClass)
     "bpmi_rp_prover_create": (_i, [_vp, ctypes.c_uint32, _cp, _cp, _cp, _cp, _cp, ctypes.POINTER(_vp)]),
     "bpmi_rp_prover_create_aggregated": (_i, [_vp, ctypes.c_uint32, ctypes.c_uint32, _cp, _cp, _cp, _cp, _cp, ctypes.POINTER(_vp)]),
     "bpmi_rp_prover_destroy": (None, [_vp]),
@@ -101,6 +102,13 @@ SIGNATURES = {
 }
 
 _lib = None
+
+
+class RpClass(ctypes.Structure):
+    """bpmi_rp_class (include/bpmi.h): one class of bpmi_rp_batch_verify_mixed_dev.  The pointers are plain addresses: whoever fills the
+    structure keeps the objects behind them alive for the call."""
+    _fields_ = [("n_gens", ctypes.c_uint32), ("values_per_proof", ctypes.c_uint32), ("n_proofs", ctypes.c_uint64), ("blobs", ctypes.c_void_p),
+                ("blobs_len", ctypes.c_uint64), ("blob_off", ctypes.c_void_p), ("v_points", ctypes.c_void_p)]
 
 
 class NativeLibraryMissing(RuntimeError):

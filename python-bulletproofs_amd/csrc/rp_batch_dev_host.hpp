@@ -98,17 +98,20 @@ struct RpRun {
   const uint64_t *blob_off;
   void *d_v_scalars, *d_pt_scalars, *d_points;
   RpGroups *G;               // nullptr: the batch as one
-  char *din, *buf;           // ctx->stage_in, ctx->rp_buf
+  char *din, *buf;           // ctx->stage_in, ctx->rp_buf (a class of a mixed batch: its own regions inside them)
+  unsigned long long *bad = nullptr;      // a class of a mixed batch: the call's ONE bad word, set up by the caller, and ...
+  uint64_t gbase = 0;                     // ... the global index of the class's proof 0 (rp_mixed_dev_host.hpp); nullptr / 0: a batch of its own
   u32 *d_contrib() const { return (u32 *)(buf + pl.contrib.off); }
   u32 *d_shared() const { return (u32 *)(buf + pl.shared.off); }
-  unsigned long long *d_bad() const { return (unsigned long long *)(buf + pl.o_bad); }
+  unsigned long long *d_bad() const { return bad ? bad : (unsigned long long *)(buf + pl.o_bad); }
   u64 *d_T() const { return (u64 *)(buf + pl.T.off); }
   u32 *d_lens() const { return pl.v2 ? (u32 *)(buf + pl.lens.off) : nullptr; }
 };
 // A batch is read in the wire format of its FIRST proof.  A well-formed proof of the OTHER format inside it is not a forged proof: the
 // device paths report it as an argument error ("mixed wire formats"), not as a verdict -- a verifier must be able to tell a
 // sender's mix-up from an attack (the host path, bpmi_rp_batch_prepare, takes the formats proof by proof).
-static int rp_mixed_formats(bpmi_ctx *ctx, const uint8_t *blobs, uint64_t blobs_len, const uint64_t *blob_off, int64_t first_bad) {
+// cls: the class of a mixed batch the proof belongs to (first_bad counts inside it), named in the message; -1: a batch of its own.
+static int rp_mixed_formats(bpmi_ctx *ctx, const uint8_t *blobs, uint64_t blobs_len, const uint64_t *blob_off, int64_t first_bad, int cls = -1) {
   if (first_bad < 0) return BPMI_OK;
   const uint64_t a0 = blob_off[0], a = blob_off[first_bad], e = blob_off[first_bad + 1];
   if (a0 + 5 > blobs_len || e > blobs_len || e < a + 5) return BPMI_OK;
@@ -120,28 +123,33 @@ static int rp_mixed_formats(bpmi_ctx *ctx, const uint8_t *blobs, uint64_t blobs_
   rp::Parsed parsed;
   const bool well_formed = b[4] == '1' ? rp::parse_blob(parsed, b, len) : (len > 0 && rpw::v2_length(b, len) == len);
   if (well_formed)
-    return fail(ctx, BPMI_E_ARG, "mixed wire formats: proof " + std::to_string(first_bad) + " is format " + std::string(1, (char)b[4]) + " in a format-" +
-                                     std::string(1, (char)call) + " batch (one format per call; bpmi_rp_wire_v2_to_v1 converts)");
+    return fail(ctx, BPMI_E_ARG, "mixed wire formats: " + (cls < 0 ? std::string() : "class " + std::to_string(cls) + ", ") + "proof " + std::to_string(first_bad) +
+                                     " is format " + std::string(1, (char)b[4]) + " in a format-" + std::string(1, (char)call) +
+                                     " batch (one format per call; bpmi_rp_wire_v2_to_v1 converts)");
   return BPMI_OK;
 }
 
 // ---- the stages of rp_prepare_enqueue ------------------------------------------------------------------------------------------
 // the buffers and events a preparation needs; R.din / R.buf are set
-static int rp_ensure_buffers(bpmi_ctx *ctx, RpRun &R) {
-  int rc = ensure_stage_in(ctx, R.pl.stage_bytes);
+static int rp_ensure_sizes(bpmi_ctx *ctx, size_t stage_bytes, size_t pin_bytes, size_t need) {
+  int rc = ensure_stage_in(ctx, stage_bytes);
   if (rc) return rc;
   rc = ensure_lane(ctx, 1);
   if (rc) return rc;
-  rc = ensure_pin(ctx, R.pl.pin_bytes);
+  rc = ensure_pin(ctx, pin_bytes);
   if (rc) return rc;
   for (int c = 0; c < RP_UPLOAD_SLICES; c++)
     if (!ctx->ev_slice[c]) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->ev_slice[c], hipEventDisableTiming));
-  const size_t need = R.pl.need;
   if (need > ctx->rp_buf_bytes) {
     if (ctx->rp_buf) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(ctx->rp_buf)); ctx->rp_buf = nullptr; ctx->rp_buf_bytes = 0; }
     HIPCHK(ctx, hipMalloc(&ctx->rp_buf, need));
     ctx->rp_buf_bytes = need;
   }
+  return BPMI_OK;
+}
+static int rp_ensure_buffers(bpmi_ctx *ctx, RpRun &R) {
+  const int rc = rp_ensure_sizes(ctx, R.pl.stage_bytes, R.pl.pin_bytes, R.pl.need);
+  if (rc) return rc;
   R.din = (char *)ctx->stage_in; R.buf = (char *)ctx->rp_buf;
   if (RpGroups *G = R.G) {
     char *b = R.buf;
@@ -157,7 +165,7 @@ static void rp_queue_decode(bpmi_ctx *ctx, const RpRun &R, hipStream_t st, u32 g
   const u32 per = R.pl.per;
   const u64 npts = (u64)(g1 - g0) * per;
   hipLaunchKernelGGL(k_ec_decompress_wire, dim3((u32)((npts + 255) / 256)), dim3(256), 0, st, (const uint8_t *)R.din, (const u64 *)(R.din + R.pl.o_off) + g0,
-                     R.pl.k, g1 - g0, (u64)g0, (u32)RP_MAX_PROOF_BYTES, (u32 *)R.d_points + 16ull * per * g0, R.d_bad(), R.G ? R.G->d_ptflag + g0 : (uint8_t *)nullptr);
+                     R.pl.k, g1 - g0, R.gbase + g0, (u32)RP_MAX_PROOF_BYTES, (u32 *)R.d_points + 16ull * per * g0, R.d_bad(), R.G ? R.G->d_ptflag + g0 : (uint8_t *)nullptr);
 }
 // Offsets, weights, the cleared results, then the blobs in slices of whole proofs.  Under RP_DECODE_BESIDE the point decoding of a
 // slice starts on the second lane as soon as the slice has arrived and runs beside the upload of the next one and, for the last
@@ -175,7 +183,7 @@ static int rp_queue_uploads(bpmi_ctx *ctx, const RpRun &R) {
   HIPCHK(ctx, h2d(ctx, din + o_off, blob_off, 8 * ((size_t)P + 1), ctx->stream));
   if (weights) HIPCHK(ctx, h2d(ctx, din + o_w, weights, 128 * (size_t)P, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(d_shared, 0, out_row, ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync(d_bad, 0xFF, 8, ctx->stream));
+  if (!R.bad) HIPCHK(ctx, hipMemsetAsync(d_bad, 0xFF, 8, ctx->stream));      // (a mixed batch's one word is cleared once, in front of its first class)
   if (G) {
     HIPCHK(ctx, hipMemsetAsync(G->d_gsum, 0, 32 * (size_t)ncols * G->ngroups, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(G->d_ptflag, 0, P, ctx->stream));            // (before the slices' events: the second lane's decoding sets flags)
@@ -230,34 +238,46 @@ static int rp_queue_group_rows(bpmi_ctx *ctx, const RpRun &R, u32 base, u32 cnt)
                      G->group, gc.t0, gc.nt, gc.lpg, pl.ncols, G->d_gsum);
   return BPMI_OK;
 }
-// rows of at most pl.rows proofs: roles, elements, then the column sums of the batch or of its groups
-static int rp_queue_rows(bpmi_ctx *ctx, const RpRun &R, uint32_t n_gens) {
+// the kernels' parameters: what every row chunk of a preparation shares, then what the chunk of the proofs [base, base + cnt) adds
+static rpd::Params rp_params(bpmi_ctx *ctx, const RpRun &R, uint32_t n_gens) {
   const RpPlan &pl = R.pl;
-  const char *din = R.din;
   const uint8_t *seed = R.seed;
-  const u32 P = pl.P, lanes = pl.lanes;
-  u32 *d_contrib = R.d_contrib();
   rpd::Params q;
-  q.Tstride = P;
-  q.weights = R.weights ? (const uint8_t *)(din + pl.o_w) : nullptr;
+  memset(&q, 0, sizeof(q));
+  q.Tstride = pl.P;
+  q.weights = R.weights ? (const uint8_t *)(R.din + pl.o_w) : nullptr;
   for (int i = 0; i < 8; i++) q.seed[i] = seed ? ((u32)seed[4 * i] << 24) | ((u32)seed[4 * i + 1] << 16) | ((u32)seed[4 * i + 2] << 8) | seed[4 * i + 3] : 0;
-  q.n = n_gens; q.k = pl.k; q.m = pl.m; q.Pall = P; q.only_role = ctx->opt_rp_only_role;
-  q.contrib = d_contrib;
+  q.n = n_gens; q.k = pl.k; q.m = pl.m; q.Pall = pl.P; q.only_role = ctx->opt_rp_only_role;
+  q.contrib = R.d_contrib();
   q.prio = pl.rp_prio;
   q.ctx = (u32 *)(R.buf + pl.ctx.off);
   q.bad = R.d_bad();
+  q.gbase = R.gbase;
+  q.lanes = pl.lanes;
+  return q;
+}
+static void rp_params_rows(rpd::Params &q, const RpRun &R, u32 base, u32 cnt) {
+  const RpPlan &pl = R.pl;
+  q.off = (const u64 *)(R.din + pl.o_off) + base;
+  q.lens = pl.v2 ? R.d_lens() + base : nullptr;
+  q.T = R.d_T() + base;
+  q.P = cnt; q.first = base;
+  q.v_scalars = (u32 *)R.d_v_scalars + 8 * (size_t)base * pl.m;
+  q.pt_scalars = (u32 *)R.d_pt_scalars + 8 * (size_t)base * pl.per;
+  q.status = (uint8_t *)(R.din + pl.o_st) + base;
+}
+// rows of at most pl.rows proofs: roles, elements, then the column sums of the batch or of its groups
+static int rp_queue_rows(bpmi_ctx *ctx, const RpRun &R, uint32_t n_gens) {
+  const RpPlan &pl = R.pl;
+  const u32 P = pl.P, lanes = pl.lanes;
+  u32 *d_contrib = R.d_contrib();
+  rpd::Params q = rp_params(ctx, R, n_gens);
   rpd::ElemGeom eg;
   eg.el_log = pl.el_log;
   eg.ranges = pl.ranges;
   for (u32 base = 0; base < P; base += pl.rows) {
     const u32 cnt = std::min(pl.rows, P - base);
-    q.off = (const u64 *)(din + pl.o_off) + base;
-    q.lens = pl.v2 ? R.d_lens() + base : nullptr;
-    q.T = R.d_T() + base;
-    q.P = cnt; q.lanes = lanes; q.first = base;
-    q.v_scalars = (u32 *)R.d_v_scalars + 8 * (size_t)base * pl.m;
-    q.pt_scalars = (u32 *)R.d_pt_scalars + 8 * (size_t)base * pl.per;
-    q.status = (uint8_t *)(din + pl.o_st) + base;
+    rp_params_rows(q, R, base, cnt);
     {
       StageTimer t(ctx, ST_RPPREP);
       hipLaunchKernelGGL(rpd::k_rp_roles, dim3(RP_ROLES * ((cnt + lanes - 1) / lanes)), dim3(64), pl.lds_bytes, ctx->stream, q);

@@ -359,6 +359,8 @@ struct Params {
   uint8_t *status;           // [role * Pall + g] = verdict of a role (1 = passed); points at this launch's proof 0
   unsigned long long *bad;   // atomicMin of the failing proof indices (whole-batch numbering)
   u32 prio;                  // the preparation's kernels raise their waves' issue priority (option "rp_priority"; raise_priority, msm_kernels.hpp)
+  u64 gbase;                 // a class of a mixed batch (k_rp_roles_mixed): the call-wide index of the class's proof 0 -- added to the index a seed
+                             // weight is derived from and to the index written to `bad`; explicit weights and every array stay class-local.  0: one class
 };
 // context slots of one proof (9 loose limbs each)
 #define CTX_BASE_G 0u                          // w4 a prod x_d^-1
@@ -406,7 +408,7 @@ __device__ __forceinline__ sq weight_of(const Params &q, u32 g, u32 t) {
     for (int i = 0; i < 4; i++) { const u64 x = ld8_raw(src + 8 * i); ws.v[2 * i] = (u32)x; ws.v[2 * i + 1] = (u32)(x >> 32); }
     bpmi::sc_reduce_once(ws);
   } else {
-    ws = derive_weight(q.seed, q.first + g, t);
+    ws = derive_weight(q.seed, q.gbase + q.first + g, t);
   }
   return to_sq(ws);
 }
@@ -727,11 +729,12 @@ __device__ __forceinline__ bool role_scalars(const Params &q, u32 g, const Layou
 
 // Four waves per group of `lanes` proofs, one per ROLE (see the head of the file).  status[role * Pall + g] = verdict of a role.
 // (RP_ROLES, RP_MAX_PROOF_BYTES: shared_defs.hpp)
-__global__ void __launch_bounds__(64) k_rp_roles(Params q) {
+// (the body of block `blk` of the launch: k_rp_roles runs it for its own blocks, k_rp_roles_mixed for the blocks of a unit)
+__device__ __forceinline__ void rp_roles_block(const Params &q, u32 blk) {
   ::raise_priority(q.prio);
   if (threadIdx.x >= q.lanes) return;
-  const u32 role = blockIdx.x & (RP_ROLES - 1);
-  const u32 g = (blockIdx.x / RP_ROLES) * q.lanes + threadIdx.x;
+  const u32 role = blk & (RP_ROLES - 1);
+  const u32 g = (blk / RP_ROLES) * q.lanes + threadIdx.x;
   if (g >= q.P) return;
   if (q.only_role >= 0 && (u32)q.only_role != role) { q.status[(size_t)role * q.Pall + g] = 1; return; }
   BPtr blob;
@@ -746,8 +749,9 @@ __global__ void __launch_bounds__(64) k_rp_roles(Params q) {
     else ok = role_scalars(q, g, L);
   }
   q.status[(size_t)role * q.Pall + g] = ok ? 1 : 0;
-  if (!ok) atomicMin(q.bad, (unsigned long long)(q.first + g));
+  if (!ok) atomicMin(q.bad, (unsigned long long)(q.gbase + q.first + g));
 }
+__global__ void __launch_bounds__(64) k_rp_roles(Params q) { rp_roles_block(q, blockIdx.x); }
 
 
 #if defined(BPMI_ROLE_PROBE)
@@ -778,11 +782,11 @@ template __global__ void k_rp_role_probe<3>(Params);
 // side 0 (gs): cell 5 + i = w4 a s_i.  side 1 (hs): cell 5 + n + i = w4 b s_i^-1 y^-i - w2 z^(2+j) 2^(i % bits) y^-i, both
 // progressions walk the same tree.  A proof whose role 2 failed gets zeros (its context is not valid).
 struct ElemGeom { u32 el_log, ranges; };       // elements per lane = 2^el_log; ranges per side = n >> el_log
-__global__ void __launch_bounds__(64) k_rp_elements(Params q, ElemGeom eg) {
+__device__ __forceinline__ void rp_elements_block(const Params &q, const ElemGeom &eg, u32 blk) {
   ::raise_priority(q.prio);
   const u32 n = q.n, k = q.k;
   const u32 groups = (q.P + 63u) / 64u;
-  const u32 grp = blockIdx.x % groups, rs = blockIdx.x / groups;          // rs = side * ranges + range
+  const u32 grp = blk % groups, rs = blk / groups;          // rs = side * ranges + range
   const u32 side = rs / eg.ranges, range = rs % eg.ranges;
   const u32 g = grp * 64u + threadIdx.x;
   if (g >= q.P) return;
@@ -843,6 +847,33 @@ __global__ void __launch_bounds__(64) k_rp_elements(Params q, ElemGeom eg) {
     mq_inl(a6, a4, F1); mq_inl(b6, b4, G1); bpmi::sq_sub(d, a6, b6); cell_store(C, col0 + 6, d);
     mq_inl(v, a6, F0); mq_inl(w, b6, G0); bpmi::sq_sub(d, v, w); cell_store(C, col0 + 7, d);
   }
+}
+__global__ void __launch_bounds__(64) k_rp_elements(Params q, ElemGeom eg) { rp_elements_block(q, eg, blockIdx.x); }
+
+// ---- a MIXED batch (bpmi_rp_batch_verify_mixed_dev, rp_mixed_dev_host.hpp): classes of different (n_gens, values_per_proof) in one call.
+// The two chain kernels above are one wave per SIMD and latency-bound, and a class of a few hundred proofs fills a few percent of the
+// chip: queued class after class they would serialise as many chains as there are classes.  Here ONE launch runs the row chunk of every
+// class of a round: a device table of units {the class's Params, its ElemGeom, the unit's first block in either launch}, read with plain
+// loads at an index that depends on blockIdx alone (uniform per block), then the SAME per-lane bodies.  The dynamic LDS of the launch is
+// the largest of the round's classes (role 2's prefix products: (k + 1) x 9 x 64 words).
+struct MixedUnit { Params q; ElemGeom eg; u32 first_roles, first_elems; };      // blocks [first, next unit's first) of the launch are this unit's
+static_assert(sizeof(MixedUnit) <= RP_MIXED_UNIT_STRIDE, "the plan lays the unit table out in RP_MIXED_UNIT_STRIDE-byte slots (shared_defs.hpp)");
+__device__ __forceinline__ const MixedUnit *mixed_unit_at(const uint8_t *units, u32 i) { return (const MixedUnit *)(units + (size_t)RP_MIXED_UNIT_STRIDE * i); }
+// the unit whose blocks hold blockIdx.x: the last one with first <= blockIdx.x (at most 64 units per round; the firsts ascend from 0)
+__global__ void __launch_bounds__(64) k_rp_roles_mixed(const uint8_t *__restrict__ units, u32 n_units) {
+  u32 u = 0;
+  while (u + 1 < n_units && mixed_unit_at(units, u + 1)->first_roles <= blockIdx.x) u++;
+  const MixedUnit *mu = mixed_unit_at(units, u);
+  const Params q = mu->q;
+  rp_roles_block(q, blockIdx.x - mu->first_roles);
+}
+__global__ void __launch_bounds__(64) k_rp_elements_mixed(const uint8_t *__restrict__ units, u32 n_units) {
+  u32 u = 0;
+  while (u + 1 < n_units && mixed_unit_at(units, u + 1)->first_elems <= blockIdx.x) u++;
+  const MixedUnit *mu = mixed_unit_at(units, u);
+  const Params q = mu->q;
+  const ElemGeom eg = mu->eg;
+  rp_elements_block(q, eg, blockIdx.x - mu->first_elems);
 }
 
 // T[w * P + g] = bytes [8w, 8w + 8) of proof g for w < W, zero beyond the proof's end (or beyond RP_MAX_PROOF_BYTES).  64 x 64
@@ -1139,6 +1170,25 @@ __global__ void __launch_bounds__(256) k_rp_shared_scalars(const u32 *__restrict
     bpmi::sc_add(v, a, b);
   }
   ::store_words8(out + 8ull * i, v.v);
+}
+
+// The scalars of the merged shared generators g, h, u, gs[0..N), hs[0..N) of a mixed batch: out[j] = the sum mod q of the classes'
+// k_rp_shared_scalars results at the indices that map to j -- g, h, u to 0..2, class c's gs_i to 3 + i and its hs_i to 3 + N + i for
+// i < n_c (a class's constants are already folded into its own prefix).  One thread per j, the classes in order: no atomics.
+struct MergeArgs { const u32 *fin[RP_MIXED_MAX_CLASSES]; u32 n[RP_MIXED_MAX_CLASSES]; u32 n_classes, N; };
+__global__ void __launch_bounds__(256) k_rp_shared_merge(MergeArgs a, u32 *__restrict__ out) {
+  const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= 3 + 2 * a.N) return;
+  const u32 side = j >= 3 + a.N ? 1u : 0u, i = j < 3 ? 0u : (j - 3 - side * a.N);
+  sc sum = sc_small(0);
+  for (u32 c = 0; c < a.n_classes; c++) {
+    const u32 n = a.n[c];
+    if (j >= 3 && i >= n) continue;
+    sc v;
+    ::load_words8(v.v, a.fin[c] + 8ull * (j < 3 ? j : 3 + side * n + i));
+    bpmi::sc_add(sum, sum, v);
+  }
+  ::store_words8(out + 8ull * j, sum.v);
 }
 
 // ---- per-proof verdicts and per-GROUP sums (bpmi_rp_batch_group_values_dev) -----------------------------------------------------------

@@ -77,6 +77,8 @@ static inline Segs segs_init() {
 // array.  A 64-bit proof is 2.6 KB, the largest shape the format allows (k = 16) under 8 KB.
 #define RP_MAX_PROOF_BYTES 32768u
 #define CTX_SLOTS(k_, m_) (2u + 3u * (k_) + (m_))      // context slots of one proof (the CTX_* indices, rp_batch_kernels.hpp)
+#define RP_MIXED_MAX_CLASSES 64   // classes of one mixed batch (bpmi_rp_batch_verify_mixed_dev)
+#define RP_MIXED_UNIT_STRIDE 256  // bytes of one slot of a mixed batch's unit table (rpd::MixedUnit, rp_batch_kernels.hpp)
 #define RP_UPLOAD_SLICES 4       // a batch of 4 096 proofs or more is uploaded in up to this many slices (ctx->ev_slice)
 
 // ---- options (bpmi_set_option, include/bpmi.h); bpmi_ctx inherits them, so ctx->opt_c is this opt_c ----------------------------

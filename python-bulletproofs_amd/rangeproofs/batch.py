@@ -236,6 +236,25 @@ class BatchRangeVerifier:
         self._raw_count += nsc
         self.count += count
 
+    def merge_prefix(self, st):
+        """Add the state() of a verifier over a PREFIX of this one's generators (same g, h, u; its gs / hs are the first len(c_gs) of
+        this verifier's): proofs of different sizes then verify as one MSM (rangeproofs.batch_mixed).  The state's constants stand
+        for a term on every generator of the PREFIX only, so they are folded into the prefix's coefficients before adding; this
+        verifier's own constants are untouched."""
+        c_g, c_h, c_u, gk, hk, c_gs, c_hs, pts, scs, nsc, count = st
+        n = len(c_gs)
+        assert n <= self.n and len(c_hs) == n and len(pts) == 64 * nsc and len(scs) == 32 * nsc
+        self.c_g = (self.c_g + c_g) % Q
+        self.c_h = (self.c_h + c_h) % Q
+        self.c_u = (self.c_u + c_u) % Q
+        for i in range(n):
+            self.c_gs[i] += c_gs[i] + gk
+            self.c_hs[i] += c_hs[i] + hk
+        self._raw_pts.append(pts)
+        self._raw_scs.append(scs)
+        self._raw_count += nsc
+        self.count += count
+
     def start_workers(self, workers):
         """A pool of `workers` processes for add_wire (spawned, so they never inherit a GPU
         context; they do integer and hash work only)."""
