@@ -133,7 +133,7 @@ static void msm_queue_sort_lds(bpmi_ctx *ctx, hipStream_t st, const Segs &segs, 
   {
     StageTimer t(ctx, ST_SCATTER, st);
     const u32 TS = g.n >= (1u << 19) ? PT_MAX : 4096u;          // scalars per level-A tile: long runs once there are enough tiles
-    hipLaunchKernelGGL(k_partition, dim3((g.n + TS - 1) / TS, g.W), dim3(1024), 0, st, g, w.P, TS, w.coarse_off, w.coarse_cursor, w.dig16, w.negs, w.dig,
+    hipLaunchKernelGGL(k_partition, dim3((g.n + TS - 1) / TS, g.W), dim3(PT_THREADS), 0, st, g, w.P, TS, w.coarse_off, w.coarse_cursor, w.dig16, w.negs, w.dig,
                        w.hist, w.coarse_hist + PART_MAX);
     // level B: one block per partition; writes off[0..G), the chunk keys and the sorted entries
     // (heavy partitions: counted and scattered by the tile kernels, which return at once when there are none)
