@@ -280,8 +280,45 @@ int bpmi_msm_batch_dev(bpmi_ctx *ctx, uint32_t nseg, const void *const *d_pts, c
 int bpmi_msm_batch_dev_enqueue(bpmi_ctx *ctx, uint32_t nseg, const void *const *d_pts, const uint64_t *n, const void *const *d_scalars, uint64_t n_vec,
                                void *d_out);
 
+/* ---- fixed-base MSM: an object that owns a point set and a table of its multiples ------------------------------------
+ *   out = sum_{i < n_scalars} scalars[i] * P_i        over the object's points P_0 .. P_{n-1}, n_scalars <= n
+ * Replaces Pippenger.multiexp(gs, es) (src/pippenger/pippenger.py:22-61) and vector_commitment(gs, hs, a, b)
+ * (src/utils/commitments.py:13) where gs (gs + hs) is a list of generators that never changes: the object keeps
+ * T[r][i] = 2^(c Wv r) P_i for r < R, so the W windows of c bits of a scalar become entries for R table points in only
+ * Wv = ceil(W / R) windows -- as many bucket additions, and the bucket reduction and the tail over Wv windows instead of W.
+ *   bpmi_fixed_base_create[_dev]  pts: n x 64 bytes (HOST / DEVICE), copied: the caller may free them.  window_bits: 0 or 10 .. 16 (W =
+ *                           255 / window_bits + 1 uniform signed windows); rows: 0 or 1 .. W, Wv = ceil(W / rows), and the effective row
+ *                           count ceil(W / Wv) is what info reports.  rows = 1 keeps a copy of the points and runs as an ordinary MSM of the
+ *                           given width.  (0, 0): automatic, by the measured rule of csrc/msm_fixed_plan_host.hpp (one of the two 0: that
+ *                           one is chosen around the other); an explicit value is never overridden.  Refused with BPMI_E_ARG before
+ *                           anything is read or allocated, the message naming the bound: n = 0, n > BPMI_MAX_N, n x rows > 2^23 (the
+ *                           sort's packed entry holds a 23-bit pair index; automatic rows are lowered until it holds), window_bits or rows
+ *                           out of range, a NULL pointer.  A table that does not fit the device is BPMI_E_NOMEM.  The points are checked to be
+ *                           on the curve under "validate_points" (create at level >= 1, create_dev at level 2): BPMI_E_ARG names the
+ *                           first bad index.  The identity, equal and opposite points are legal.
+ *   bpmi_fixed_base_info    info[0] n, [1] window bits c, [2] windows W, [3] rows R (effective), [4] virtual windows Wv, [5] table bytes,
+ *                           [6] build time in microseconds, [7] 0.  c = W = Wv = 0 with R = 1: the automatic rule chose the ordinary MSM
+ *                           under the ctx's own options.
+ *   bpmi_fixed_base_table   count entries of row `row` from index `first` to HOST memory, 64 bytes each, affine and canonical, the identity
+ *                           64 zero bytes (tests, debugging)
+ *   bpmi_msm_fixed[_dev]    scalars: n_scalars x 32 bytes (HOST / DEVICE), any 256-bit values, reduced mod q on load; the missing n -
+ *                           n_scalars scalars count as 0 (n_scalars > n: BPMI_E_ARG); n_scalars = 0 gives the identity and runs no GPU work.
+ *                           The result is affine and canonical: the bytes of bpmi_msm_dev over the same points and zero-padded scalars.
+ *   bpmi_msm_fixed_dev_enqueue   the asynchronous form, finished by bpmi_msm_finish(ctx, slot, out) of the object's ctx.
+ * The object uses its ctx's lanes, workspace and pending slots exactly as bpmi_msm_dev / bpmi_msm_dev_enqueue do (the BPMI_E_STATE rules
+ * and "async_lanes" included; the scalars stay valid until `finish`).  One thread at a time per ctx; destroy the object before its ctx. */
+typedef struct bpmi_fixed_base bpmi_fixed_base;
+int bpmi_fixed_base_create(bpmi_ctx *ctx, const uint8_t *pts, uint64_t n, uint32_t window_bits, uint32_t rows, bpmi_fixed_base **out);
+int bpmi_fixed_base_create_dev(bpmi_ctx *ctx, const void *d_pts, uint64_t n, uint32_t window_bits, uint32_t rows, bpmi_fixed_base **out);
+void bpmi_fixed_base_destroy(bpmi_fixed_base *fx);
+int bpmi_fixed_base_info(const bpmi_fixed_base *fx, uint64_t info[8]);
+int bpmi_fixed_base_table(bpmi_fixed_base *fx, uint32_t row, uint64_t first, uint64_t count, uint8_t *out);
+int bpmi_msm_fixed(bpmi_fixed_base *fx, const uint8_t *scalars, uint64_t n_scalars, uint8_t out[64]);
+int bpmi_msm_fixed_dev(bpmi_fixed_base *fx, const void *d_scalars, uint64_t n_scalars, uint8_t out[64]);
+int bpmi_msm_fixed_dev_enqueue(bpmi_fixed_base *fx, int slot, const void *d_scalars, uint64_t n_scalars);
+
 /* ---- batched point operations ----------------------------------------------------
- * out[i] = scalars[i] * pts[i]       replaces `ModP * Point` / `int * Point`
+ * out[i] = scalars[i] * pts[i]      replaces `ModP * Point` / `int * Point`
  * (src/utils/utils.py:43-44), e.g. hsp[i] = y^-i * hs[i]
  * (src/rangeproofs/rangeproof_prover.py:77, rangeproof_verifier.py:72). */
 int bpmi_ec_mul_batch(bpmi_ctx *ctx, const uint8_t *pts, const uint8_t *scalars, uint64_t n, uint8_t *out);

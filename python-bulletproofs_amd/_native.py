@@ -46,6 +46,14 @@ SIGNATURES = {
     "bpmi_msm_batch": (_i, [_vp, _cp, _u64, _cp, _u64, _vp]),
     "bpmi_msm_batch_dev": (_i, [_vp, ctypes.c_uint32, _vp, _vp, _vp, _u64, _vp]),
     "bpmi_msm_batch_dev_enqueue": (_i, [_vp, ctypes.c_uint32, _vp, _vp, _vp, _u64, _vp]),
+    "bpmi_fixed_base_create": (_i, [_vp, _cp, _u64, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(_vp)]),
+    "bpmi_fixed_base_create_dev": (_i, [_vp, _vp, _u64, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(_vp)]),
+    "bpmi_fixed_base_destroy": (None, [_vp]),
+    "bpmi_fixed_base_info": (_i, [_vp, ctypes.POINTER(_u64)]),
+    "bpmi_fixed_base_table": (_i, [_vp, ctypes.c_uint32, _u64, _u64, _cp]),
+    "bpmi_msm_fixed": (_i, [_vp, _cp, _u64, _cp]),
+    "bpmi_msm_fixed_dev": (_i, [_vp, _vp, _u64, _cp]),
+    "bpmi_msm_fixed_dev_enqueue": (_i, [_vp, _i, _vp, _u64]),
     "bpmi_sc_dot": (_i, [_vp, _cp, _cp, _u64, _cp]),
     "bpmi_sc_dot_dev": (_i, [_vp, _vp, _vp, _u64, _cp]),
     "bpmi_sc_fold": (_i, [_vp, _cp, _cp, _cp, _cp, _u64, _cp]),

@@ -60,9 +60,11 @@ using namespace bpmi;
 #include "ipa_batch_plan_host.hpp"
 #include "ipa_packed_plan_host.hpp"
 #include "msm_batch_plan_host.hpp"
+#include "msm_fixed_plan_host.hpp"
 #include "context.hpp"
 #include "device_util.hpp"
 #include "msm_kernels.hpp"
+#include "msm_fixed_kernels.hpp"
 #include "fold_ops_host.hpp"
 #include "point_kernels.hpp"
 #include "point_check_host.hpp"
@@ -70,6 +72,7 @@ using namespace bpmi;
 #include "scalar_kernels.hpp"
 #include "host_tail.hpp"
 #include "msm_host.hpp"
+#include "msm_fixed_host.hpp"
 #include "rp_batch_host.hpp"
 #include "ipa_packed_host.hpp"
 #include "host_pool.hpp"
@@ -258,15 +261,22 @@ int bpmi_debug_msm_runs(bpmi_ctx *ctx, int lane, uint32_t state[3]) {
 // the ctx stream; finish waits for THAT MSM only and runs the host part of its tail.  Two slots, so the
 // host tail (and the caller's own work, e.g. the exchange of partial results) of MSM k overlaps the
 // kernels of MSM k + 1.
+static int msm_enqueue_async(bpmi_ctx *ctx, int slot, const Segs &s, const FixedBaseCall *fx);
 int bpmi_msm_dev_enqueue(bpmi_ctx *ctx, int slot, const void *d_pts, const void *d_scalars, uint64_t n) {
   if (!ctx || (n && (!d_pts || !d_scalars))) return ctx ? fail(ctx, BPMI_E_ARG, "null argument") : BPMI_E_ARG;
   if (slot < 0 || slot >= BPMI_LANES) return fail(ctx, BPMI_E_ARG, "slot must be 0, 1 or 2");
   if (n > (1ull << 23)) return fail(ctx, BPMI_E_ARG, "bpmi_msm_dev_enqueue takes at most 2^23 pairs (use bpmi_msm_dev)");
+  Segs s = segs_init();
+  s.pts[0] = (const u32 *)d_pts; s.sc[0] = (const u32 *)d_scalars; s.n[0] = (u32)n; s.total = (u32)n;
+  return msm_enqueue_async(ctx, slot, s, nullptr);
+}
+// the asynchronous enqueue behind bpmi_msm_dev_enqueue and bpmi_msm_fixed_dev_enqueue (fx: the fixed-base call, msm_fixed_host.hpp): the
+// slot's state rules, the lanes of "async_lanes" and their ordering, the chained mode -- one text for both
+static int msm_enqueue_async(bpmi_ctx *ctx, int slot, const Segs &s, const FixedBaseCall *fx) {
+  const uint64_t n = s.total;
   if (ctx->opt_split) return fail(ctx, BPMI_E_STATE, "option split is not available with the asynchronous entry points");
   if (ctx->pend[slot].async) return fail(ctx, BPMI_E_STATE, "an MSM is still pending in this slot (bpmi_msm_finish it first)");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  Segs s = segs_init();
-  s.pts[0] = (const u32 *)d_pts; s.sc[0] = (const u32 *)d_scalars; s.n[0] = (u32)n; s.total = (u32)n;
   // option async_lanes: slot 1 runs on the second lane (own stream + workspace), so the latency-bound tail stages of
   // one MSM (segmented scan, bucket reduction: few waves) overlap the throughput stages of the next one
   const int lane = ctx->opt_async_lanes ? slot : 0;
@@ -290,7 +300,7 @@ int bpmi_msm_dev_enqueue(bpmi_ctx *ctx, int slot, const void *d_pts, const void 
   MsmMode mode;
   mode.chained = ctx->opt_async_lanes != 0;
   mode.free_run = ctx->opt_accum_chain == 0;
-  rc = msm_enqueue(ctx, mode, lane, slot, s);
+  rc = fx ? fixed_base_enqueue(ctx, mode, lane, slot, *fx) : msm_enqueue(ctx, mode, lane, slot, s);
   if (rc == BPMI_OK) { ctx->pend[slot].async = true; ctx->pend[slot].async_empty = (n == 0); }
   return rc;
 }
@@ -354,6 +364,94 @@ int bpmi_msm2(bpmi_ctx *ctx, const uint8_t *pts0, const uint8_t *sc0, uint64_t n
   rc = pc.verdict();
   if (rc) { memset(out0, 0, 64); memset(out1, 0, 64); }
   return rc;
+}
+
+// ---- fixed-base MSM: an object that owns a point set and the table of its multiples (msm_fixed_plan_host.hpp, msm_fixed_host.hpp) ----
+// the argument checks of both create calls: BPMI_E_ARG before anything is read or allocated
+static int fixed_base_args(bpmi_ctx *ctx, const void *pts, uint64_t n, uint32_t window_bits, uint32_t rows, bpmi_fixed_base **out, FixedPlan &p) {
+  if (!ctx) return BPMI_E_ARG;
+  if (out) *out = nullptr;
+  if (!pts || !out) return fail(ctx, BPMI_E_ARG, "null argument");
+  p = fixed_plan(n, window_bits, rows);
+  if (p.err) return fail(ctx, p.err, std::string("bpmi_fixed_base_create: ") + p.msg);
+  return BPMI_OK;
+}
+int bpmi_fixed_base_create_dev(bpmi_ctx *ctx, const void *d_pts, uint64_t n, uint32_t window_bits, uint32_t rows, bpmi_fixed_base **out) {
+  FixedPlan p;
+  const int rc = fixed_base_args(ctx, d_pts, n, window_bits, rows, out, p);
+  if (rc) return rc;
+  return fixed_base_build(ctx, "bpmi_fixed_base_create_dev", d_pts, p, ctx->opt_validate >= 2, out);
+}
+int bpmi_fixed_base_create(bpmi_ctx *ctx, const uint8_t *pts, uint64_t n, uint32_t window_bits, uint32_t rows, bpmi_fixed_base **out) {
+  FixedPlan p;
+  int rc = fixed_base_args(ctx, pts, n, window_bits, rows, out, p);
+  if (rc) return rc;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  rc = ensure_stage_in(ctx, 64 * n + 512);
+  if (rc) return rc;
+  HIPCHK(ctx, h2d(ctx, ctx->stage_in, pts, 64 * n, ctx->stream));
+  return fixed_base_build(ctx, "bpmi_fixed_base_create", ctx->stage_in, p, ctx->opt_validate >= 1, out);
+}
+void bpmi_fixed_base_destroy(bpmi_fixed_base *fx) {
+  if (!fx) return;
+  (void)hipSetDevice(fx->ctx->device);
+  (void)sync_lanes(fx->ctx);                     // an MSM over the table may still be queued
+  if (fx->table) (void)hipFree(fx->table);
+  delete fx;
+}
+int bpmi_fixed_base_info(const bpmi_fixed_base *fx, uint64_t info[8]) {
+  if (!fx || !info) return BPMI_E_ARG;
+  const FixedPlan &p = fx->plan;
+  info[0] = p.n; info[1] = p.c; info[2] = p.W; info[3] = p.R; info[4] = p.Wv; info[5] = p.table_bytes; info[6] = (uint64_t)fx->build_us; info[7] = 0;
+  return BPMI_OK;
+}
+int bpmi_fixed_base_table(bpmi_fixed_base *fx, uint32_t row, uint64_t first, uint64_t count, uint8_t *out) {
+  if (!fx) return BPMI_E_ARG;
+  bpmi_ctx *ctx = fx->ctx;
+  if (count && !out) return fail(ctx, BPMI_E_ARG, "null argument");
+  if (row >= fx->plan.R || first > fx->plan.n || count > fx->plan.n - first) return fail(ctx, BPMI_E_ARG, "bpmi_fixed_base_table: row or range outside the table");
+  if (!count) return BPMI_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipMemcpyAsync(out, fx->table + 16ull * (fx->plan.n * row + first), 64 * count, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return BPMI_OK;
+}
+static int fixed_msm_args(bpmi_fixed_base *fx, const void *scalars, uint64_t n_scalars) {
+  if (!fx) return BPMI_E_ARG;
+  if (n_scalars && !scalars) return fail(fx->ctx, BPMI_E_ARG, "null argument");
+  if (n_scalars > fx->plan.n) return fail(fx->ctx, BPMI_E_ARG, "n_scalars exceeds the object's n points");
+  return BPMI_OK;
+}
+int bpmi_msm_fixed_dev(bpmi_fixed_base *fx, const void *d_scalars, uint64_t n_scalars, uint8_t out[64]) {
+  int rc = fixed_msm_args(fx, d_scalars, n_scalars);
+  if (rc) return rc;
+  bpmi_ctx *ctx = fx->ctx;
+  if (!out) return fail(ctx, BPMI_E_ARG, "null argument");
+  if (n_scalars == 0) { memset(out, 0, 64); return BPMI_OK; }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  return fixed_base_run(ctx, FixedBaseCall{fx, d_scalars, n_scalars}, out);
+}
+int bpmi_msm_fixed(bpmi_fixed_base *fx, const uint8_t *scalars, uint64_t n_scalars, uint8_t out[64]) {
+  int rc = fixed_msm_args(fx, scalars, n_scalars);
+  if (rc) return rc;
+  bpmi_ctx *ctx = fx->ctx;
+  if (!out) return fail(ctx, BPMI_E_ARG, "null argument");
+  if (n_scalars == 0) { memset(out, 0, 64); return BPMI_OK; }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  rc = ensure_stage_in(ctx, 32 * n_scalars + 512);
+  if (rc) return rc;
+  HIPCHK(ctx, h2d(ctx, ctx->stage_in, scalars, 32 * n_scalars, ctx->stream));
+  return fixed_base_run(ctx, FixedBaseCall{fx, ctx->stage_in, n_scalars}, out);
+}
+int bpmi_msm_fixed_dev_enqueue(bpmi_fixed_base *fx, int slot, const void *d_scalars, uint64_t n_scalars) {
+  const int rc = fixed_msm_args(fx, d_scalars, n_scalars);
+  if (rc) return rc;
+  bpmi_ctx *ctx = fx->ctx;
+  if (slot < 0 || slot >= BPMI_LANES) return fail(ctx, BPMI_E_ARG, "slot must be 0, 1 or 2");
+  const FixedBaseCall call = {fx, d_scalars, n_scalars};
+  Segs s = segs_init();
+  s.total = (u32)n_scalars;                      // (what the slot's bookkeeping reads: an MSM of no scalars leaves it empty)
+  return msm_enqueue_async(ctx, slot, s, &call);
 }
 
 // ---- batched point ops --------------------------------------------------------------------

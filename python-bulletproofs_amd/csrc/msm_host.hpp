@@ -108,23 +108,25 @@ static int msm_queue_small(bpmi_ctx *ctx, hipStream_t st, const bpmi_ctx::Pendin
   if (!ctx->opt_direct) HIPCHK(ctx, hipMemcpyAsync(pd.pin, w.E, 4ull * XYZZ_WORDS * g.W, hipMemcpyDeviceToHost, st));
   return BPMI_OK;
 }
-// sort path 2: the two-level LDS partition sort
-static void msm_queue_sort_lds(bpmi_ctx *ctx, hipStream_t st, const Segs &segs, const MsmGeom &g, const MsmWs &w) {
+// sort path 2: the two-level LDS partition sort.  `rec` (the fixed-base MSM, msm_fixed_kernels.hpp): the recoding is k_fixed_recode with
+// rec's arguments -- the real scalars into the codes of the virtual geometry g -- and the scan of the counts always its own launch
+static void msm_queue_sort_lds(bpmi_ctx *ctx, hipStream_t st, const Segs &segs, const MsmGeom &g, const MsmWs &w, const MsmRecode *rec = nullptr) {
   {
     StageTimer t(ctx, ST_DIGITS, st);
     // few blocks (every block ends with a flush of its 2048-bin LDS histogram), many threads: a thread recodes its scalars one after
     // the other and every one starts with a load, so the waves per SIMD are what hides that latency (512 blocks of 256 threads: 38 us at
     // n = 2^20, 256 blocks of 1024: 28.5; options "hist_threads" / "hist_blocks", tools/hist_sweep.py)
     const u32 ht = ctx->opt_hist_threads > 0 ? (u32)ctx->opt_hist_threads : 1024u;
-    const u32 hb = (u32)std::min<uint64_t>(((uint64_t)g.n + ht - 1) / ht, ctx->opt_hist_blocks > 0 ? (u32)ctx->opt_hist_blocks : 256u);
+    const u32 hb = (u32)std::min<uint64_t>(((uint64_t)(rec ? rec->real.n : g.n) + ht - 1) / ht, ctx->opt_hist_blocks > 0 ? (u32)ctx->opt_hist_blocks : 256u);
     // (round 5: the last block to flush runs the scan of the partition counts itself; ticket word behind the any_heavy flag and the
     // segmented scan's ticket, zeroed by the memset of msm_queue_sort)
     CoarseScanOut so = {nullptr, nullptr, nullptr, nullptr};
-    if (ctx->opt_histscan) { so.coarse_off = w.coarse_off; so.coarse_cursor = w.coarse_cursor; so.offG = w.off + g.G; so.ticket = w.coarse_hist + PART_MAX + 2; }
-    hipLaunchKernelGGL(k_coarse_hist, dim3(hb), dim3(ht), 0, st, segs, g, w.P, w.coarse_hist, w.dig16, w.negs, so);
+    if (ctx->opt_histscan && !rec) { so.coarse_off = w.coarse_off; so.coarse_cursor = w.coarse_cursor; so.offG = w.off + g.G; so.ticket = w.coarse_hist + PART_MAX + 2; }
+    if (rec) hipLaunchKernelGGL(k_fixed_recode, dim3(hb), dim3(ht), 0, st, rec->sc, rec->real, rec->n_scalars, rec->R, rec->Wv, g, w.P, w.coarse_hist, w.dig16, w.negs);
+    else hipLaunchKernelGGL(k_coarse_hist, dim3(hb), dim3(ht), 0, st, segs, g, w.P, w.coarse_hist, w.dig16, w.negs, so);
   }
   debug_sync(ctx, "ST_DIGITS", st);
-  if (!ctx->opt_histscan) {
+  if (!ctx->opt_histscan || rec) {
     StageTimer t(ctx, ST_SCAN, st);
     // exclusive scan of <= 2048 partition counts; total -> coarse_off[P] and off[G]
     hipLaunchKernelGGL(k_coarse_scan, dim3(1), dim3(1024), 0, st, w.coarse_hist, w.P, w.coarse_off, w.coarse_cursor, w.off + g.G);
@@ -176,7 +178,7 @@ static void msm_queue_sort_atomic(bpmi_ctx *ctx, hipStream_t st, const Segs &seg
   debug_sync(ctx, "ST_SCATTER", st);
 }
 // recoding .. sorted entries, the buckets cleared: everything of the bucket pipeline before the accumulation
-static int msm_queue_sort(bpmi_ctx *ctx, hipStream_t st, const Segs &segs, const MsmGeom &g, const MsmWs &w) {
+static int msm_queue_sort(bpmi_ctx *ctx, hipStream_t st, const Segs &segs, const MsmGeom &g, const MsmWs &w, const MsmRecode *rec = nullptr) {
   {
     StageTimer t(ctx, ST_MISC, st);
     if (w.P) HIPCHK(ctx, hipMemsetAsync(w.coarse_hist, 0, 4ull * COARSE_HIST_WORDS, st));      // (a multiple of 256 bytes: ONE fill kernel, not an aligned part and a tail)
@@ -186,7 +188,7 @@ static int msm_queue_sort(bpmi_ctx *ctx, hipStream_t st, const Segs &segs, const
     }
   }
   debug_sync(ctx, "ST_MISC", st);
-  if (w.P) msm_queue_sort_lds(ctx, st, segs, g, w);
+  if (w.P) msm_queue_sort_lds(ctx, st, segs, g, w, rec);
   else msm_queue_sort_atomic(ctx, st, segs, g, w);
   return BPMI_OK;
 }
@@ -291,14 +293,17 @@ static int msm_queue_tail(bpmi_ctx *ctx, hipStream_t st, const bpmi_ctx::Pending
 //   the SAME arguments queued on this lane (the plan is a function of the arguments: it is simply computed again).  A synchronous
 //   pair queues both sorts before either accumulation (msm_run_pair).  MSMs on the one-launch kernels or on GLV scalars have no
 //   sort to queue ahead: phase 1 does nothing for them and phase 2 everything.
-static int msm_enqueue(bpmi_ctx *ctx, const MsmMode &mode, int lane, int slot, const Segs &segs_in, u32 w0 = 0, u32 wcount = 0, int phase = 0) {
+//   rec: the fixed-base MSM (msm_fixed_host.hpp) -- segs_in are the table's virtual pairs, the plan is rec's virtual geometry and the recoding
+//   rec's kernel; whole MSMs in one phase, never replayed as a graph (the key of a captured sequence does not cover rec's arguments)
+static int msm_enqueue(bpmi_ctx *ctx, const MsmMode &mode, int lane, int slot, const Segs &segs_in, u32 w0 = 0, u32 wcount = 0, int phase = 0,
+                       const MsmRecode *rec = nullptr) {
   Segs segs = segs_in;
   const uint64_t n = segs.total;
   bpmi_ctx::PendingMsm &pd = ctx->pend[slot];
   if (pd.active) return fail(ctx, BPMI_E_STATE, "an MSM is still pending in this slot (bpmi_msm_finish it first)");
   if (n == 0) return BPMI_OK;
   if (n > BPMI_MAX_N) return fail(ctx, BPMI_E_ARG, "n exceeds BPMI_MAX_N");
-  const MsmPlan pl = msm_pick_geometry(*ctx, mode, n, w0, wcount);
+  const MsmPlan pl = rec ? rec->plan : msm_pick_geometry(*ctx, mode, n, w0, wcount);
   MsmGeom g = pl.g;
   MsmWs w;
   msm_layout(g, w, nullptr, pl.glv);
@@ -319,7 +324,7 @@ static int msm_enqueue(bpmi_ctx *ctx, const MsmMode &mode, int lane, int slot, c
     return BPMI_OK;
   }
   MsmCapture cap(ctx, st, pd);
-  if (phase == 0 && ctx->opt_graph && !ctx->prof && !g_debug_sync && !mode.chained) {
+  if (phase == 0 && ctx->opt_graph && !ctx->prof && !g_debug_sync && !mode.chained && !rec) {
     msm_graph_key(cap.key, ctx, pl, lane, slot, segs_in, w0, wcount);
     bool replayed;
     rc = cap.begin(replayed);
@@ -345,7 +350,7 @@ static int msm_enqueue(bpmi_ctx *ctx, const MsmMode &mode, int lane, int slot, c
     if ((rc = msm_queue_small(ctx, st, pd, segs, g, w, E_dst))) return rc;
   } else {
     ctx->lane[lane].run_planned = g.runs; ctx->lane[lane].run_flags = w.P ? w.run_flags : nullptr;
-    if (!(phase == 2 && sort_ahead) && (rc = msm_queue_sort(ctx, st, segs, g, w))) return rc;
+    if (!(phase == 2 && sort_ahead) && (rc = msm_queue_sort(ctx, st, segs, g, w, rec))) return rc;
     if ((rc = msm_queue_accumulate(ctx, mode, lane, st, segs, g, w, pl.glv))) return rc;
     msm_queue_segscan(ctx, st, g, w);
     tail = wcount ? 2 : (ctx->opt_tail ? ctx->opt_tail : 2);      // window groups are combined on the host

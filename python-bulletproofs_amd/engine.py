@@ -169,6 +169,16 @@ class Engine:
         self._ck(self.lib.bpmi_msm_batch(self.ctx, pts, n, scalars, n_vec, out))
         return out.raw[:64 * n_vec]
 
+    def fixed_base_create(self, pts, n, window_bits=0, rows=0):
+        """A FixedBase over n points (bpmi_fixed_base_create[_dev]): `pts` is n x 64 host bytes, or device memory (a DeviceBuffer, a tensor,
+        an address).  window_bits / rows: 0 = automatic, else 10 .. 16 / 1 .. W; the points are copied."""
+        h = ctypes.c_void_p()
+        if isinstance(pts, (bytes, bytearray)):
+            self._ck(self.lib.bpmi_fixed_base_create(self.ctx, bytes(pts), n, window_bits, rows, ctypes.byref(h)))
+        else:
+            self._ck(self.lib.bpmi_fixed_base_create_dev(self.ctx, _ptr(pts), n, window_bits, rows, ctypes.byref(h)))
+        return FixedBase(self, h.value)
+
     def msm_geometry(self, n, pipelined=False):
         """What an MSM of n pairs runs as under the current options (bpmi_msm_geometry): a dict with the kernel family, window bits,
         windows (and how many are one bit wider), buckets, chunk length, slices and pairs per slice.  No GPU work."""
@@ -348,6 +358,51 @@ class Engine:
         calls = (ctypes.c_uint64 * _native.NSTAGES)()
         self._ck(self.lib.bpmi_profile_read(self.ctx, ms, calls))
         return {self.lib.bpmi_profile_stage_name(i).decode(): (ms[i], calls[i]) for i in range(_native.NSTAGES)}
+
+
+class FixedBase:
+    """A point set and the table of its multiples on the device (bpmi_fixed_base, include/bpmi.h): MSMs over the first n_scalars of its
+    points, through the engine's lanes and pending slots like msm_dev / msm_dev_enqueue.  Close it before its engine."""
+
+    def __init__(self, engine, handle):
+        self.engine = engine
+        self.handle = handle
+
+    @property
+    def info(self):
+        v = (ctypes.c_uint64 * 8)()
+        self.engine._ck(self.engine.lib.bpmi_fixed_base_info(self.handle, v))
+        return {"n": v[0], "window_bits": v[1], "windows": v[2], "rows": v[3], "virtual_windows": v[4], "table_bytes": v[5], "build_us": v[6]}
+
+    def table_bytes(self, row, first, count):
+        out = ctypes.create_string_buffer(max(64 * count, 1))
+        self.engine._ck(self.engine.lib.bpmi_fixed_base_table(self.handle, row, first, count, out))
+        return out.raw[:64 * count]
+
+    def msm_bytes(self, scalars, n_scalars):
+        out = ctypes.create_string_buffer(64)
+        self.engine._ck(self.engine.lib.bpmi_msm_fixed(self.handle, scalars, n_scalars, out))
+        return out.raw
+
+    def msm_dev(self, d_scalars, n_scalars):
+        out = ctypes.create_string_buffer(64)
+        self.engine._ck(self.engine.lib.bpmi_msm_fixed_dev(self.handle, _ptr(d_scalars) if n_scalars else None, n_scalars, out))
+        return out.raw
+
+    def msm_dev_enqueue(self, slot, d_scalars, n_scalars):
+        """Queue one MSM in pending slot `slot`; Engine.msm_finish(slot) returns its result."""
+        self.engine._ck(self.engine.lib.bpmi_msm_fixed_dev_enqueue(self.handle, slot, _ptr(d_scalars) if n_scalars else None, n_scalars))
+
+    def close(self):
+        if self.handle and getattr(self.engine, "ctx", None):
+            self.engine.lib.bpmi_fixed_base_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class IpaState:

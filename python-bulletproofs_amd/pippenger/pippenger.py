@@ -21,6 +21,33 @@ class DevicePoints:
         self.buf = self.engine.upload(pack_points(points))
 
 
+class FixedBasePoints:
+    """A list of generators that never changes, kept on the device with a table of its multiples (bpmi_fixed_base, include/bpmi.h):
+    `multiexp(es)` is the sum of es[i] * points[i] over the first len(es) <= n points.  window_bits / rows: 0 = automatic."""
+
+    def __init__(self, points, window_bits=0, rows=0, engine=None):
+        self.engine = engine or _engine.default_engine()
+        self.n = len(points)
+        self.fixed = self.engine.fixed_base_create(pack_points(points), self.n, window_bits, rows)
+
+    def __len__(self):
+        return self.n
+
+    @property
+    def info(self):
+        return self.fixed.info
+
+    def multiexp(self, es):
+        if len(es) > self.n:
+            raise Exception("More exponents than group elements")
+        if not es:
+            return Point.IDENTITY_ELEMENT
+        return Point.from_le64(self.fixed.msm_bytes(pack_scalars(es, secp256k1.q), len(es)))
+
+    def close(self):
+        self.fixed.close()
+
+
 class Pippenger:
     def __init__(self, group):
         self.G = group
@@ -39,6 +66,8 @@ class Pippenger:
         n = len(gs)
         if n == 0:
             return self.G.unit
+        if isinstance(gs, FixedBasePoints):
+            return gs.multiexp(es)
         eng = _engine.default_engine()
         scalars = pack_scalars(es, self.order)       # es[i] % order, pippenger.py:26
         if isinstance(gs, DevicePoints):

@@ -15,6 +15,12 @@ def vector_commitment(g, h, a, b):
     return PipSECP256k1.multiexp(g + h, a + b)
 
 
+def vector_commitment_fixed(fx, a, b):
+    """vector_commitment(g, h, a, b) over a FixedBasePoints `fx` built once over g + h (pippenger.FixedBasePoints)."""
+    assert len(a) == len(b) and len(a) + len(b) == len(fx)
+    return PipSECP256k1.multiexp(fx, a + b)
+
+
 def vector_commitment_batch(g, h, A, B):
     """[vector_commitment(g, h, a, b) for a, b in zip(A, B)] in one native call: the generators are uploaded once and stay two segments
     (g | h) of bpmi_msm_batch_dev, the rows of A and of B are its two scalar matrices -- no list concatenation."""

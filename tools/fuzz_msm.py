@@ -3,6 +3,7 @@
 shapes (uniform, tiny, near q/2 and q, repeated, zero), point shapes (duplicates, negated
 pairs, identities) and engine options (window bits, chunk length, tail placement, window-group
 split, small-MSM threshold, GLV split on / off, fused / unfused wave scan, the round-5 and round-6 options, the accumulation by runs); a few percent of the cases are large enough for the LDS sort path.
+A quarter of the cases run again as a fixed-base object (bpmi_fixed_base_create, bpmi_msm_fixed) with random window bits, rows and a prefix of the scalars.
   python tools/fuzz_msm.py [seconds]"""
 import os
 import random
@@ -93,6 +94,23 @@ while time.time() - t0 < budget:
     if got != want:
         fails += 1
         print("MISMATCH n=%d shape=%d kind=%d opts=%s seed=%d case=%d" % (n, shape, kind, opts, seed, cases), flush=True)
+    if rnd.random() < 0.25:
+        # the same points as a fixed-base object (bpmi_fixed_base_create, bpmi_msm_fixed) under the same options: any window bits, any rows
+        # (0 = automatic), the first m <= n scalars
+        c = rnd.choice((0, 0, 10, 11, 12, 13, 14, 15, 16, 16))
+        rows = rnd.choice((0, 1, 2, rnd.randrange(1, 255 // (c or 16) + 2), 255 // (c or 16) + 1))
+        W = 255 // (c or 16) + 1
+        R = -(-W // -(-W // rows)) if rows else 1
+        if n * R <= 1 << 23:
+            m = rnd.choice((n, n, n - 1, rnd.randrange(n + 1)))
+            fx = eng.fixed_base_create(pb, n, c, rows)
+            got = fx.msm_bytes(sb[:32 * m], m)
+            fx.close()
+            want = cbind.msm_bytes(pb[:64 * m], sb[:32 * m], m, 4) if m else bytes(64)
+            cases += 1
+            if got != want:
+                fails += 1
+                print("MISMATCH fixed base n=%d m=%d c=%d rows=%d shape=%d kind=%d opts=%s seed=%d case=%d" % (n, m, c, rows, shape, kind, opts, seed, cases), flush=True)
 for k in ("window_bits", "chunk", "tail", "split", "small_n", "glv", "mid_single_min", "slice_n", "rounds", "accum_runs_cap"):
     eng.set_option(k, 0)
 eng.set_option("accum_runs", 1)
