@@ -13,7 +13,9 @@
 //   k_scan_*        exclusive scans of the (coarse) histograms -> run offsets
 //   k_accum_runs    (16-bit windows from 2^19 pairs) every thread adds ONE whole bucket run, the buckets in order
 //                   of their run length (k_runs_hist / k_runs_scatter: a counting sort of the buckets); a
-//                   flag on the device hands MSMs with a long run to the next two kernels
+//                   flag on the device hands MSMs with a long run to the next two kernels.  <true>: one
+//                   dense array, the point of an entry fetched without the segment walk; the first two
+//                   entries of a run stand in front of the loop (the second: affine + affine, xyzz_mmadd)
 //   k_accum_l0      every thread adds exactly L sorted entries (perfectly balanced for
 //                   ANY digit distribution); runs that end inside a chunk go to their
 //                   bucket, the first/last run of a chunk become partial records

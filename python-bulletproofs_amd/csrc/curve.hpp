@@ -148,6 +148,40 @@ BPMI_HD void xyzz_madd_signed(xyzz &acc, const affine &P, bool negate) {
   xyzz_madd(acc, P.x, ny);
 }
 
+// r = (x1, y1) + (x2, y2), two affine points NEITHER of which is the identity (mmadd-2008-s): 4M + 2S in FIVE reductions and two
+// carry passes -- the second entry of a bucket run, where the accumulator still has ZZ = ZZZ = 1 and the mixed addition would
+// spend four products on multiplying by one.
+//   x1, x2  tight or loose (any encoding of the coordinate: x and x + p are the same point)
+//   y1      tight or loose;  y2  tight, loose or LAZY (magnitude <= 2, e.g. 2p - y)
+//   r       X, Y, ZZ, ZZZ loose, as xyzz_madd leaves them; r may be the record x1 / y1 live in (they are read before it is written)
+// The differences cannot ride in a reduction here (nothing is multiplied before them), so they are carried:
+//   P  = carry(x2 - x1 + 2p)   magnitude 3 -> tight      R = carry(y2 - y1 + 2p)   magnitude 4 (limbs < 2^31) -> tight
+// (a single fe_carry leaves a value < 2^257: 0 mod p is 0, p or 2p, what fe_is_zero_tight tests -- fe_is_zero's own contract).
+// Columns (9 * sum of magnitude products <= 63):  PP = P^2, PPP = P PP, Q = x1 PP: 9 each;  X3 = R^2 + (8p - PPP - 2Q): 9 and an
+// addend below 2^32;  Y3 = R (Q - X3 + 2p) + (2p - y1) PPP: 9 * (1 * 3 + 2 * 1) = 45.
+// Exceptional cases behind xyzz_madd's two-compare prefilter (limb 4 of a tight 0, p or 2p is 0 or 2^29 - 1).
+BPMI_HD void xyzz_mmadd(xyzz &r, const fe &x1, const fe &y1, const fe &x2, const fe &y2) {
+  fe P, R, t;
+  fe_sub(t, x2, x1); fe_carry(P, t);
+  fe_sub(t, y2, y1); fe_carry(R, t);
+  if (fe_maybe_zero(P)) {
+    if (fe_is_zero_tight(P)) {
+      if (fe_is_zero_tight(R)) { fe_carry(t, y2); xyzz_dbl_affine(r, x2, t); return; }      // the same point twice
+      xyzz_set_inf(r); return;                                                               // P and -P
+    }
+  }
+  fe PP, PPP, Q, ny1;
+  fe_neg(ny1, y1);                                        // 2p - y1, magnitude-2 factor of Y3 (before r.Y is written: r may hold y1)
+  fe_sqr(PP, P);
+  fe_mul(PPP, P, PP);
+  fe_mul(Q, x1, PP);
+  fe_bias8_sub_a_2b(t, PPP, Q);                           // 8p - PPP - 2Q
+  fe_sqr_add(r.X, R, t);                                  // X3  (x1 is dead from here on)
+  fe_sub(t, Q, r.X);                                      // Q - X3 + 2p, magnitude 3
+  fe_mul2(r.Y, R, t, ny1, PPP);                           // Y3 = R (Q - X3) - y1 PPP
+  r.ZZ = PP; r.ZZZ = PPP;
+}
+
 // r = a + b, both XYZZ (add-2008-s): 12M + 2S in thirteen reductions (the subtractions ride in them)
 BPMI_HD void xyzz_add(xyzz &r, const xyzz &a, const xyzz &b) {
   if (xyzz_is_inf(a)) { r = b; return; }

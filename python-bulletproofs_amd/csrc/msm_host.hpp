@@ -212,7 +212,10 @@ static int msm_queue_accumulate(bpmi_ctx *ctx, const MsmMode &mode, int lane, hi
     // the accumulation by runs first (at most G runs; returns at once when the table kernels found a run over the cap), the chunked one behind it
     // (returns at once otherwise): the flag on the device chooses, nothing waits for the host
     const u32 *long_run = g.runs ? w.run_flags + RUN_FLAG_WORD : nullptr;
-    if (g.runs) hipLaunchKernelGGL(k_accum_runs, dim3((g.G + 255) / 256), dim3(256), 0, st_acc, segs, g, w.off, w.sidx, w.run_order, w.run_flags, w.buckets);
+    if (g.runs) {
+      auto runs = (!glv && segs_one_dense(segs)) ? k_accum_runs<true> : k_accum_runs<false>;      // one dense array: the point of an entry without the segment walk
+      hipLaunchKernelGGL(runs, dim3((g.G + 255) / 256), dim3(256), 0, st_acc, segs, g, w.off, w.sidx, w.run_order, w.run_flags, w.buckets);
+    }
     hipLaunchKernelGGL(kern, dim3((w.nchunks + 255) / 256), dim3(256), 0, st_acc, segs, g, w.off, w.chunk_key, w.sidx, w.buckets, w.rec_key[0], w.rec_pt[0], long_run);
   }
   if (own_acc) {

@@ -978,7 +978,43 @@ __global__ void __launch_bounds__(256) k_runs_scatter(MsmGeom g, const u32 *__re
 // Thread t adds the run of bucket order[t] and stores the bucket.  The loop is k_accum_l0's without its run boundaries: the point of entry
 // j + 1 and the index of entry j + 2 in flight while entry j is added.  Complete for any run: xyzz_madd_signed skips identity points, doubles
 // an equal point and returns to the identity (and goes on from it) when P meets -P.
-__global__ void __launch_bounds__(256) k_accum_runs(Segs segs, MsmGeom g, const u32 *__restrict__ off, const u32 *__restrict__ sidx,
+//
+// DENSE (segs_one_dense, shared_defs.hpp: one array, no half-block selection, no GLV -- the headline, the slices of a large MSM, the
+// commitments, the fixed-base table): the point of entry idx is pts[0] + 16 idx, without load_entry_point's segment walk and remap.
+//
+// The first two entries of a run stand in front of the loop.  The runs of a wave start together and order[] is sorted by length, so what
+// k_accum_l0 had to keep in its loop costs no divergence here: entry 1 only makes the accumulator the affine point (x, +-y, 1, 1), and
+// entry 2 meets ZZ = ZZZ = 1 -- the affine + affine addition xyzz_mmadd, 4M + 2S in five reductions against 8M + 2S in nine.  Whether
+// the accumulator is affine is known from control flow (`fin`); the loop from entry 3 on is the old one, "accumulator is the identity"
+// path included (P + (-P) can empty it at any entry).  Runs of one and two entries leave through the same store.
+// (Measured and left out: an exact "nine zero limbs" identity test in the loop in place of xyzz_madd's prefiltered one -- 50
+// instructions fewer per entry by the ledger, and 5 us per step SLOWER than this form, three runs against three on one box.)
+template <bool DENSE> __device__ __forceinline__ void runs_load_point(u32 w[16], const Segs &segs, u32 idx) {
+  if (DENSE) load_words16(w, segs.pts[0] + 16ull * idx);
+  else load_entry_point<false>(w, segs, idx);
+}
+// entry j of the run [.., end): its limbs out of the words in flight, then the point of entry j + 1 and the index of entry j + 2 on their way
+template <bool DENSE> __device__ __forceinline__ void runs_next_entry(affine &P, u32 &e, u32 (&w_next)[16], u32 &e_next, u32 &e_next2, const Segs &segs,
+                                                                      const u32 *__restrict__ sidx, u32 j, u32 end) {
+  e = e_next;
+  affine_from_words(P, w_next);
+  // (the limbs before the next loads overwrite the words: see k_accum_l0)
+  asm volatile("" : "+v"(P.x.v[0]), "+v"(P.x.v[1]), "+v"(P.x.v[2]), "+v"(P.x.v[3]), "+v"(P.x.v[4]), "+v"(P.x.v[5]), "+v"(P.x.v[6]),
+               "+v"(P.x.v[7]), "+v"(P.x.v[8]), "+v"(P.y.v[0]), "+v"(P.y.v[1]), "+v"(P.y.v[2]), "+v"(P.y.v[3]), "+v"(P.y.v[4]),
+               "+v"(P.y.v[5]), "+v"(P.y.v[6]), "+v"(P.y.v[7]), "+v"(P.y.v[8]));
+  if (j + 1 < end) {
+    e_next = e_next2;
+    if (j + 2 < end) e_next2 = sidx[j + 2];
+    runs_load_point<DENSE>(w_next, segs, e_next & 0x7FFFFFFFu);
+  }
+}
+// y or the lazy 2p - y: a select, never a branch (xyzz_madd_signed)
+__device__ __forceinline__ void runs_signed_y(fe &sy, const fe &y, bool negate) {
+  fe_neg(sy, y);
+#pragma unroll
+  for (int k = 0; k < 9; k++) sy.v[k] = negate ? sy.v[k] : y.v[k];
+}
+template <bool DENSE> __global__ void __launch_bounds__(256) k_accum_runs(Segs segs, MsmGeom g, const u32 *__restrict__ off, const u32 *__restrict__ sidx,
                                                     const u32 *__restrict__ order, const u32 *__restrict__ flags, u32 *__restrict__ buckets) {
   if (flags[RUN_FLAG_WORD]) return;                 // a run longer than the cap: k_accum_l0's MSM
   const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -986,24 +1022,32 @@ __global__ void __launch_bounds__(256) k_accum_runs(Segs segs, MsmGeom g, const 
   const u32 b = order[t];
   const u32 start = off[b], end = off[b + 1];
   xyzz acc;
-  xyzz_set_inf(acc);
   u32 e_next = sidx[start];
   u32 e_next2 = (start + 1 < end) ? sidx[start + 1] : 0u;
   u32 w_next[16];
-  load_entry_point<false>(w_next, segs, e_next & 0x7FFFFFFFu);
-  for (u32 j = start; j < end; j++) {
-    const u32 e = e_next;
-    affine P;
-    affine_from_words(P, w_next);
-    // (the limbs before the next loads overwrite the words: see k_accum_l0)
-    asm volatile("" : "+v"(P.x.v[0]), "+v"(P.x.v[1]), "+v"(P.x.v[2]), "+v"(P.x.v[3]), "+v"(P.x.v[4]), "+v"(P.x.v[5]), "+v"(P.x.v[6]),
-                 "+v"(P.x.v[7]), "+v"(P.x.v[8]), "+v"(P.y.v[0]), "+v"(P.y.v[1]), "+v"(P.y.v[2]), "+v"(P.y.v[3]), "+v"(P.y.v[4]),
-                 "+v"(P.y.v[5]), "+v"(P.y.v[6]), "+v"(P.y.v[7]), "+v"(P.y.v[8]));
-    if (j + 1 < end) {
-      e_next = e_next2;
-      if (j + 2 < end) e_next2 = sidx[j + 2];
-      load_entry_point<false>(w_next, segs, e_next & 0x7FFFFFFFu);
+  runs_load_point<DENSE>(w_next, segs, e_next & 0x7FFFFFFFu);
+  u32 j = start, e;
+  affine P;
+  fe sy;
+  // entry 1 (every run has one): the accumulator becomes the point, or stays the identity for an identity point
+  runs_next_entry<DENSE>(P, e, w_next, e_next, e_next2, segs, sidx, j, end);
+  bool fin = !affine_is_inf(P);                     // the accumulator is a finite AFFINE point
+  runs_signed_y(sy, P.y, (e >> 31) != 0);
+  if (fin) { acc.X = P.x; fe_carry(acc.Y, sy); fe_set_one(acc.ZZ); fe_set_one(acc.ZZZ); }
+  else xyzz_set_inf(acc);
+  j++;
+  // entry 2
+  if (j < end) {
+    runs_next_entry<DENSE>(P, e, w_next, e_next, e_next2, segs, sidx, j, end);
+    if (!affine_is_inf(P)) {
+      runs_signed_y(sy, P.y, (e >> 31) != 0);
+      if (fin) xyzz_mmadd(acc, acc.X, acc.Y, P.x, sy);
+      else { acc.X = P.x; fe_carry(acc.Y, sy); fe_set_one(acc.ZZ); fe_set_one(acc.ZZZ); }
     }
+    j++;
+  }
+  for (; j < end; j++) {
+    runs_next_entry<DENSE>(P, e, w_next, e_next, e_next2, segs, sidx, j, end);
     xyzz_madd_signed(acc, P, (e >> 31) != 0);
   }
   xyzz_store_g(buckets + (u64)b * XYZZ_WORDS, acc);

@@ -45,6 +45,11 @@ static inline Segs segs_init() {
   s.hlog[0] = s.hlog[1] = s.hlog[2] = 0xFFu;
   return s;
 }
+// One dense array: logical pair i is physical pair i of segment 0 -- the point of a sort entry is pts[0] + 16 * index with no segment
+// walk and no half-block remap (k_accum_runs<true>).  Never with GLV: its entries index virtual pairs.
+static inline bool segs_one_dense(const Segs &s) {
+  return s.total != 0 && s.n[0] == s.total && s.n[1] == 0 && s.n[2] == 0 && s.hlog[0] >= 32u && !s.glv_sub;
+}
 
 // ---- sizing constants of the MSM (the kernels they belong to: msm_kernels.hpp) ------------------------------------------------
 // MsmGeom.prio is a mask of the stages whose kernels raise their waves' issue priority (raise_priority, msm_kernels.hpp):

@@ -7,7 +7,9 @@ separately).
 
     python tools/isa_counts.py                       # prints the JSON object
     python tools/isa_counts.py --write               # also writes profiles/r04_isa_counts.json and the ISA excerpt
-    python tools/isa_counts.py --loops [--write]     # the per-entry loops of k_accum_l0<false, true> and k_accum_runs, block by block
+    python tools/isa_counts.py --loops [--write]     # the per-entry loops of k_accum_l0<false, true> and of both k_accum_runs instantiations
+                                                     # (<true>: dense point fetch), block by block, and what stands in front of the loop
+                                                     # (k_accum_runs: the first two entries of a run) counted on its own
                                                      # (--write: profiles/accum_loop_isa_ledger.json)
 
 --loops tallies the whole loop, not only the addition: the loop is the first outermost backward branch whose span holds a whole
@@ -76,7 +78,7 @@ def loop_tally(kernel):
             break
         if blocks[k]["branches"][-1].startswith("s_branch"):
             end = k
-    body, tail = blocks[lo:end + 1], blocks[end + 1:]
+    head, body, tail = blocks[:lo], blocks[lo:end + 1], blocks[end + 1:]
     count = lambda bs, key: sum(b_[key] for b_ in bs)
     # the rare paths of the mixed addition: the doubling (acc == addend; the only other block with hundreds of multiply-adds besides the two of the
     # main path, which are the first two in program order) and the blocks outlined behind the loop
@@ -90,6 +92,8 @@ def loop_tally(kernel):
             "loop_common_path_memory_instructions": count(common, "memory_instructions"),
             "mixed_addition_main_path_instructions": count(heavy[:2], "instructions"), "mixed_addition_main_path_v_mad_u64_u32": count(heavy[:2], "v_mad_u64_u32"),
             "rare_blocks_not_in_common_path": rare, "loop_blocks": fmt(body),
+            "before_loop_instructions": count(head, "instructions"), "before_loop_v_mad_u64_u32": count(head, "v_mad_u64_u32"),
+            "before_loop_memory_instructions": count(head, "memory_instructions"), "before_loop_blocks_of_20_or_more": fmt([b_ for b_ in head if b_["instructions"] >= 20]),
             "after_loop_instructions": count(tail, "instructions"), "after_loop_v_mad_u64_u32": count(tail, "v_mad_u64_u32"),
             "after_loop_blocks_of_20_or_more": fmt([b_ for b_ in tail if b_["instructions"] >= 20]),
             "vgprs": int(re.search(r"; NumVgprs: (\d+)", kernel).group(1)), "scratch_bytes": int(re.search(r"; ScratchSize: (\d+)", kernel).group(1)),
@@ -100,7 +104,8 @@ def loops(text):
     out = {"how": "hipcc -O3 --offload-arch=gfx950 -S; the first outermost loop (backward branch) that holds >= 900 v_mad_u64_u32 is the per-entry loop, with the "
                   "blocks laid out behind it that jump back into it; blocks in program order; 'skipped when s_cbranch_execz': executed by the whole wave as soon as ONE "
                   "lane needs it; common path = every block but the doubling and the outlined ones (tools/isa_counts.py --loops)"}
-    for name, pat in (("k_accum_l0<false,true>", r"^_Z10k_accum_l0ILb0ELb1E.*?; Occupancy: \d+"), ("k_accum_runs", r"^_Z12k_accum_runs.*?; Occupancy: \d+")):
+    for name, pat in (("k_accum_l0<false,true>", r"^_Z10k_accum_l0ILb0ELb1E.*?; Occupancy: \d+"), ("k_accum_runs<true>", r"^_Z12k_accum_runsILb1EE.*?; Occupancy: \d+"),
+                      ("k_accum_runs<false>", r"^_Z12k_accum_runsILb0EE.*?; Occupancy: \d+")):
         out[name] = loop_tally(re.search(pat, text, re.S | re.M).group(0))
     print(json.dumps(out, indent=1))
     if "--write" in sys.argv:
