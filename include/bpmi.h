@@ -687,6 +687,26 @@ int bpmi_ipa_prove_batch(bpmi_ipa_batch_prover *pv, int protocol, uint64_t n_pro
                          const uint8_t *seeds, const uint64_t *seed_off, uint8_t *ab, uint8_t *xs, uint8_t *LR, uint8_t *head, uint8_t *transcripts,
                          uint64_t cap, uint64_t *tr_off);
 int bpmi_ipa_batch_prover_last_ms(const bpmi_ipa_batch_prover *pv, double ms[4]);
+/* The STATEMENTS of a batch from the prover's tables: out[p] = sum_j a_p[j] g_j + sum_j b_p[j] (c_j h_j) + t_p u -- a loop of
+ * `vector_commitment(g, h, a_p, b_p)` (src/utils/commitments.py:13, :9-13) plus `inner_product(a, b) * u`: the P that NIProver takes
+ * as an input and every verifier takes (src/tests/test_innerprod.py:26, :112).  One launch lays out the scalars, one walks the tables
+ * (16 additions per term at 16-bit windows, no buckets), one makes the points affine.
+ *   c_j          the prover's h_scale, or 1 without one: multiplied into the scalars, no point is scaled.
+ *   a, b         count x n x 32 B little-endian in [0, q).  Either may be NULL (all zeros: its half of every job's terms is dropped,
+ *                not multiplied by zero), not both.
+ *   u_mode       0: no u term, t must be NULL (NIProver's statement).  1: t_p = <a_p, b_p>, summed on the device over the UNSCALED b;
+ *                t must be NULL, a and b are both required (FastNIProver2's statement).  2: t holds count x 32 B scalars in [0, q).
+ *   out          HOST memory, count x 64 B affine (x, y little-endian), canonical; the identity is 64 zero bytes; complete on return.
+ * BPMI_E_ARG with a message naming the cause, before anything is read or allocated: pv or out NULL, u_mode outside 0 .. 2, t given
+ * where it must be NULL or missing under u_mode 2, a and b both NULL (or one of them under u_mode 1), count beyond the caps of
+ * bpmi_ipa_prove_batch (2^20 proofs, 2^27 elements).  A scalar that is not below q is BPMI_E_ARG naming the array and the first such
+ * index.  No output is written on any error.  count = 0 is BPMI_OK and touches nothing.  Shares the prover's buffers: one call at a
+ * time per prover and ctx, like proving.
+ *   bpmi_ipa_batch_prover_commit_last_ms  of the last such call: the device milliseconds of its three kernels | the milliseconds of
+ *                the whole call on the host's clock (checks, staging, both copies).  bpmi_ipa_batch_prover_last_ms is not touched. */
+int bpmi_ipa_batch_prover_commit_batch(bpmi_ipa_batch_prover *pv, uint64_t count, const uint8_t *a, const uint8_t *b, int u_mode, const uint8_t *t,
+                                       uint8_t *out);
+int bpmi_ipa_batch_prover_commit_last_ms(const bpmi_ipa_batch_prover *pv, double ms[2]);
 
 /* ---- batch verifier of PACKED inner-product proofs ---------------------------------------- */
 /* What bpmi_ipa_prove_batch writes, verified without leaving native code: the Fiat-Shamir re-hash, the byte-level checks and the

@@ -92,6 +92,8 @@ SIGNATURES = {
     "bpmi_ipa_prove_batch_transcript_bytes": (_u64, [_vp, _i, _u64]),
     "bpmi_ipa_prove_batch": (_i, [_vp, _i, _u64, _cp, _cp, _cp, _cp, _cp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "bpmi_ipa_batch_prover_last_ms": (_i, [_vp, ctypes.POINTER(ctypes.c_double)]),
+    "bpmi_ipa_batch_prover_commit_batch": (_i, [_vp, _u64, _cp, _cp, _i, _cp, _vp]),
+    "bpmi_ipa_batch_prover_commit_last_ms": (_i, [_vp, ctypes.POINTER(ctypes.c_double)]),
     # (k | ctx, k | ctx, g, h, hscale, n), protocol, n_proofs, ab, xs, LR, transcripts, tr_off, start, u, P, c, head, weights, seed, ...
     "bpmi_ipa_batch_prepare": (_i, [ctypes.c_uint32, _i, _u64, _cp, _cp, _cp, _cp, _vp, _vp, _cp, _cp, _cp, _cp, _cp, _cp, _i, _vp, _vp, _vp, _vp]),
     "bpmi_ipa_batch_prepare_dev": (_i, [_vp, ctypes.c_uint32, _i, _u64, _cp, _cp, _cp, _cp, _vp, _vp, _cp, _cp, _cp, _cp, _cp, _cp, _vp, _vp, _vp, _vp]),

@@ -1,7 +1,8 @@
 // ipa_prove_host.hpp -- part of libbpmi (included by bpmi.hip; one translation unit).  HOST code.
 // The batched inner-product prover's object and launch sequence (kernels: ipa_prove_kernels.hpp; plan: ipa_prove_plan_host.hpp):
 // bpmi_ipa_batch_prover_create builds the fixed-base tables of a generator set (u, g, h) once; bpmi_ipa_prove_batch proves any
-// number of arguments over them, every protocol step as one launch over the whole batch.
+// number of arguments over them, every protocol step as one launch over the whole batch; bpmi_ipa_batch_prover_commit_batch makes the
+// statements P_p of a batch from the same tables.
 #pragma once
 
 struct bpmi_ipa_batch_prover {
@@ -11,12 +12,14 @@ struct bpmi_ipa_batch_prover {
   u32 *table = nullptr;                        // [(1 + 2n)][wt][bt] affine points: base 0 u, 1 + j g_j, 1 + n + j h_j
   u32 tw = 16, wt = 16, bt = 32768;
   unsigned short *bases = nullptr;             // device: the base lists (ipp_plan)
+  unsigned short *cbases = nullptr;            // device: the base lists of a statement's job (ipp_commit_bases_all)
   u32 off_head = 0, off_round = 0;
   u32 *hscale = nullptr;                       // device: n scalars, or nullptr
   void *buf = nullptr; size_t buf_bytes = 0;   // the batch's device arrays (grown on demand)
   void *pin = nullptr; size_t pin_bytes = 0;   // page-locked staging of the inputs / the proofs
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};      // phase boundaries of a batch
   double last_ms[4] = {0};                     // device milliseconds of the last batch: begin + head | rounds | copy out | whole
+  double commit_ms[2] = {0};                   // the last bpmi_ipa_batch_prover_commit_batch: its kernels on the device | the whole call on the host's clock
 };
 
 extern "C" {
@@ -26,6 +29,7 @@ void bpmi_ipa_batch_prover_destroy(bpmi_ipa_batch_prover *pv) {
   if (pv->ctx) { (void)hipSetDevice(pv->ctx->device); (void)hipStreamSynchronize(pv->ctx->stream); }
   if (pv->table) (void)hipFree(pv->table);
   if (pv->bases) (void)hipFree(pv->bases);
+  if (pv->cbases) (void)hipFree(pv->cbases);
   if (pv->hscale) (void)hipFree(pv->hscale);
   if (pv->buf) (void)hipFree(pv->buf);
   if (pv->pin) (void)hipHostFree(pv->pin);
@@ -70,6 +74,11 @@ static int ipa_batch_prover_create_impl(bpmi_ctx *ctx, uint32_t n, const uint8_t
   const std::vector<unsigned short> &bl = plan.bases;
   e = hipMalloc(&pv->bases, 2 * bl.size());
   if (e == hipSuccess) e = hipMemcpy(pv->bases, bl.data(), 2 * bl.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    const std::vector<unsigned short> cl = ipp_commit_bases_all(n);
+    e = hipMalloc(&pv->cbases, 2 * cl.size());
+    if (e == hipSuccess) e = hipMemcpy(pv->cbases, cl.data(), 2 * cl.size(), hipMemcpyHostToDevice);
+  }
   if (e == hipSuccess && h_scale) {
     e = hipMalloc(&pv->hscale, 32 * (size_t)n);
     if (e == hipSuccess) e = hipMemcpy(pv->hscale, h_scale, 32 * (size_t)n, hipMemcpyHostToDevice);
@@ -252,6 +261,97 @@ int bpmi_ipa_prove_batch(bpmi_ipa_batch_prover *pv, int protocol, uint64_t n_pro
 int bpmi_ipa_batch_prover_last_ms(const bpmi_ipa_batch_prover *pv, double ms[4]) {
   if (!pv || !ms) return BPMI_E_ARG;
   for (int i = 0; i < 4; i++) ms[i] = pv->last_ms[i];
+  return BPMI_OK;
+}
+
+// The statements of a batch from the prover's tables: out[p] = sum a_p[j] g_j + sum b_p[j] (c_j h_j) + t_p u.  One upload of [a | b | t]
+// through the staging buffer, k_ip_commit_scalars lays out (and under u_mode 1 sums) the rows of count jobs of one type over the base
+// list of ipp_commit_bases, k_pv_msm, k_pv_affine, one copy down.  The prover's device and staging buffers are shared with proving.
+static int ipa_batch_prover_commit_batch_impl(bpmi_ipa_batch_prover *pv, uint64_t count, const uint8_t *a, const uint8_t *b, int u_mode, const uint8_t *t, uint8_t *out) {
+  const char *const fn = "bpmi_ipa_batch_prover_commit_batch: ";
+  if (!pv) return fail(nullptr, BPMI_E_ARG, std::string(fn) + "null argument (pv)");
+  bpmi_ctx *ctx = pv->ctx;
+  if (count == 0) {
+    if (u_mode < 0 || u_mode > 2) return fail(ctx, BPMI_E_ARG, std::string(fn) + "u_mode must be 0 (no u term), 1 (t = <a, b>) or 2 (t given)");
+    return BPMI_OK;
+  }
+  // the argument errors and the per-call caps come first: nothing of a batch beyond them is read or allocated
+  IppCommitCall call;
+  call.pv = true; call.out = out != nullptr; call.a = a != nullptr; call.b = b != nullptr; call.t = t != nullptr; call.u_mode = u_mode;
+  if (const char *bad = ipp_commit_error(call)) return fail(ctx, BPMI_E_ARG, std::string(fn) + bad);
+  if (const char *over = ipp_batch_error(pv->max_proofs, count)) return fail(ctx, BPMI_E_ARG, std::string(fn) + over);
+  const auto wall0 = std::chrono::steady_clock::now();
+  const u32 C = (u32)count, n = pv->n;
+  for (uint64_t i = 0; i < count * n; i++) {
+    if (a && !rp_scalar_reduced(a + 32 * i)) return fail(ctx, BPMI_E_ARG, std::string(fn) + "a[" + std::to_string(i) + "] is not below the group order");
+    if (b && !rp_scalar_reduced(b + 32 * i)) return fail(ctx, BPMI_E_ARG, std::string(fn) + "b[" + std::to_string(i) + "] is not below the group order");
+  }
+  if (t) for (uint64_t i = 0; i < count; i++)
+    if (!rp_scalar_reduced(t + 32 * i)) return fail(ctx, BPMI_E_ARG, std::string(fn) + "t[" + std::to_string(i) + "] is not below the group order");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const u32 T = (a ? n : 0u) + (b ? n : 0u) + (u_mode ? 1u : 0u);
+  using rpp_host::up256;
+  size_t o = 0;
+  auto take = [&](size_t bytes) { const size_t at = o; o += up256(bytes); return at; };
+  const size_t o_ain = take(a ? 32ull * C * n : 0), o_bin = take(b ? 32ull * C * n : 0), o_tin = take(t ? 32ull * C : 0);
+  const size_t in_bytes = o;                                   // everything above is uploaded in one copy
+  const size_t o_jsc = take(32ull * C * T), o_jout = take(144ull * C), o_pts = take(64ull * C);
+  if (o > pv->buf_bytes) {
+    if (pv->buf) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(pv->buf)); pv->buf = nullptr; pv->buf_bytes = 0; }
+    HIPCHK(ctx, hipMalloc(&pv->buf, o + o / 8));
+    pv->buf_bytes = o + o / 8;
+  }
+  const size_t pin_need = std::max(in_bytes, (size_t)(64ull * C));
+  if (pin_need > pv->pin_bytes) {
+    if (pv->pin) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipHostFree(pv->pin)); pv->pin = nullptr; pv->pin_bytes = 0; }
+    HIPCHK(ctx, hipHostMalloc(&pv->pin, pin_need + pin_need / 8, hipHostMallocDefault));
+    pv->pin_bytes = pin_need + pin_need / 8;
+  }
+  char *d = (char *)pv->buf, *hp = (char *)pv->pin;
+  if (a) memcpy(hp + o_ain, a, 32ull * C * n);
+  if (b) memcpy(hp + o_bin, b, 32ull * C * n);
+  if (t) memcpy(hp + o_tin, t, 32ull * C);
+  hipStream_t st = ctx->stream;
+  HIPCHK(ctx, hipMemcpyAsync(d, hp, in_bytes, hipMemcpyHostToDevice, st));
+  ipp::Commit K;
+  K.count = C; K.n = n; K.T = T; K.u_mode = (u32)u_mode;
+  K.a_in = a ? (const u32 *)(d + o_ain) : nullptr; K.b_in = b ? (const u32 *)(d + o_bin) : nullptr; K.t_in = t ? (const u32 *)(d + o_tin) : nullptr;
+  K.hscale = pv->hscale; K.jsc = (u32 *)(d + o_jsc);
+  (void)hipEventRecord(pv->ev[0], st);
+  const u32 NT = pv->NT;
+  const dim3 grid((C + NT / n - 1) / (NT / n));
+  if (NT == 256u) hipLaunchKernelGGL(ipp::k_ip_commit_scalars<256>, grid, dim3(256), 0, st, K);
+  else if (NT == 512u) hipLaunchKernelGGL(ipp::k_ip_commit_scalars<512>, grid, dim3(512), 0, st, K);
+  else hipLaunchKernelGGL(ipp::k_ip_commit_scalars<1024>, grid, dim3(1024), 0, st, K);
+  rpp::MsmJobs J;
+  J.njobs = C; J.ntypes = 1; J.T = T; J.bases = pv->cbases + ipp_commit_bases_offset(n, a != nullptr, b != nullptr); J.scalars = K.jsc; J.stride = T; J.out = (u32 *)(d + o_jout);
+  const rpp::Tab tab = rpp::Tab{pv->table, pv->tw, pv->wt, pv->bt};
+  const int gl = ipp_job_lanes_log2(n, count, ctx->opt_prover_job_lanes);
+  const dim3 mgrid((u32)((((uint64_t)C << gl) + 255) / 256));
+  if (gl == 6) hipLaunchKernelGGL(rpp::k_pv_msm<6>, mgrid, dim3(256), 0, st, J, tab);
+  else hipLaunchKernelGGL(rpp::k_pv_msm<4>, mgrid, dim3(256), 0, st, J, tab);
+  hipLaunchKernelGGL(rpp::k_pv_affine, dim3((C + 255u) / 256u), dim3(256), 0, st, (const u32 *)J.out, C, 1u, (u32 *)(d + o_pts), 1u, 0u, 0u);
+  (void)hipEventRecord(pv->ev[1], st);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(hp, d + o_pts, 64ull * C, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return fail(ctx, BPMI_E_HIP, std::string(fn) + hipGetErrorString(e));
+  memcpy(out, hp, 64ull * C);
+  { float ms = 0; (void)hipEventElapsedTime(&ms, pv->ev[0], pv->ev[1]); pv->commit_ms[0] = ms; }
+  pv->commit_ms[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+  return BPMI_OK;
+}
+int bpmi_ipa_batch_prover_commit_batch(bpmi_ipa_batch_prover *pv, uint64_t count, const uint8_t *a, const uint8_t *b, int u_mode, const uint8_t *t, uint8_t *out) {
+  try {
+    return ipa_batch_prover_commit_batch_impl(pv, count, a, b, u_mode, t, out);
+  } catch (const std::bad_alloc &) {
+    return pv && pv->ctx ? fail(pv->ctx, BPMI_E_NOMEM, "bpmi_ipa_batch_prover_commit_batch: out of host memory") : BPMI_E_NOMEM;
+  }
+}
+
+int bpmi_ipa_batch_prover_commit_last_ms(const bpmi_ipa_batch_prover *pv, double ms[2]) {
+  if (!pv || !ms) return BPMI_E_ARG;
+  ms[0] = pv->commit_ms[0]; ms[1] = pv->commit_ms[1];
   return BPMI_OK;
 }
 

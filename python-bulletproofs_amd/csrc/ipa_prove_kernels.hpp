@@ -202,4 +202,58 @@ template <u32 NT> __global__ void __launch_bounds__(NT) k_ip_round_wide(Batch B,
   st_sc((up ? jr : jl) + 8ull * ((n >> 1) + rank), mulq(hb, hfj));          // L: b_(i+half) hf_j for i < half; R: b_(i-half) hf_j for i >= half
 }
 
+// ---- the statements of a batch (bpmi_ipa_batch_prover_commit_batch): P_p = sum a_p[j] g_j + sum b_p[j] (c_j h_j) + t_p u, a loop of
+// vector_commitment(g, h, a_p, b_p) (src/utils/commitments.py:13) plus inner_product(a, b) * u.  This kernel only lays out the scalars:
+// job p of k_pv_msm over the base list of ipp_commit_bases takes the row [a_p | b_p c_j | t_p] of T terms (a NULL half is left out,
+// u_mode 0 has no t_p); the points come from the prover's tables.
+struct Commit {
+  u32 count, n, T;
+  u32 u_mode;                // 0: no u term; 1: t_p = <a_p, b_p> over the UNSCALED b, summed here; 2: t_p = t_in[p]
+  const u32 *a_in, *b_in;    // count x n scalars each; one of them may be nullptr
+  const u32 *t_in;           // count scalars (u_mode 2)
+  const u32 *hscale;         // n scalars c_j, or nullptr
+  u32 *jsc;                  // count x T
+};
+__device__ __forceinline__ sc sc_shfl_xor(const sc &a, int mask) {
+  sc r;
+#pragma unroll
+  for (int i = 0; i < 8; i++) r.v[i] = (u32)__shfl_xor((int)a.v[i], mask, 64);
+  return r;
+}
+// n lanes per proof in blocks of NT (the plan's rule: a proof never straddles a block; n <= 64 divides a wave).  The branches on u_mode,
+// the NULL halves and n are uniform over the launch, so every lane of a block -- those of proofs beyond `count` in the last block
+// included, which carry zeros -- reaches every shuffle and the barrier.  The dot of u_mode 1: a butterfly of shuffles over the
+// min(n, 64) lanes a proof has in a wave; for n > 64 the n / 64 wave sums meet in LDS and the proof's first wave adds them with the
+// same butterfly.
+template <u32 NT> __global__ void __launch_bounds__(NT) k_ip_commit_scalars(Commit C) {
+  __shared__ u32 s_w[(NT / 64u) * 8u];
+  const u32 n = C.n, tid = threadIdx.x;
+  const u32 p = blockIdx.x * (NT / n) + tid / n, j = tid & (n - 1u);
+  const bool live = p < C.count;
+  const size_t e = (size_t)p * n + j;
+  u32 *row = C.jsc + 8ull * (size_t)p * C.T;
+  const u32 off_b = C.a_in ? n : 0u, off_t = off_b + (C.b_in ? n : 0u);
+  sc aj = sc_u32(0), bj = sc_u32(0);
+  if (live) {
+    if (C.a_in) { aj = ld_sc(C.a_in + 8ull * e); st_sc(row + 8ull * j, aj); }
+    if (C.b_in) { bj = ld_sc(C.b_in + 8ull * e); st_sc(row + 8ull * (off_b + j), C.hscale ? mulq(bj, ld_sc(C.hscale + 8ull * j)) : bj); }
+  }
+  if (C.u_mode == 2u) {
+    if (live && j == 0u) st_sc(row + 8ull * off_t, ld_sc(C.t_in + 8ull * p));
+    return;
+  }
+  if (C.u_mode != 1u) return;
+  sc acc = mulq(aj, bj);                                     // (a dead lane: 0 x 0)
+  const u32 in_wave = n < 64u ? n : 64u;
+  for (u32 d = 1; d < in_wave; d <<= 1) acc = addq(acc, sc_shfl_xor(acc, (int)d));
+  if (n > 64u) {
+    const u32 wave = tid >> 6, waves = n >> 6;               // waves per proof: 2 .. 16
+    if ((tid & 63u) == 0u) st_sc(s_w + 8u * wave, acc);
+    __syncthreads();
+    acc = j < waves ? ld_sc(s_w + 8u * ((tid - j) / 64u + j)) : sc_u32(0);
+    for (u32 d = 1; d < waves; d <<= 1) acc = addq(acc, sc_shfl_xor(acc, (int)d));
+  }
+  if (live && j == 0u) st_sc(row + 8ull * off_t, acc);
+}
+
 }  // namespace ipp

@@ -1,7 +1,8 @@
 // ipa_prove_plan_host.hpp -- part of libbpmi; plain C++17 (no HIP, no bpmi_ctx), also compiled for the host by tests/csrc_host.
 // The plan of a batched inner-product prover as a pure function of (vector length, option values): the argument errors, the block
 // size of the n-lanes-per-proof kernel, the window bits and the size of the fixed-base tables, the per-call caps, the bound of a
-// proof's transcript text and the base lists of every job kind.  tests/test_ipa_prove_plan_cpu.py checks it without a GPU;
+// proof's transcript text and the base lists of every job kind -- at the end those of the statements call (ipp_commit_error,
+// ipp_commit_bases; tests/test_ipa_commit_plan_cpu.py).  tests/test_ipa_prove_plan_cpu.py checks it without a GPU;
 // ipa_prove_host.hpp consumes it.  The geometry is the range prover's (rp_prove_plan_host.hpp): the same tables over 2n + 1 bases
 // instead of 2n + 3, the same block sizes, caps and job-lane rule.
 #pragma once
@@ -109,3 +110,41 @@ static inline const char *ipp_cap_error(u32 k, int protocol, uint64_t n_proofs, 
 
 // log2 of the lanes k_pv_msm gives a job: the range prover's rule (rpp_job_lanes_log2), a round's launch has 2 x proofs jobs
 static inline int ipp_job_lanes_log2(u32 n, uint64_t njobs, int opt) { return rpp_job_lanes_log2(n, njobs, opt); }
+
+// ---- the statements of a batch (bpmi_ipa_batch_prover_commit_batch): out[p] = sum a_p[j] g_j + sum b_p[j] (c_j h_j) + t_p u -------------
+// which arrays a call hands in (true: non-NULL), and its u_mode: 0 no u term, 1 t_p = <a_p, b_p> summed on the device, 2 t given
+struct IppCommitCall {
+  bool pv = false, out = false, a = false, b = false, t = false;
+  int u_mode = 0;
+};
+// nullptr, or the text of the BPMI_E_ARG: the NULL rules and u_mode, before anything is read
+static inline const char *ipp_commit_error(const IppCommitCall &c) {
+  if (!c.pv) return "null argument (pv)";
+  if (!c.out) return "null argument (out)";
+  if (c.u_mode < 0 || c.u_mode > 2) return "u_mode must be 0 (no u term), 1 (t = <a, b>) or 2 (t given)";
+  if (c.u_mode != 2 && c.t) return "t must be NULL unless u_mode is 2";
+  if (c.u_mode == 2 && !c.t) return "null argument (u_mode 2 takes t)";
+  if (!c.a && !c.b) return "a and b are both NULL (one of them may be: all zeros)";
+  if (c.u_mode == 1 && (!c.a || !c.b)) return "u_mode 1 sums <a, b>: it takes both a and b";
+  return nullptr;
+}
+// the base list of a statement's job: g_0 .. g_(n-1) (bases 1 + j) when a is given, h_0 .. h_(n-1) (1 + n + j) when b is, then u (0)
+// LAST: of 2n + 1 terms it is the one that does not fill a round of the job's 16 lanes, the remainder term k_pv_msm shares out by
+// windows.  A NULL half is dropped from the list, not multiplied by zero.
+static inline std::vector<unsigned short> ipp_commit_bases(u32 n, bool have_a, bool have_b, bool have_u) {
+  std::vector<unsigned short> bl;
+  bl.reserve((size_t)n * ((have_a ? 1u : 0u) + (have_b ? 1u : 0u)) + (have_u ? 1u : 0u));
+  if (have_a) for (u32 j = 0; j < n; j++) bl.push_back((unsigned short)(1 + j));
+  if (have_b) for (u32 j = 0; j < n; j++) bl.push_back((unsigned short)(1 + n + j));
+  if (have_u) bl.push_back(0);
+  return bl;
+}
+// the device copy: the lists (a, b, u), (a, u), (b, u) one after the other; a call without a u term takes its list one entry short
+static inline u32 ipp_commit_bases_offset(u32 n, bool have_a, bool have_b) { return have_a && have_b ? 0u : have_a ? 2u * n + 1u : 3u * n + 2u; }
+static inline std::vector<unsigned short> ipp_commit_bases_all(u32 n) {
+  std::vector<unsigned short> all = ipp_commit_bases(n, true, true, true);
+  const std::vector<unsigned short> a_only = ipp_commit_bases(n, true, false, true), b_only = ipp_commit_bases(n, false, true, true);
+  all.insert(all.end(), a_only.begin(), a_only.end());
+  all.insert(all.end(), b_only.begin(), b_only.end());
+  return all;
+}

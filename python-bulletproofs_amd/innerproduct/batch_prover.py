@@ -8,6 +8,8 @@ device.  Same proofs, field for field:
     bp = BatchInnerProductProver(g, h, u)
     proofs1 = bp.prove1(Ps, cs, as_, bs, seeds)         # proofs1[i] == NIProver(g, h, u, Ps[i], cs[i], as_[i], bs[i], group, seeds[i]).prove()
     proofs2 = bp.prove2(as_, bs, transcripts)           # proofs2[i] == FastNIProver2(g, h, u, P_i, as_[i], bs[i], group, transcripts[i]).prove()
+    Ps = bp.commit(as_, bs)                             # Ps[i] == vector_commitment(g, h, as_[i], bs[i]): prove1's statements, from the same tables
+    Ps2 = bp.commit(as_, bs, "inner")                   # ... + <as_[i], bs[i]> * u: the statements of proofs2
     bp.close()
 
 What BatchInnerProductVerifier consumes.  Vectors of 1 .. 1 024 elements (a power of two); longer ones stay with the single-proof
@@ -15,7 +17,7 @@ provers, where one proof fills the chip on its own."""
 import ctypes
 
 from .. import engine as _engine
-from ..ec import Point, pack_points, pack_scalars, secp256k1
+from ..ec import Point, pack_points, pack_scalars, secp256k1, unpack_points
 from ..utils.utils import ModP
 from .inner_product_verifier import Proof1, Proof2
 
@@ -148,6 +150,49 @@ class BatchInnerProductProver:
             transcripts = [sb[offs[i]: offs[i + 1]] for i in range(len(trs))]
         starts = [len(t.split(b"&")) if t else 1 for t in (transcripts or [None] * len(trs))]
         return [self._proof2(i, ab, xs, lr, tr, starts[i]) for i, tr in enumerate(trs)]
+
+    # ---- the statements ------------------------------------------------------------------------------------------------------
+    def commit_packed(self, as_, bs, u_term=None):
+        """The statements of a batch from the prover's tables, in one device call (bpmi_ipa_batch_prover_commit_batch): 64 bytes per
+        statement, P_p = sum as_[p][j] g[j] + sum bs[p][j] (h_scale[j] h[j]) + t_p u -- a loop of vector_commitment(g, h, a, b)
+        (reference: src/utils/commitments.py:13) plus inner_product(a, b) * u.  as_, bs: lists of n-element vectors or packed bytes,
+        either may be None (all zeros).  u_term: None -- no u term, the P that prove1 and Verifier1 take; "inner" -- t_p = <a_p, b_p>
+        (over the unscaled b), the P under which prove2's proofs verify; or one scalar per statement, a list or packed bytes."""
+        if as_ is None and bs is None:
+            raise ValueError("as_ and bs are both None (one of them may be: all zeros)")
+        ab, count = (None, None) if as_ is None else _rows(as_, self.n, "as_")
+        bb, count_b = (None, None) if bs is None else _rows(bs, self.n, "bs")
+        if ab is not None and bb is not None and count_b != count:
+            raise ValueError("as_ and bs must have the same length")
+        count = count_b if count is None else count
+        tb, mode = None, 0
+        if isinstance(u_term, str):
+            if u_term != "inner":
+                raise ValueError('u_term is None, "inner", or one scalar per statement')
+            if ab is None or bb is None:
+                raise ValueError('u_term = "inner" sums <a, b>: it takes both as_ and bs')
+            mode = 1
+        elif u_term is not None:
+            tb, mode = (bytes(u_term) if _is_bytes(u_term) else pack_scalars(u_term, Q)), 2
+            if len(tb) != 32 * count:
+                raise ValueError("u_term must hold one scalar per statement")
+        if count == 0:
+            return b""
+        eng = self._engine
+        out = ctypes.create_string_buffer(64 * count)
+        eng._ck(eng.lib.bpmi_ipa_batch_prover_commit_batch(self._handle, count, ab, bb, mode, tb, ctypes.cast(out, ctypes.c_void_p)))
+        return out.raw
+
+    def commit(self, as_, bs, u_term=None):
+        """[Point]: commit_packed's statements as points."""
+        raw = self.commit_packed(as_, bs, u_term)
+        return unpack_points(raw, len(raw) // 64)
+
+    def commit_last_ms(self):
+        """Of the last commit: device milliseconds of its kernels, and the whole call (bpmi_ipa_batch_prover_commit_last_ms)."""
+        ms = (ctypes.c_double * 2)()
+        self._engine._ck(self._engine.lib.bpmi_ipa_batch_prover_commit_last_ms(self._handle, ms))
+        return dict(zip(("device", "call"), ms))
 
     def last_ms(self):
         """Device milliseconds of the last batch by phase (bpmi_ipa_batch_prover_last_ms)."""
