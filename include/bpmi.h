@@ -435,6 +435,37 @@ int bpmi_ipa_verify_batch_dev(bpmi_ctx *ctx, const void *d_g, const void *d_h, c
                               const uint8_t *weights, const uint8_t *extra_pts, const uint8_t *extra_scalars, uint64_t n_extra,
                               uint8_t out[64]);
 
+/* ---- a batch of inner-product proofs of DIFFERENT lengths over the prefixes of one generator list, in one MSM ----------------
+ * A generator list is a capacity: a statement of n_p = 2^k_p elements is made over g[:n_p], h[:n_p] (and c[:n_p]), and its verifier is
+ * Verifier2 over those prefixes (src/innerproduct/inner_product_verifier.py:127-147), with s_{p,i} from the proof's own k_p challenges
+ * (get_ss, :91-102; MSB first over k_p bits).  Under the weights of bpmi_ipa_verify_batch_dev generator i collects the proofs that
+ * reach it:
+ *   SA_i = sum_{p : n_p > i} w_p a_p s_{p,i},   SB_i = c_i sum_{p : n_p > i} w_p b_p s_{p,i}^-1,   i < n_top = max_p n_p
+ * so proofs of 64, 256 and 4 096 elements are ONE MSM of 2 n_top + (extra pairs) and sum_p n_p x 2 multiplications mod q, not one
+ * batch per length.  The MSM reads the first n_top generators only.
+ *   n_gens       the capacity: 2^K points in d_g and d_h each (scalars in scale / d_hscale), K <= 22
+ *   ks           n_proofs round counts k_p, in any order; every k_p <= K
+ *   xs, xinvs    sum_p k_p x 32 bytes: proof after proof in the order of ks, each proof's k_p challenges (NULL allowed when every k_p = 0)
+ *   a, b, weights   n_proofs x 32 bytes, values in [0, q), in the order of ks
+ * Per call: 1 <= n_proofs <= 2^16; sum_p n_p <= 2^32; the half tables (64 (2^(k_p/2) + 2^(k_p - k_p/2)) bytes per proof) at most 1 GiB; at
+ * most 2^22 extra points.  A call outside these bounds is refused with BPMI_E_ARG before anything is allocated.  One call at a time per ctx.
+ *
+ * SA, SB of a mixed batch, to host memory.  scale: n_gens x 32 bytes (the first n_top are read) or NULL; sa, sb: room for
+ * n_top = 2^max(k_p) scalars each; *n_top: that count.  For proofs of ONE length the bytes are those of bpmi_sc_svector_sum. */
+int bpmi_sc_svector_sum_mixed(bpmi_ctx *ctx, uint64_t n_gens, uint64_t n_proofs, const uint32_t *ks, const uint8_t *xs, const uint8_t *xinvs,
+                              const uint8_t *a, const uint8_t *b, const uint8_t *weights, const uint8_t *scale, uint8_t *sa, uint8_t *sb,
+                              uint64_t *n_top);
+/* The whole mixed batch over generators in device memory (n_gens points each, d_hscale: n_gens scalars or NULL):
+ *   out = sum_{i < n_top} SA_i g_i + sum_{i < n_top} SB_i h_i + sum_t extra_scalars[t] * extra_pts[t]
+ * the identity (64 zero bytes) iff every weighted equation holds.  The extra pairs follow the contract of bpmi_ipa_verify_batch_dev:
+ * already multiplied by their proof's weight, the library does not know their owner.  Points are checked as there (option
+ * "validate_points": the extra points at level 1, the first n_top generators at level 2); a call refused for a point leaves 0xFF.. in
+ * out, never the identity. */
+int bpmi_ipa_verify_batch_mixed_dev(bpmi_ctx *ctx, const void *d_g, const void *d_h, const void *d_hscale, uint64_t n_gens, uint64_t n_proofs,
+                                    const uint32_t *ks, const uint8_t *xs, const uint8_t *xinvs, const uint8_t *a, const uint8_t *b,
+                                    const uint8_t *weights, const uint8_t *extra_pts, const uint8_t *extra_scalars, uint64_t n_extra,
+                                    uint8_t out[64]);
+
 /* ---- inner-product argument prover, split at the Fiat-Shamir edge ----------------------
  * One object = one run of FastNIProver2.prove (src/innerproduct/inner_product_prover.py:70-110).
  * g, h: n points; a, b: n scalars; u: one point; all copied to the device once and kept

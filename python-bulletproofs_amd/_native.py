@@ -62,6 +62,8 @@ SIGNATURES = {
     "bpmi_ipa_verify_dev": (_i, [_vp, _vp, _vp, _vp, _u64, _cp, _cp, ctypes.c_uint32, _cp, _cp, _cp, _cp, _u64, _cp]),
     "bpmi_sc_svector_sum": (_i, [_vp, ctypes.c_uint32, _u64, _cp, _cp, _cp, _cp, _cp, _cp, _cp, _cp]),
     "bpmi_ipa_verify_batch_dev": (_i, [_vp, _vp, _vp, _vp, _u64, _u64, _cp, _cp, ctypes.c_uint32, _cp, _cp, _cp, _cp, _cp, _u64, _cp]),
+    "bpmi_sc_svector_sum_mixed": (_i, [_vp, _u64, _u64, ctypes.POINTER(ctypes.c_uint32), _cp, _cp, _cp, _cp, _cp, _cp, _cp, _cp, ctypes.POINTER(_u64)]),
+    "bpmi_ipa_verify_batch_mixed_dev": (_i, [_vp, _vp, _vp, _vp, _u64, _u64, ctypes.POINTER(ctypes.c_uint32), _cp, _cp, _cp, _cp, _cp, _cp, _cp, _u64, _cp]),
     "bpmi_ipa_create": (_i, [_vp, _cp, _cp, _cp, _cp, _u64, _cp, ctypes.POINTER(_vp)]),
     "bpmi_ipa_create_scaled": (_i, [_vp, _cp, _cp, _cp, _cp, _u64, _cp, _cp, ctypes.POINTER(_vp)]),
     "bpmi_ipa_create_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _cp, ctypes.POINTER(_vp)]),

@@ -61,6 +61,7 @@ using namespace bpmi;
 #include "rp_prove_plan_host.hpp"
 #include "ipa_prove_plan_host.hpp"
 #include "ipa_batch_plan_host.hpp"
+#include "ipa_mixed_plan_host.hpp"
 #include "ipa_packed_plan_host.hpp"
 #include "msm_batch_plan_host.hpp"
 #include "msm_fixed_plan_host.hpp"
@@ -72,7 +73,9 @@ using namespace bpmi;
 #include "point_kernels.hpp"
 #include "point_check_host.hpp"
 #include "svector_batch.hpp"
+#include "svector_mixed.hpp"
 #include "scalar_kernels.hpp"
+#include "ipa_mixed_kernels.hpp"
 #include "host_tail.hpp"
 #include "msm_host.hpp"
 #include "msm_fixed_host.hpp"
@@ -894,6 +897,7 @@ int bpmi_ipa_verify_dev(bpmi_ctx *ctx, const void *d_g, const void *d_h, const v
 
 #include "ipa_host.hpp"
 #include "ipa_batch_host.hpp"
+#include "ipa_mixed_host.hpp"
 #include "ipa_packed_dev_host.hpp"
 #include "msm_batch_host.hpp"
 #include "rp_batch_dev_host.hpp"

@@ -306,6 +306,25 @@ class Engine:
                                                     xs, xinvs, k, a, b, weights, extra_pts, extra_scalars, n_extra, out))
         return out.raw
 
+    def sc_svector_sum_mixed_bytes(self, n_gens, ks, xs, xinvs, a, b, weights, scale=None):
+        """(SA, SB) of bpmi_sc_svector_sum_mixed as packed bytes, n_top = 2^max(ks) scalars each: the weighted sums of the s-vectors of
+        proofs of different lengths 2^ks[p] over the prefixes of n_gens generators.  xs, xinvs: every proof's ks[p] packed challenges,
+        proof after proof; a, b, weights: one packed scalar per proof; scale: n_gens packed scalars or None."""
+        n = 1 << min(max(ks, default=0), 22)           # (a longer proof is refused by the call)
+        sa, sb, n_top = ctypes.create_string_buffer(32 * n), ctypes.create_string_buffer(32 * n), ctypes.c_uint64(0)
+        self._ck(self.lib.bpmi_sc_svector_sum_mixed(self.ctx, n_gens, len(ks), (ctypes.c_uint32 * max(len(ks), 1))(*ks), xs, xinvs, a, b, weights, scale,
+                                                    sa, sb, ctypes.byref(n_top)))
+        return sa.raw[:32 * n_top.value], sb.raw[:32 * n_top.value]
+
+    def ipa_verify_batch_mixed_dev(self, d_g, d_h, n_gens, ks, xs, xinvs, a, b, weights, extra_pts, extra_scalars, n_extra, d_hscale=None):
+        """The 64-byte value of a batch of Verifier2 checks of different lengths 2^ks[p] over the prefixes of n_gens device-resident
+        generators under the given weights (identity = every proof accepted); argument forms as ipa_verify_batch_dev."""
+        out = ctypes.create_string_buffer(64)
+        self._ck(self.lib.bpmi_ipa_verify_batch_mixed_dev(self.ctx, _ptr(d_g), _ptr(d_h), None if d_hscale is None else _ptr(d_hscale), n_gens, len(ks),
+                                                          (ctypes.c_uint32 * max(len(ks), 1))(*ks), xs, xinvs, a, b, weights, extra_pts, extra_scalars,
+                                                          n_extra, out))
+        return out.raw
+
     # ---- packed inner-product proofs (what bpmi_ipa_prove_batch writes) ----
     def ipa_batch_prepare_dev(self, k, protocol, count, ab, xs, lr, transcripts, starts, u, P, c=None, head=None, weights=None, seed=None):
         """(records, extra_pts, extra_scalars, status) of bpmi_ipa_batch_prepare_dev as bytes: the per-proof preparation of the packed

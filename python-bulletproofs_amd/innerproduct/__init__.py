@@ -1,7 +1,9 @@
 from .inner_product_prover import NIProver, FastNIProver2
 from .inner_product_verifier import Proof1, Proof2, Verifier1, Verifier2
 from .batch import BatchInnerProductVerifier, batch_verify_inner_products, locate_by_bisection
+from .batch_mixed import MixedBatchInnerProductVerifier, batch_verify_inner_products_mixed
 from .batch_prover import BatchInnerProductProver
 
 __all__ = ["NIProver", "FastNIProver2", "Proof1", "Proof2", "Verifier1", "Verifier2",
-           "BatchInnerProductVerifier", "batch_verify_inner_products", "locate_by_bisection", "BatchInnerProductProver"]
+           "BatchInnerProductVerifier", "batch_verify_inner_products", "locate_by_bisection", "BatchInnerProductProver",
+           "MixedBatchInnerProductVerifier", "batch_verify_inner_products_mixed"]
