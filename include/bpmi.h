@@ -799,6 +799,61 @@ int bpmi_ipa_verify_batch_packed_dev(bpmi_ctx *ctx, const void *d_g, const void 
                                      const uint32_t *start, const uint8_t *u, const uint8_t *P, const uint8_t *c, const uint8_t *head, const uint8_t *weights,
                                      const uint8_t *seed, uint8_t out[64], uint8_t *status);
 
+/* ---- packed inner-product proofs of DIFFERENT lengths: a list of classes, one MSM ------------------------------------------
+ * The packed verifier above for proofs over the PREFIXES of one generator list (the statements of bpmi_ipa_verify_batch_mixed_dev:
+ * Verifier2 / Verifier1 over g[:n], h[:n], src/innerproduct/inner_product_verifier.py:104-147 and :44-58, with get_ss, :91-102, over the
+ * proof's own k challenges).  A CLASS is what one call of bpmi_ipa_verify_batch_packed_dev takes -- n_proofs packed proofs of one
+ * n = 2^k, e.g. the arrays one bpmi_ipa_batch_prover wrote -- and a call takes 1 .. 64 classes, in any order of k, several of one k
+ * allowed.  Every class is prepared on the device (the re-hash, the byte-level checks, one inversion per proof, the weighted scalars:
+ * one launch per round over the row chunks of ALL classes, csrc/ipa_packed_kernels.hpp), then the batch is the one mixed s-vector sum
+ * and the ONE MSM of bpmi_ipa_verify_batch_mixed_dev.  No host loop over proofs.
+ *   protocol     1 or 2, one per call.  Protocol 1: a class's u is that class's one point (64 B), checked on the host; protocol 2:
+ *                n_proofs x 64 B.  The NULL / non-NULL rules of every class are those of the single-class call.
+ *   classes      a class with n_proofs = 0 is legal and skipped: its pointers are not read.  If every class is empty the verify call
+ *                writes the identity, the preparation calls touch nothing, and both return BPMI_OK.
+ *   numbering    proofs are numbered CLASS-MAJOR over the call, class 0's first.  That global index addresses `status` (one byte per
+ *                proof, bits as above), the explicit `weights` (1 x 32 B per proof under protocol 2, 3 x 32 B under protocol 1) and
+ *                is the index of a seed-derived weight: SHA-256(seed || LE64(global index) || t) cut to 248 bits, 0 -> 1.
+ *   validity     of a packed proof: unchanged, with the proof's own k, over the first 2^k generators.
+ * Outputs of the preparation (K: the capacity, n_gens = 2^K; every k <= K):
+ *   extra_pts, extra_scalars   the classes' blocks back to back in the CALLER's class order; inside a block proof-major, 2k + 2
+ *                (protocol 2) or 2k + 4 (protocol 1) pairs per proof in the pair order above
+ *   records      the classes' blocks (16k + 24 words per proof) in the order the mixed s-vector sum reads them: descending k, stable
+ *                among equal k -- a class's proofs stay contiguous.  rec_byte_off[c] (n_classes entries): the byte offset of class
+ *                c's block (0 for an empty class)
+ *   a flagged proof contributes nothing: zero record, zero scalars, identity points.
+ * The verify call: out = the one combination over [g[:n_top] | h[:n_top] | every class's extra pairs], n_top = 2^max k; the batch is
+ * valid iff every status byte is 0 and out is 64 zero bytes.  Generators are checked as in bpmi_ipa_verify_batch_mixed_dev (the first
+ * n_top at "validate_points" = 2); a call refused for a point leaves 0xFF.. in out.
+ * BPMI_E_ARG before anything is read beyond tr_off, allocated or uploaded, and no output is written (the message names the class
+ * where there is one): n_classes outside 1 .. 64 or a NULL classes; K > 22 or a k above K; a class the single-class call refuses;
+ * more than 2^16 proofs, 2^32 elements (the sum of 2^k), 1 GiB of half tables, 2^22 extra pairs or 4 GiB of transcripts in total.
+ * One call at a time per ctx.
+ *   bpmi_ipa_batch_prepare_mixed       HOST code on `threads` threads over the whole call, no ctx (message: bpmi_last_error(NULL))
+ *   bpmi_ipa_batch_prepare_mixed_dev   the same bytes (tests/test_gpu_ipa_packed_mixed.py) by the kernels, into device memory;
+ *                                      rec_byte_off and status to the host
+ *   bpmi_ipa_verify_batch_packed_mixed_dev   the whole verification */
+typedef struct bpmi_ipa_packed_class {
+  uint32_t k;                 /* n = 2^k elements, over g[:n], h[:n] (, c[:n]) */
+  uint64_t n_proofs;
+  const uint8_t *ab, *xs, *LR, *transcripts;      /* exactly the arrays of bpmi_ipa_verify_batch_packed_dev for this class */
+  const uint64_t *tr_off;
+  const uint32_t *start;
+  const uint8_t *u, *P, *c, *head;
+} bpmi_ipa_packed_class;
+int bpmi_ipa_batch_prepare_mixed(uint32_t K, int protocol, uint32_t n_classes, const bpmi_ipa_packed_class *classes, const uint8_t *weights,
+                                 const uint8_t *seed, int threads, uint8_t *records, uint64_t *rec_byte_off, uint8_t *extra_pts,
+                                 uint8_t *extra_scalars, uint8_t *status);
+int bpmi_ipa_batch_prepare_mixed_dev(bpmi_ctx *ctx, uint32_t K, int protocol, uint32_t n_classes, const bpmi_ipa_packed_class *classes,
+                                     const uint8_t *weights, const uint8_t *seed, void *d_records, uint64_t *rec_byte_off, void *d_extra_pts,
+                                     void *d_extra_scalars, uint8_t *status);
+int bpmi_ipa_verify_batch_packed_mixed_dev(bpmi_ctx *ctx, const void *d_g, const void *d_h, const void *d_hscale, uint64_t n_gens, int protocol,
+                                           uint32_t n_classes, const bpmi_ipa_packed_class *classes, const uint8_t *weights, const uint8_t *seed,
+                                           uint8_t out[64], uint8_t *status);
+/* test hook (not part of the drop-in surface): the byte budget of the transposed transcripts of ONE round of the mixed packed calls
+ * on this ctx (0: the default, 2^28) -- a small value makes a few hundred proofs run as several rounds.  Not an option. */
+int bpmi_debug_ipap_t_budget(bpmi_ctx *ctx, uint64_t bytes);
+
 /* Page-locked host memory (hipHostMalloc) for buffers handed to the library repeatedly, e.g. the receive buffer of wire proofs. */
 int bpmi_host_alloc(bpmi_ctx *ctx, size_t bytes, void **out);
 int bpmi_host_free(bpmi_ctx *ctx, void *p);

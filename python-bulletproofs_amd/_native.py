@@ -100,6 +100,11 @@ SIGNATURES = {
     "bpmi_ipa_batch_prepare": (_i, [ctypes.c_uint32, _i, _u64, _cp, _cp, _cp, _cp, _vp, _vp, _cp, _cp, _cp, _cp, _cp, _cp, _i, _vp, _vp, _vp, _vp]),
     "bpmi_ipa_batch_prepare_dev": (_i, [_vp, ctypes.c_uint32, _i, _u64, _cp, _cp, _cp, _cp, _vp, _vp, _cp, _cp, _cp, _cp, _cp, _cp, _vp, _vp, _vp, _vp]),
     "bpmi_ipa_verify_batch_packed_dev": (_i, [_vp, _vp, _vp, _vp, _u64, _i, _u64, _cp, _cp, _cp, _cp, _vp, _vp, _cp, _cp, _cp, _cp, _cp, _cp, _vp, _vp]),
+    # (K | ctx, K | ctx, g, h, hscale, n_gens), protocol, n_classes, classes (an array of IpaPackedClass), weights, seed, ...
+    "bpmi_ipa_batch_prepare_mixed": (_i, [ctypes.c_uint32, _i, ctypes.c_uint32, _vp, _cp, _cp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "bpmi_ipa_batch_prepare_mixed_dev": (_i, [_vp, ctypes.c_uint32, _i, ctypes.c_uint32, _vp, _cp, _cp, _vp, _vp, _vp, _vp, _vp]),
+    "bpmi_ipa_verify_batch_packed_mixed_dev": (_i, [_vp, _vp, _vp, _vp, _u64, _i, ctypes.c_uint32, _vp, _cp, _cp, _vp, _vp]),
+    "bpmi_debug_ipap_t_budget": (_i, [_vp, _u64]),
     "bpmi_host_alloc": (_i, [_vp, ctypes.c_size_t, ctypes.POINTER(_vp)]),
     "bpmi_host_free": (_i, [_vp, _vp]),
     "bpmi_ipa_destroy": (None, [_vp]),
@@ -121,6 +126,12 @@ class RpClass(ctypes.Structure):
     structure keeps the objects behind them alive for the call."""
     _fields_ = [("n_gens", ctypes.c_uint32), ("values_per_proof", ctypes.c_uint32), ("n_proofs", ctypes.c_uint64), ("blobs", ctypes.c_void_p),
                 ("blobs_len", ctypes.c_uint64), ("blob_off", ctypes.c_void_p), ("v_points", ctypes.c_void_p)]
+
+
+class IpaPackedClass(ctypes.Structure):
+    """bpmi_ipa_packed_class (include/bpmi.h): one class of the mixed packed inner-product calls.  Plain addresses, as RpClass."""
+    _fields_ = [("k", ctypes.c_uint32), ("n_proofs", ctypes.c_uint64)] + [(name, ctypes.c_void_p) for name in
+                ("ab", "xs", "LR", "transcripts", "tr_off", "start", "u", "P", "c", "head")]
 
 
 class NativeLibraryMissing(RuntimeError):

@@ -9,29 +9,20 @@
 
 extern "C" {
 
-// the records (sorted order), descriptors, C table, units and block index assembled on the host and uploaded as one piece, then the
-// launches that leave SA and SB in the workspace
-static int ipam_svector_sum(bpmi_ctx *ctx, const IpamPlan &pl, const u32 *ks, const void *d_scale, const uint8_t *xs, const uint8_t *xinvs, const uint8_t *a,
-                            const uint8_t *b, const uint8_t *weights) {
+// the three launches that leave SA and SB in the workspace, from the proofs' records (sorted order) that are in the workspace
+// already: uploaded by ipam_svector_sum, or written there by the preparation kernels (ipa_packed_mixed_dev_host.hpp).  Only the control
+// regions -- descriptors, C table, units, block index -- are uploaded here, as one piece.
+static int ipam_svector_launches(bpmi_ctx *ctx, const IpamPlan &pl, const void *d_scale) {
   char *base = (char *)ctx->stage_in;
   const u32 P = (u32)pl.n_proofs;
-  std::vector<uint8_t> head(pl.o_tab - pl.o_rec);
-  uint8_t *at = head.data();
-  std::vector<uint64_t> first(P);                           // proof p's challenges start at pair first[p] of xs / xinvs
-  uint64_t pairs = 0;
-  for (u32 p = 0; p < P; p++) { first[p] = pairs; pairs += ks[p]; }
-  for (u32 s = 0; s < P; s++) {
-    const u32 p = pl.perm[s], k = ks[p];
-    uint8_t *r = at + 4 * (size_t)pl.desc[s].rec_off;
-    for (u32 j = 0; j < k; j++) { memcpy(r + 64 * j, xs + 32 * (first[p] + j), 32); memcpy(r + 64 * j + 32, xinvs + 32 * (first[p] + j), 32); }
-    memcpy(r + 64 * k, a + 32 * (size_t)p, 32); memcpy(r + 64 * k + 32, b + 32 * (size_t)p, 32); memcpy(r + 64 * k + 64, weights + 32 * (size_t)p, 32);
-  }
-  memcpy(at + (pl.o_desc - pl.o_rec), pl.desc.data(), pl.b_desc);
-  memcpy(at + (pl.o_ctab - pl.o_rec), pl.C.data(), pl.b_ctab);
-  memcpy(at + (pl.o_units - pl.o_rec), pl.unit.data(), pl.b_units);
-  memcpy(at + (pl.o_blocks - pl.o_rec), pl.block_first.data(), pl.b_blocks);
-  HIPCHK(ctx, h2d(ctx, base + pl.o_rec, head.data(), head.size(), ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));          // head is owned by this frame
+  std::vector<uint8_t> control(pl.o_tab - pl.o_desc);
+  uint8_t *at = control.data();
+  memcpy(at, pl.desc.data(), pl.b_desc);
+  memcpy(at + (pl.o_ctab - pl.o_desc), pl.C.data(), pl.b_ctab);
+  memcpy(at + (pl.o_units - pl.o_desc), pl.unit.data(), pl.b_units);
+  memcpy(at + (pl.o_blocks - pl.o_desc), pl.block_first.data(), pl.b_blocks);
+  HIPCHK(ctx, h2d(ctx, base + pl.o_desc, control.data(), control.size(), ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));          // control (and the caller's records) are owned by host frames
   const u32 *desc = (const u32 *)(base + pl.o_desc), *tabs = (const u32 *)(base + pl.o_tab);
   u32 *sa = (u32 *)(base + pl.o_sa), *sb = (u32 *)(base + pl.o_sb), *part = (u32 *)(base + pl.o_part);
   const u32 n_top = (u32)pl.n_top;
@@ -48,6 +39,27 @@ static int ipam_svector_sum(bpmi_ctx *ctx, const IpamPlan &pl, const u32 *ks, co
   }
   HIPCHK(ctx, hipGetLastError());
   return BPMI_OK;
+}
+
+// the records assembled on the host in sorted order and uploaded, then the launches (whose wait covers this frame's buffer)
+static int ipam_svector_sum(bpmi_ctx *ctx, const IpamPlan &pl, const u32 *ks, const void *d_scale, const uint8_t *xs, const uint8_t *xinvs, const uint8_t *a,
+                            const uint8_t *b, const uint8_t *weights) {
+  char *base = (char *)ctx->stage_in;
+  const u32 P = (u32)pl.n_proofs;
+  std::vector<uint8_t> recs(4 * (size_t)pl.rec_words);
+  std::vector<uint64_t> first(P);                           // proof p's challenges start at pair first[p] of xs / xinvs
+  uint64_t pairs = 0;
+  for (u32 p = 0; p < P; p++) { first[p] = pairs; pairs += ks[p]; }
+  for (u32 s = 0; s < P; s++) {
+    const u32 p = pl.perm[s], k = ks[p];
+    uint8_t *r = recs.data() + 4 * (size_t)pl.desc[s].rec_off;
+    for (u32 j = 0; j < k; j++) { memcpy(r + 64 * j, xs + 32 * (first[p] + j), 32); memcpy(r + 64 * j + 32, xinvs + 32 * (first[p] + j), 32); }
+    memcpy(r + 64 * k, a + 32 * (size_t)p, 32); memcpy(r + 64 * k + 32, b + 32 * (size_t)p, 32); memcpy(r + 64 * k + 64, weights + 32 * (size_t)p, 32);
+  }
+  HIPCHK(ctx, h2d(ctx, base + pl.o_rec, recs.data(), recs.size(), ctx->stream));
+  const int rc = ipam_svector_launches(ctx, pl, d_scale);
+  if (rc) (void)hipStreamSynchronize(ctx->stream);         // recs is owned by this frame
+  return rc;
 }
 
 static bool ipam_challenges_missing(uint64_t n_proofs, const uint32_t *ks, const uint8_t *xs, const uint8_t *xinvs) {

@@ -85,8 +85,9 @@ static inline bool text_checks(u32 k, int protocol, uint64_t p, const IpaPackedI
   return true;
 }
 
-// proof p: its status byte; rec: 64 k + 96 bytes, pts / sc: ipap_pairs(k, protocol) x 64 / 32 bytes
-static inline uint8_t prepare_one(u32 k, int protocol, uint64_t p, const IpaPackedIn &in, uint8_t *rec, uint8_t *pts, uint8_t *sc, rp::Items &it) {
+// proof p: its status byte; rec: 64 k + 96 bytes, pts / sc: ipap_pairs(k, protocol) x 64 / 32 bytes.  gbase: a class of a mixed batch
+// (prepare_all_mixed): the call-wide index of the class's proof 0, added only to the index a seed weight is derived from
+static inline uint8_t prepare_one(u32 k, int protocol, uint64_t p, const IpaPackedIn &in, uint8_t *rec, uint8_t *pts, uint8_t *sc, rp::Items &it, uint64_t gbase = 0) {
   const u32 pairs = ipap_pairs(k, protocol);
   Sq a, b, c = rp::q_small(0), x1 = rp::q_small(0), xs[IPAB_K_MAX], xinv[IPAB_K_MAX], pre[IPAB_K_MAX];
   bool ok = load_lt_q(a, in.ab + 64 * p);
@@ -110,7 +111,7 @@ static inline uint8_t prepare_one(u32 k, int protocol, uint64_t p, const IpaPack
   Sq w[3];
   for (u32 t = 0; t < ipap_weights(protocol); t++) {
     if (in.weights) rp::q_from_le(w[t], in.weights + 32 * (ipap_weights(protocol) * p + t));
-    else rp::derive_weight(w[t], in.seed, p, (int)t);
+    else rp::derive_weight(w[t], in.seed, gbase + p, (int)t);
   }
   // one inversion for the k challenges (Montgomery's trick)
   Sq run = rp::q_small(1);
@@ -156,6 +157,43 @@ static inline void prepare_all(u32 k, int protocol, uint64_t n_proofs, const Ipa
   const uint64_t per = (n_proofs + T - 1) / T;
   for (uint64_t t = 0; t < T; t++) {
     const uint64_t lo = t * per, hi = lo + per < n_proofs ? lo + per : n_proofs;
+    if (lo < hi) pool.emplace_back(range, lo, hi);
+  }
+  for (auto &th : pool) th.join();
+}
+
+// ---- a MIXED batch: classes of different k in one call (include/bpmi.h, bpmi_ipa_batch_prepare_mixed).  The specification the
+// kernels k_ipap_roles_mixed / k_ipap_finish_mixed are compared with byte for byte (tests/test_gpu_ipa_packed_mixed.py).
+// One class: its arrays (in.weights: the class's slice of the explicit weights, or null), where its blocks of the outputs begin, and
+// the global index of its proof 0 (status and seed weights).
+struct MixedClass {
+  u32 k = 0;
+  uint64_t n_proofs = 0, gbase = 0;
+  IpaPackedIn in;
+  uint8_t *rec = nullptr, *pts = nullptr, *sc = nullptr;
+};
+// every proof of every class on `threads` host threads: contiguous ranges of the GLOBAL index, so the threads share the whole call,
+// not one class after the other; status: the call's array.  The arguments have passed ipa_packed_mixed_plan.
+static inline void prepare_all_mixed(int protocol, const std::vector<MixedClass> &cls, int threads, uint8_t *status) {
+  uint64_t total = 0;
+  for (const MixedClass &c : cls) total += c.n_proofs;
+  auto range = [&](uint64_t lo, uint64_t hi) {
+    rp::Items it;
+    for (const MixedClass &c : cls) {
+      const uint64_t a = lo > c.gbase ? lo - c.gbase : 0, b = hi < c.gbase + c.n_proofs ? (hi > c.gbase ? hi - c.gbase : 0) : c.n_proofs;
+      const u32 pairs = ipap_pairs(c.k, protocol);
+      const size_t rec_bytes = 64 * (size_t)c.k + 96;
+      for (uint64_t p = a; p < b; p++)
+        status[c.gbase + p] = prepare_one(c.k, protocol, p, c.in, c.rec + rec_bytes * p, c.pts + 64ull * pairs * p, c.sc + 32ull * pairs * p, it, c.gbase);
+    }
+  };
+  uint64_t T = threads < 1 ? 1 : (uint64_t)threads;
+  if (T > total) T = total ? total : 1;
+  if (T == 1) { range(0, total); return; }
+  std::vector<std::thread> pool;
+  const uint64_t per = (total + T - 1) / T;
+  for (uint64_t t = 0; t < T; t++) {
+    const uint64_t lo = t * per, hi = lo + per < total ? lo + per : total;
     if (lo < hi) pool.emplace_back(range, lo, hi);
   }
   for (auto &th : pool) th.join();

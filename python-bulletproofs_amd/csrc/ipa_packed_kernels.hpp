@@ -17,6 +17,8 @@
 //                  role 3  the inverse-free scalars: u (and u_new), L_j, P (and P_new, u)
 //   k_ipap_finish  one lane per extra pair: the status byte from the roles' verdicts; the pair's point copied (a valid proof) or
 //                  the identity, a zero scalar and a zero record (a flagged one: it contributes nothing)
+// A call over classes of different k (bpmi_ipa_verify_batch_packed_mixed_dev) runs the same bodies from k_ipap_roles_mixed -- one
+// launch over the row chunks of every class -- and k_ipap_finish_mixed; see "a MIXED batch" below.
 // Layout.  The fixed-size arrays (ab, xs, LR, P, ...) are read in place: a lane's 32- or 64-byte row is whole cache lines' worth
 // of aligned words, and a row is read once.  The transcripts are TRANSPOSED first (k_ipap_transpose, the layout of k_rp_transpose
 // with this ABI's 2^17-byte cap): the chain walks every transcript front to back, eight bytes at a time, and the proofs of a
@@ -41,6 +43,8 @@ struct Params {
   u32 *records;              // whole call: 16 k + 24 words per proof
   u32 *extra_sc;             // whole call: pairs x 8 words per proof
   uint8_t *roles;            // [role * Pall + proof]: 0 = passed, bit 0 / bit 1 as in the status byte
+  u64 gbase;                 // a class of a mixed batch (k_ipap_roles_mixed): the call-wide index of the class's proof 0 -- added only to the index a
+                             // seed weight is derived from; explicit weights and every array stay class-local.  0: one class
 };
 
 extern __shared__ u32 ipap_slots[];        // role 2: k prefix products of 9 limbs per lane, limb-major
@@ -188,7 +192,7 @@ __device__ __forceinline__ u32 role_text(const Params &q, const Proof &pr, bool 
 __device__ __forceinline__ sq weight_of(const Params &q, u64 G, u32 t) {
   sc ws;
   if (q.weights) ws = load_le_reduced(q.weights + 32 * ((q.protocol == 1 ? 3 : 1) * G + t));
-  else ws = derive_weight(q.seed, G, t);
+  else ws = derive_weight(q.seed, q.gbase + G, t);
   return to_sq(ws);
 }
 
@@ -276,9 +280,10 @@ __device__ __forceinline__ bool role_scalars(const Params &q, const Proof &pr, b
 }
 
 // Four waves per 64 proofs, one per role.  roles[role * Pall + proof] = the status bits that role found.
-__global__ void __launch_bounds__(64) k_ipap_roles(Params q) {
-  const u32 role = blockIdx.x & (IPAP_ROLES - 1);
-  const u32 g = (blockIdx.x / IPAP_ROLES) * 64 + threadIdx.x;
+// (the body of block `blk` of the launch: k_ipap_roles runs it for its own blocks, k_ipap_roles_mixed for the blocks of a unit)
+__device__ __forceinline__ void ipap_roles_block(const Params &q, u32 blk) {
+  const u32 role = blk & (IPAP_ROLES - 1);
+  const u32 g = (blk / IPAP_ROLES) * 64 + threadIdx.x;
   if (g >= q.P_launch) return;
   Proof pr;
   pr.G = q.first + g;
@@ -294,11 +299,11 @@ __global__ void __launch_bounds__(64) k_ipap_roles(Params q) {
   else bits = role_scalars(q, pr, too_long) ? 0u : 1u;
   q.roles[(size_t)role * q.Pall + pr.G] = (uint8_t)bits;
 }
+__global__ void __launch_bounds__(64) k_ipap_roles(Params q) { ipap_roles_block(q, blockIdx.x); }
 
-// One lane per extra pair of the call.  A proof some role flagged contributes nothing: identity points, zero scalars, a zero record.
-__global__ void __launch_bounds__(256) k_ipap_finish(Params q, u32 pairs, u32 *extra_pts, uint8_t *status) {
-  const u64 idx = (u64)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= (u64)q.Pall * pairs) return;
+// Extra pair `idx` (= proof * pairs + t) of the class q describes.  A proof some role flagged contributes nothing: identity points, zero
+// scalars, a zero record.  extra_pts: the class's block; status: the byte of the class's proof 0.
+__device__ __forceinline__ void ipap_finish_pair(const Params &q, u32 pairs, u64 idx, u32 *extra_pts, uint8_t *status) {
   const u32 p = (u32)(idx / pairs), t = (u32)(idx % pairs), k = q.k;
   u32 bits = 0;
 #pragma unroll
@@ -323,6 +328,46 @@ __global__ void __launch_bounds__(256) k_ipap_finish(Params q, u32 pairs, u32 *e
   }
   ::store_words16(extra_pts + 16 * idx, w);
   if (t == 0) status[p] = (uint8_t)bits;
+}
+// One lane per extra pair of the call.
+__global__ void __launch_bounds__(256) k_ipap_finish(Params q, u32 pairs, u32 *extra_pts, uint8_t *status) {
+  const u64 idx = (u64)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (u64)q.Pall * pairs) return;
+  ipap_finish_pair(q, pairs, idx, extra_pts, status);
+}
+
+// ---- a MIXED batch (bpmi_ipa_verify_batch_packed_mixed_dev, ipa_packed_mixed_dev_host.hpp): classes of different k in one call.
+// k_ipap_roles is single-wave serial chains and a class of a few hundred proofs fills a few percent of the chip: queued class after
+// class the chains of the classes would run one behind the other.  Here ONE launch runs the row chunks of every class of a round
+// (the shape of rpd::k_rp_roles_mixed): a device table of units {the class's Params for this round, the unit's first block}, read
+// with plain loads at an index that depends on blockIdx alone (uniform per block: scalar loads), then the SAME per-lane bodies.  A
+// class's records / extra_sc / roles pointers point at its own blocks, so the bodies' addressing holds unchanged.  The dynamic LDS
+// of the launch is that of the round's largest k (role 2's prefix products: k x 9 x 64 words).
+struct MixedUnit { Params q; u32 first_block, pad; };      // blocks [first_block, next unit's first_block) of the launch are this unit's
+static_assert(sizeof(MixedUnit) <= IPAPM_UNIT_STRIDE, "the plan lays the unit table out in IPAPM_UNIT_STRIDE-byte slots (ipa_packed_mixed_plan_host.hpp)");
+__device__ __forceinline__ const MixedUnit *mixed_unit_at(const uint8_t *units, u32 i) { return (const MixedUnit *)(units + (size_t)IPAPM_UNIT_STRIDE * i); }
+// the unit whose blocks hold blockIdx.x: the last one with first_block <= blockIdx.x (at most 64 units per round; the firsts ascend from 0)
+__global__ void __launch_bounds__(64) k_ipap_roles_mixed(const uint8_t *__restrict__ units, u32 n_units) {
+  u32 u = 0;
+  while (u + 1 < n_units && mixed_unit_at(units, u + 1)->first_block <= blockIdx.x) u++;
+  const MixedUnit *mu = mixed_unit_at(units, u);
+  const Params q = mu->q;
+  ipap_roles_block(q, blockIdx.x - mu->first_block);
+}
+// One lane per extra pair of the call; the lane's class by bisection over the pair offsets (n_cls + 1 ascending words, pair_off[0] = 0).
+// classes: slot j = the Params of non-empty class j (Pall = its proofs, gbase = its first global index; first_block is not used);
+// extra_pts: the call's array (the classes' blocks back to back); status: the call's array, global index.
+__global__ void __launch_bounds__(256) k_ipap_finish_mixed(const uint8_t *__restrict__ classes, const u32 *__restrict__ pair_off, u32 n_cls, u32 *extra_pts, uint8_t *status) {
+  const u64 idx = (u64)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= pair_off[n_cls]) return;
+  u32 lo = 0, hi = n_cls;                                     // pair_off[lo] <= idx < pair_off[hi]
+  while (hi - lo > 1) {
+    const u32 mid = (lo + hi) / 2;
+    if (pair_off[mid] <= idx) lo = mid; else hi = mid;
+  }
+  const Params q = mixed_unit_at(classes, lo)->q;
+  const u32 first = pair_off[lo];
+  ipap_finish_pair(q, 2u * q.k + (q.protocol == 1 ? 4u : 2u), idx - first, extra_pts + 16ull * first, status + q.gbase);
 }
 
 // T[w * P + g] = bytes [8w, 8w + 8) of the transcript of proof first + g for w < W, zero beyond its end (or beyond `cap`).  64 x 64

@@ -350,6 +350,38 @@ class Engine:
                                                            ctypes.cast(out, ctypes.c_void_p), ctypes.cast(status, ctypes.c_void_p)))
         return out.raw, status.raw[:count]
 
+    # ---- packed inner-product proofs of different lengths: a list of classes (bpmi_ipa_packed_class) ----
+    def ipa_batch_prepare_mixed_dev(self, K, protocol, classes, weights=None, seed=None):
+        """(records, rec_byte_off, extra_pts, extra_scalars, status) of bpmi_ipa_batch_prepare_mixed_dev: the preparation of a mixed packed
+        batch by the device kernels; argument forms as ipa_batch_prepare_mixed_host."""
+        arr, keep, total, rec_bytes, pairs = packed_class_array(protocol, classes)
+        d_rec, d_pts, d_sc = self.alloc(max(rec_bytes, 16)), self.alloc(max(64 * pairs, 16)), self.alloc(max(32 * pairs, 16))
+        status, offs = ctypes.create_string_buffer(max(total, 1)), (ctypes.c_uint64 * max(len(classes), 1))()
+        try:
+            self._ck(self.lib.bpmi_ipa_batch_prepare_mixed_dev(self.ctx, K, protocol, len(classes), ctypes.addressof(arr), weights, seed, d_rec.ptr,
+                                                               ctypes.addressof(offs), d_pts.ptr, d_sc.ptr, ctypes.cast(status, ctypes.c_void_p)))
+            return d_rec.download(rec_bytes), list(offs)[:len(classes)], d_pts.download(64 * pairs), d_sc.download(32 * pairs), status.raw[:total]
+        finally:
+            del keep
+            for d in (d_rec, d_pts, d_sc):
+                d.free()
+
+    def ipa_verify_batch_packed_mixed_dev(self, d_g, d_h, n_gens, protocol, classes, weights=None, seed=None, d_hscale=None):
+        """(out, status) of bpmi_ipa_verify_batch_packed_mixed_dev: the 64-byte value of the weighted combination over the unflagged
+        proofs of every class (identity = all of them verify) and one status byte per proof, class-major.  classes: a list of
+        (k, count, ab, xs, lr, transcripts, starts, u, P, c, head) -- per class the arguments of ipa_verify_batch_packed_dev."""
+        arr, keep, total, _, _ = packed_class_array(protocol, classes)
+        out, status = ctypes.create_string_buffer(64), ctypes.create_string_buffer(max(total, 1))
+        self._ck(self.lib.bpmi_ipa_verify_batch_packed_mixed_dev(self.ctx, _ptr(d_g), _ptr(d_h), None if d_hscale is None else _ptr(d_hscale), n_gens, protocol,
+                                                                 len(classes), ctypes.addressof(arr), weights, seed, ctypes.cast(out, ctypes.c_void_p),
+                                                                 ctypes.cast(status, ctypes.c_void_p)))
+        del keep
+        return out.raw, status.raw[:total]
+
+    def ipap_t_budget(self, nbytes):
+        """bpmi_debug_ipap_t_budget (tests): the transposition budget of the mixed packed calls of this engine; 0 restores the default."""
+        self._ck(self.lib.bpmi_debug_ipap_t_budget(self.ctx, nbytes))
+
     # ---- IPA prover state ----
     def ipa_create(self, g, h, a, b, n, u, h_scale=None):
         st = ctypes.c_void_p()
@@ -536,6 +568,50 @@ def ipa_batch_prepare_host(k, protocol, count, ab, xs, lr, transcripts, starts, 
     if rc != 0:
         raise EngineError("libbpmi error %d: %s" % (rc, lib.bpmi_last_error(None).decode()))
     return rec.raw[: (64 * k + 96) * count], pts.raw[: 64 * pairs], sc.raw[: 32 * pairs], status.raw[:count]
+
+
+def packed_class_array(protocol, classes):
+    """(array of IpaPackedClass, the objects its addresses point into, proofs, record bytes, extra pairs) of a list of classes
+    (k, count, ab, xs, lr, transcripts, starts, u, P, c, head): per class the arguments of packed_proof_args behind its k.  A class
+    with count = 0 keeps NULL pointers."""
+    arr, keep = (_native.IpaPackedClass * max(len(classes), 1))(), []
+
+    def addr(x):
+        if x is None:
+            return None
+        if isinstance(x, ctypes.Array):
+            keep.append(x)
+            return ctypes.addressof(x)
+        p = ctypes.c_char_p(x)
+        keep.append((x, p))
+        return ctypes.cast(p, ctypes.c_void_p).value
+    total = rec_bytes = pairs = 0
+    for i, (k, count, *rest) in enumerate(classes):
+        arr[i].k, arr[i].n_proofs = k, count
+        if not count:
+            continue
+        for name, v in zip(("ab", "xs", "LR", "transcripts", "tr_off", "start", "u", "P", "c", "head"), packed_proof_args(count, *rest)):
+            setattr(arr[i], name, addr(v))
+        total, rec_bytes, pairs = total + count, rec_bytes + (64 * k + 96) * count, pairs + count * (2 * k + (4 if protocol == 1 else 2))
+    return arr, keep, total, rec_bytes, pairs
+
+
+def ipa_batch_prepare_mixed_host(K, protocol, classes, weights=None, seed=None, threads=4):
+    """(records, rec_byte_off, extra_pts, extra_scalars, status) of bpmi_ipa_batch_prepare_mixed as bytes: the preparation of a mixed packed
+    batch in native HOST code (no GPU, no Engine).  classes: packed_class_array; weights: packed scalars by global (class-major) index
+    (1 per proof under Protocol 2, 3 under Protocol 1) or None with a 32-byte seed.  records: the classes' blocks in descending k
+    (stable), class c's at rec_byte_off[c]; extra pairs: the classes' blocks in the given order."""
+    lib = _native.load()
+    arr, keep, total, rec_bytes, pairs = packed_class_array(protocol, classes)
+    rec, pts, sc, status = (ctypes.create_string_buffer(max(nb, 1)) for nb in (rec_bytes, 64 * pairs, 32 * pairs, total))
+    offs = (ctypes.c_uint64 * max(len(classes), 1))()
+    vp = lambda b: ctypes.cast(b, ctypes.c_void_p)
+    rc = lib.bpmi_ipa_batch_prepare_mixed(K, protocol, len(classes), ctypes.addressof(arr), weights, seed, threads, vp(rec), ctypes.addressof(offs), vp(pts), vp(sc),
+                                          vp(status))
+    del keep
+    if rc != 0:
+        raise EngineError("libbpmi error %d: %s" % (rc, lib.bpmi_last_error(None).decode()))
+    return rec.raw[:rec_bytes], list(offs)[:len(classes)], pts.raw[: 64 * pairs], sc.raw[: 32 * pairs], status.raw[:total]
 
 
 _default = None

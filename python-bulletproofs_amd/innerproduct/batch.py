@@ -191,7 +191,8 @@ class BatchInnerProductVerifier:
     # faster than add() + verify() over 1 024 proofs of 64 .. 1 024 elements, 2.1x at 16 proofs of 64; SLOWER at one proof (0.39 ms
     # against 0.22) and at three proofs of 4 elements (0.31 against 0.24): three launches of single-wave chains and the uploads are
     # its floor, so add() + verify() stays the right path below a handful of proofs.
-    def _packed_rows(self, protocol, u, Ps, cs, ab, xs, lr, head, transcripts, starts):
+    def _packed_rows(self, protocol, u, Ps, cs, ab, xs, lr, head, transcripts, starts, k=None):
+        """k: the rows' round count (None: this verifier's; MixedBatchInnerProductVerifier passes a class's own)."""
         to_bytes = lambda v: bytes(v) if isinstance(v, (bytes, bytearray, memoryview)) else pack_points(v)
         count = len(transcripts)
         rows = {"ab": bytes(ab), "xs": bytes(xs), "lr": bytes(lr), "P": to_bytes(Ps), "trs": list(transcripts),
@@ -202,7 +203,7 @@ class BatchInnerProductVerifier:
             rows["head"] = bytes(head)
         else:
             rows["u"], rows["c"], rows["head"] = to_bytes(u), b"", b""
-        k = self.k
+        k = self.k if k is None else k
         sizes = {"ab": 64, "xs": 32 * k, "lr": 128 * k, "P": 64, "c": 32 if protocol == 1 else 0, "head": 128 if protocol == 1 else 0}
         if protocol == 2:
             sizes["u"] = 64
