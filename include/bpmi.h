@@ -798,6 +798,24 @@ int bpmi_ipa_verify_batch_packed_dev(bpmi_ctx *ctx, const void *d_g, const void 
                                      const uint8_t *ab, const uint8_t *xs, const uint8_t *LR, const uint8_t *transcripts, const uint64_t *tr_off,
                                      const uint32_t *start, const uint8_t *u, const uint8_t *P, const uint8_t *c, const uint8_t *head, const uint8_t *weights,
                                      const uint8_t *seed, uint8_t out[64], uint8_t *status);
+/* Which GROUPS of a packed batch hold an invalid proof, in one call (the counterpart of bpmi_rp_batch_group_values_dev): the
+ * preparation above runs once, the s-vectors are summed per group of `group` consecutive proofs, and the groups' MSMs over
+ * [g | h | the group's extra pairs] run as one launch over (group, window) with a device tail -- or, where a group's 2n + group x
+ * (2k + 2 | 2k + 4) pairs exceed 8 448, as one MSM per group.  Every argument before `group` as in bpmi_ipa_verify_batch_packed_dev
+ * (NULL rules, explicit weights or seed-derived ones by batch index).
+ *   group    >= 1; a value above n_proofs is clamped to it
+ *   values   HOST memory, ceil(n_proofs / group) x 64 B: values[t] = the combination over the unflagged proofs of
+ *            [t group, (t + 1) group) -- the 64 bytes bpmi_ipa_verify_batch_packed_dev writes for that sub-batch under the same weights;
+ *            64 zero bytes exactly when all of them verify
+ *   status   n_proofs bytes, bits as above; a flagged proof contributes to no group
+ * n_proofs = 0 is BPMI_OK and touches nothing.  BPMI_E_ARG before anything is read, allocated or uploaded: what the verify call
+ * refuses; group = 0; values or status NULL; ceil(n_proofs / group) x 2n > 2^26 (the rows of group scalars).  The generators are
+ * checked at "validate_points" = 2; a call refused for a point leaves 0xFF in every byte of values.  bpmi_debug_ipap_t_budget (below)
+ * cuts this call's preparation into rounds of at least 64 proofs as well.  One call at a time per ctx. */
+int bpmi_ipa_group_values_packed_dev(bpmi_ctx *ctx, const void *d_g, const void *d_h, const void *d_hscale, uint64_t n, int protocol, uint64_t n_proofs,
+                                     const uint8_t *ab, const uint8_t *xs, const uint8_t *LR, const uint8_t *transcripts, const uint64_t *tr_off,
+                                     const uint32_t *start, const uint8_t *u, const uint8_t *P, const uint8_t *c, const uint8_t *head, const uint8_t *weights,
+                                     const uint8_t *seed, uint64_t group, uint8_t *values, uint8_t *status);
 
 /* ---- packed inner-product proofs of DIFFERENT lengths: a list of classes, one MSM ------------------------------------------
  * The packed verifier above for proofs over the PREFIXES of one generator list (the statements of bpmi_ipa_verify_batch_mixed_dev:
@@ -851,7 +869,8 @@ int bpmi_ipa_verify_batch_packed_mixed_dev(bpmi_ctx *ctx, const void *d_g, const
                                            uint32_t n_classes, const bpmi_ipa_packed_class *classes, const uint8_t *weights, const uint8_t *seed,
                                            uint8_t out[64], uint8_t *status);
 /* test hook (not part of the drop-in surface): the byte budget of the transposed transcripts of ONE round of the mixed packed calls
- * on this ctx (0: the default, 2^28) -- a small value makes a few hundred proofs run as several rounds.  Not an option. */
+ * on this ctx (0: the default, 2^28) -- a small value makes a few hundred proofs run as several rounds.  It also bounds one preparation
+ * launch of bpmi_ipa_group_values_packed_dev (at least 64 proofs).  Not an option. */
 int bpmi_debug_ipap_t_budget(bpmi_ctx *ctx, uint64_t bytes);
 
 /* Page-locked host memory (hipHostMalloc) for buffers handed to the library repeatedly, e.g. the receive buffer of wire proofs. */

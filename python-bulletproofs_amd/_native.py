@@ -100,6 +100,7 @@ SIGNATURES = {
     "bpmi_ipa_batch_prepare": (_i, [ctypes.c_uint32, _i, _u64, _cp, _cp, _cp, _cp, _vp, _vp, _cp, _cp, _cp, _cp, _cp, _cp, _i, _vp, _vp, _vp, _vp]),
     "bpmi_ipa_batch_prepare_dev": (_i, [_vp, ctypes.c_uint32, _i, _u64, _cp, _cp, _cp, _cp, _vp, _vp, _cp, _cp, _cp, _cp, _cp, _cp, _vp, _vp, _vp, _vp]),
     "bpmi_ipa_verify_batch_packed_dev": (_i, [_vp, _vp, _vp, _vp, _u64, _i, _u64, _cp, _cp, _cp, _cp, _vp, _vp, _cp, _cp, _cp, _cp, _cp, _cp, _vp, _vp]),
+    "bpmi_ipa_group_values_packed_dev": (_i, [_vp, _vp, _vp, _vp, _u64, _i, _u64, _cp, _cp, _cp, _cp, _vp, _vp, _cp, _cp, _cp, _cp, _cp, _cp, _u64, _vp, _vp]),
     # (K | ctx, K | ctx, g, h, hscale, n_gens), protocol, n_classes, classes (an array of IpaPackedClass), weights, seed, ...
     "bpmi_ipa_batch_prepare_mixed": (_i, [ctypes.c_uint32, _i, ctypes.c_uint32, _vp, _cp, _cp, _i, _vp, _vp, _vp, _vp, _vp]),
     "bpmi_ipa_batch_prepare_mixed_dev": (_i, [_vp, ctypes.c_uint32, _i, ctypes.c_uint32, _vp, _cp, _cp, _vp, _vp, _vp, _vp, _vp]),

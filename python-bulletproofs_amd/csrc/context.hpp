@@ -58,7 +58,7 @@ struct bpmi_ctx : BpmiOptions {
   void *stage_in = nullptr; size_t stage_in_bytes = 0;  // device staging for host-pointer entry points
   // (the options: struct BpmiOptions, shared_defs.hpp)
   void *rp_buf = nullptr; size_t rp_buf_bytes = 0;   // batch preparation: per-proof contributions to the shared generators
-  uint64_t ipap_t_budget = 0;                        // bpmi_debug_ipap_t_budget: bytes of one round's transposed transcripts of the mixed packed calls (0: IPAP_T_BYTES_MAX)
+  uint64_t ipap_t_budget = 0;                        // bpmi_debug_ipap_t_budget: bytes of one round's transposed transcripts of the mixed packed calls and of the grouped one (0: IPAP_T_BYTES_MAX)
   bool async_lanes_ordered = false;                  // option async_lanes: this burst's extra lanes are ordered behind the ctx stream
   void *fold_tab = nullptr; size_t fold_tab_bytes = 0;     // tables + scratch of the width-4 NAF generator fold, allocated at the first fold, kept
   const void *fold_key_g = nullptr, *fold_key_h = nullptr; uint64_t fold_key_n = 0;     // whose tables fold_tab holds (nullptr: nobody's)

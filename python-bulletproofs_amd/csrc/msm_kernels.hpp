@@ -1997,6 +1997,35 @@ template <u32 THREADS, u32 NMAX> __global__ void __launch_bounds__(THREADS) k_ms
 template __global__ void k_msm_group<MID_THREADS, MID_NMAX>(GroupMsm);
 template __global__ void k_msm_group<GROUP_LIGHT_THREADS, GROUP_LIGHT_NMAX>(GroupMsm);
 
+// The groups of a batch of packed inner-product proofs (bpmi_ipa_group_values_packed_dev, ipa_group_plan_host.hpp): the shared
+// generators are TWO arrays of n points, and each group has its own row of scalars over either one (k_sc_svector_sum_groups); the
+// third segment is the extra pairs of the group's proofs, `per` per proof, proof-major.  Block (t, w) as in k_msm_group.
+struct IpaGroupMsm {
+  const u32 *g, *h;                   // n generators each
+  const u32 *sa, *sb;                 // their scalars, one row of n per group
+  const u32 *x_pts, *x_sc;            // extra points and their scalars, `per` per proof
+  u32 n, per, group, P, W;
+  u32 *E;                             // [t][w]: W window sums per group
+};
+template <u32 THREADS, u32 NMAX> __global__ void __launch_bounds__(THREADS) k_msm_ipa_group(IpaGroupMsm J) {
+  const u32 t = blockIdx.x / J.W, w = blockIdx.x - t * J.W;
+  const u32 g0 = t * J.group, cnt = min(J.group, J.P - g0);
+  Segs s;
+  s.pts[0] = J.g; s.sc[0] = J.sa + 8ull * J.n * t; s.n[0] = J.n;
+  s.pts[1] = J.h; s.sc[1] = J.sb + 8ull * J.n * t; s.n[1] = J.n;
+  s.pts[2] = J.x_pts + 16ull * J.per * g0; s.sc[2] = J.x_sc + 8ull * J.per * g0; s.n[2] = cnt * J.per;
+  s.total = s.n[0] + s.n[1] + s.n[2];
+  s.hlog[0] = s.hlog[1] = s.hlog[2] = 0xFFu;
+  s.phase[0] = s.phase[1] = s.phase[2] = 0;
+  s.glv_sub = nullptr; s.glv_neg = nullptr; s.glv_bx = nullptr;
+  MsmGeom g = {};                                  // (the body reads n and W only)
+  g.n = s.total; g.c = MID_C; g.W = J.W; g.B = MID_B;
+  u32 *const Et = J.E + (u64)t * J.W * XYZZ_WORDS;
+  msm_mid_block<THREADS, NMAX>(s, g, w, 1u, 0u, Et);
+}
+template __global__ void k_msm_ipa_group<MID_THREADS, MID_NMAX>(IpaGroupMsm);
+template __global__ void k_msm_ipa_group<GROUP_LIGHT_THREADS, GROUP_LIGHT_NMAX>(IpaGroupMsm);
+
 // ---- tail: result = sum_w 2^(c w) sum_v 2^(off[v]) E[w][v], to canonical affine -------------
 BPMI_HD void msm_tail_combine(u32 out_words[16], const u32 *E, u32 W, u32 c, const TailOffs &to) {
   // ONE Horner chain over bit positions: E[w][v] carries weight 2^(start of window w + off[v]), so walking from the top bit down

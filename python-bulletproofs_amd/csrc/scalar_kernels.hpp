@@ -282,6 +282,19 @@ __global__ void __launch_bounds__(256) k_sc_svector_sum_finish(const u32 *__rest
   store_words8(sa + 8ull * i, ra);
   store_words8(sb + 8ull * i, rb);
 }
+// The sums per GROUP of `group` consecutive proofs (bpmi_ipa_group_values_packed_dev; plan: ipa_group_plan_host.hpp): rows SA[t][i],
+// SB[t][i] of n = 2^k scalars, canonical, SB with the shared scale.  Threads are flat over (group, element): for n < 64 several groups
+// share a wave, so a small n idles no lane.  ngroups n <= 2^25 (the plan's cap): the index stays in 32 bits.
+__global__ void __launch_bounds__(256) k_sc_svector_sum_groups(const u32 *__restrict__ tabs, u32 ntab, u32 k, u32 kl, u32 n_proofs, u32 group, u32 ngroups,
+                                                               const u32 *__restrict__ scale, u32 *__restrict__ sa, u32 *__restrict__ sb) {
+  const u32 idx = blockIdx.x * 256u + threadIdx.x;
+  const u32 t = idx >> k, i = idx & ((1u << k) - 1u);
+  if (t >= ngroups) return;
+  u32 ra[8], rb[8];
+  svb_group_element(ra, rb, tabs, ntab, kl, i, t, group, n_proofs, scale);
+  store_words8(sa + 8ull * idx, ra);
+  store_words8(sb + 8ull * idx, rb);
+}
 
 // Self-test hook: the DEVICE bodies of the multiplication family (csrc/field_gen.hpp) on raw limbs, so that a
 // test can feed lazy magnitudes and compare the limbs with the host build of the same header (tests/test_gpu_field.py).

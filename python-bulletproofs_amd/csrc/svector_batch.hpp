@@ -111,4 +111,22 @@ BPMI_HD void svb_finish_element(u32 out_a[8], u32 out_b[8], const u32 *part, u32
   for (int q = 0; q < 8; q++) { out_a[q] = A.v[q]; out_b[q] = B.v[q]; }
 }
 
+// Element i of GROUP t (bpmi_ipa_group_values_packed_dev): svb_sum_element over the group's proofs [t group, min((t + 1) group, n_proofs)),
+// then SB times the shared scale c_i (or scale == null).  Canonical output: these are the scalars of row t of the groups' MSMs.
+BPMI_HD void svb_group_element(u32 out_a[8], u32 out_b[8], const u32 *tabs, uint64_t tab_entries, u32 kl, u32 i, u32 t, u32 group, u32 n_proofs,
+                               const u32 *scale) {
+  const u32 p0 = t * group;
+  const u32 p1 = n_proofs - p0 < group ? n_proofs : p0 + group;
+  svb_sum_element(out_a, out_b, tabs, tab_entries, kl, i, p0, p1);
+  if (scale) {
+    sc B, c;
+#pragma unroll
+    for (int q = 0; q < 8; q++) B.v[q] = out_b[q];
+    svb_load8(c.v, scale + 8ull * i);
+    sc_mul(B, B, c);
+#pragma unroll
+    for (int q = 0; q < 8; q++) out_b[q] = B.v[q];
+  }
+}
+
 }  // namespace bpmi

@@ -350,6 +350,20 @@ class Engine:
                                                            ctypes.cast(out, ctypes.c_void_p), ctypes.cast(status, ctypes.c_void_p)))
         return out.raw, status.raw[:count]
 
+    def ipa_group_values_packed_dev(self, d_g, d_h, n, protocol, count, ab, xs, lr, transcripts, starts, u, P, c=None, head=None, weights=None, seed=None,
+                                    d_hscale=None, group=1):
+        """(values, status) of bpmi_ipa_group_values_packed_dev: values[t] = the 64-byte value of the weighted combination over the
+        unflagged proofs of [t group, (t + 1) group) (identity = all of them verify) -- what ipa_verify_batch_packed_dev returns for that
+        sub-batch under the same weights -- and one status byte per proof.  One preparation and one launch of the groups' MSMs."""
+        per = max(1, min(int(group), count))             # (group = 0 is the native call's argument error)
+        ngroups = (count + per - 1) // per
+        values, status = ctypes.create_string_buffer(max(64 * ngroups, 1)), ctypes.create_string_buffer(max(count, 1))
+        self._ck(self.lib.bpmi_ipa_group_values_packed_dev(self.ctx, _ptr(d_g), _ptr(d_h), None if d_hscale is None else _ptr(d_hscale), n, protocol, count,
+                                                           *packed_proof_args(count, ab, xs, lr, transcripts, starts, u, P, c, head), weights, seed, group,
+                                                           ctypes.cast(values, ctypes.c_void_p), ctypes.cast(status, ctypes.c_void_p)))
+        raw = values.raw
+        return [raw[64 * t: 64 * t + 64] for t in range(ngroups)], status.raw[:count]
+
     # ---- packed inner-product proofs of different lengths: a list of classes (bpmi_ipa_packed_class) ----
     def ipa_batch_prepare_mixed_dev(self, K, protocol, classes, weights=None, seed=None):
         """(records, rec_byte_off, extra_pts, extra_scalars, status) of bpmi_ipa_batch_prepare_mixed_dev: the preparation of a mixed packed
@@ -379,7 +393,8 @@ class Engine:
         return out.raw, status.raw[:total]
 
     def ipap_t_budget(self, nbytes):
-        """bpmi_debug_ipap_t_budget (tests): the transposition budget of the mixed packed calls of this engine; 0 restores the default."""
+        """bpmi_debug_ipap_t_budget (tests): the transposition budget of the mixed packed calls and of ipa_group_values_packed_dev on this engine; 0 restores
+        the default."""
         self._ck(self.lib.bpmi_debug_ipap_t_budget(self.ctx, nbytes))
 
     # ---- IPA prover state ----

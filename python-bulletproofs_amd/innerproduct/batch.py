@@ -12,6 +12,7 @@ Two ways in.  Proof OBJECTS: `add` / `add_proof1` re-derive each transcript in P
 the arrays BatchInnerProductProver.prove2_packed / prove1_packed return: `verify_packed2` / `verify_packed1` hand them to ONE native
 call (bpmi_ipa_verify_batch_packed_dev) that re-hashes, compares, inverts and weights every proof on the device, one lane per proof,
 and runs the same MSM; the weights come from a fresh 32-byte seed per call, and the note above applies unchanged."""
+import math
 import secrets
 
 from .. import engine as _engine
@@ -21,6 +22,8 @@ from .inner_product_verifier import Verifier2
 
 Q = secp256k1.q
 CALL_MAX = 1 << 16             # proofs per native call (IPAB_PROOFS_MAX, csrc/ipa_batch_plan_host.hpp)
+GROUP_MAX_PAIRS = 8448         # MID_NMAX (csrc/shared_defs.hpp): the pairs of one group's MSM in the one-launch group kernel
+GROUP_ROWS_MAX = 1 << 26       # group scalars per native call: groups x 2 n (IPAG_ROWS_MAX, csrc/ipa_group_plan_host.hpp)
 
 
 def locate_by_bisection(count, subset_is_valid):
@@ -244,7 +247,13 @@ class BatchInnerProductVerifier:
                 return False
         return True
 
-    def _locate_packed(self, protocol, rows, sizes, count):
+    def _locate_packed(self, protocol, rows, sizes, count, group=None):
+        if group is None or int(group) >= 1:
+            from ..rangeproofs.batch import locate_plan          # (here: rangeproofs.batch imports this package)
+            grp = self.default_group(protocol, count) if group is None else int(group)
+            return locate_plan(count, grp, lambda idx, g: self._group_values_packed(protocol, rows, sizes, range(count) if idx is None else idx, g, None))
+        if int(group) != 0:
+            raise ValueError("group must be None, 0 (bisection) or at least 1")
         flagged = []
         for lo in range(0, count, CALL_MAX):
             hi = min(lo + CALL_MAX, count)
@@ -261,6 +270,69 @@ class BatchInnerProductVerifier:
             return True
         return sorted(flagged + [rest[j] for j in locate_by_bisection(len(rest), probe)])
 
+    # ---- packed proofs, per GROUP of consecutive proofs: one native call names the groups that hold an invalid proof ---------------
+    # bpmi_ipa_group_values_packed_dev (csrc/ipa_group_dev_host.hpp): the preparation of the packed verifier once, the s-vector sums per
+    # group, the groups' MSMs over [g | h | the group's extra pairs] in one launch.  locate_packed* is two such calls (locate_plan).
+    def default_group(self, protocol, count=None):
+        """The group size locate_packed1 / locate_packed2 start with.  Where a group's MSM fits the one-launch group kernel: the largest
+        power of two with 2 n + group * per <= 8448 pairs (MID_NMAX, csrc/shared_defs.hpp), per = 2 log2 n + 2 extra pairs of a proof under
+        Protocol 2 and 2 log2 n + 4 under Protocol 1.  Where not even one proof fits (n >= 8192) every group is a multi-scalar
+        multiplication of its own, and the plan runs count / group + bad * group of them: the largest power of two <= sqrt(count) (1
+        without a count).  Both are CAPACITY rules -- what fits a launch, what balances the two levels -- and NOT measured optima:
+        profiles/r18_ipa_locate_packed.txt has the first rule ahead of the bisection in every case it measured (2^14 x 64 and
+        2^10 x 1024 proofs), but no other group size was timed against it, and the second rule was not measured at all."""
+        per = 2 * self.k + (4 if protocol == 1 else 2)
+        fit = (GROUP_MAX_PAIRS - 2 * self.n) // per
+        if fit >= 1:
+            return 1 << (fit.bit_length() - 1)
+        root = math.isqrt(count) if count and count > 0 else 1
+        return 1 << (max(root, 1).bit_length() - 1)
+
+    def _group_values_packed(self, protocol, rows, sizes, idx, group, wb):
+        """(values, status) over the rows idx (a range or a sorted list) in groups of `group` consecutive rows of idx.  A batch beyond
+        one call's caps -- 2^16 proofs, ceil(proofs / group) * 2 n <= 2^26 group scalars -- runs as consecutive calls cut at multiples of
+        `group`, each under its own slice of the explicit weights wb or a fresh seed."""
+        group = int(group)
+        if group < 1:
+            raise ValueError("group must be at least 1")
+        count = len(idx)
+        group = min(group, max(count, 1))
+        per_w = 32 * (3 if protocol == 1 else 1)
+        groups_per_call = min(max(CALL_MAX // group, 1), max(GROUP_ROWS_MAX // (2 * self.n), 1))
+        chunk = groups_per_call * group
+        values, status = [], b""
+        for lo in range(0, count, chunk):
+            hi = min(lo + chunk, count)
+            sub = idx[lo:hi]
+            if isinstance(sub, range) and sub.step == 1:
+                cut = lambda name: rows[name][sizes[name] * sub.start: sizes[name] * sub.stop]
+            else:
+                cut = lambda name: b"".join(rows[name][sizes[name] * i: sizes[name] * (i + 1)] for i in sub)
+            u = rows["u"] if protocol == 1 else cut("u")
+            starts = None if rows["starts"] is None else [rows["starts"][i] for i in sub]
+            weights = None if wb is None else wb[per_w * lo: per_w * hi]
+            seed = None if weights is not None else secrets.token_bytes(32)
+            v, st = self.engine.ipa_group_values_packed_dev(self._d[0], self._d[1], self.n, protocol, hi - lo, cut("ab"), cut("xs"), cut("lr"),
+                                                            [rows["trs"][i] for i in sub], starts, u, cut("P"), cut("c"), cut("head"), weights, seed,
+                                                            self._d_scale, group)
+            values += v
+            status += st
+        return values, status
+
+    def group_values_packed2(self, us, Ps, ab, xs, lr, transcripts, starts=None, group=1, weights=None):
+        """(values, status) of a packed Protocol-2 batch (the arguments of verify_packed2) per GROUP of `group` consecutive proofs:
+        values[t] = the 64-byte value of the weighted combination over the unflagged proofs of [t group, (t + 1) group) -- 64 zero bytes
+        when all of them verify --, status[i] = bit 0: proof i fails a byte-level check, bit 1: it has an invalid point (a flagged proof
+        takes part in no group).  Never a verdict: the values and the status are the result.  A batch beyond one native call's caps
+        (2^16 proofs, ceil(count / group) * 2 n <= 2^26) is cut into consecutive calls at multiples of `group`."""
+        rows, sizes, count = self._packed_rows(2, us, Ps, None, ab, xs, lr, None, transcripts, starts)
+        return self._group_values_packed(2, rows, sizes, range(count), group, self._weights_bytes(2, weights, count))
+
+    def group_values_packed1(self, u, Ps, cs, ab, xs, lr, head, transcripts, group=1, weights=None):
+        """group_values_packed2 for a packed Protocol-1 batch (the arguments of verify_packed1; weights: three per proof)."""
+        rows, sizes, count = self._packed_rows(1, u, Ps, cs, ab, xs, lr, head, transcripts, None)
+        return self._group_values_packed(1, rows, sizes, range(count), group, self._weights_bytes(1, weights, count))
+
     def verify_packed2(self, us, Ps, ab, xs, lr, transcripts, starts=None, weights=None):
         """True iff every Protocol-2 proof of the packed batch (ab, xs, lr, transcripts: what prove2_packed returns) is valid for its
         statement (us[i], Ps[i]) -- points or packed bytes, 64 per proof.  starts: Proof2.start_transcript per proof (None: 1, the
@@ -276,16 +348,19 @@ class BatchInnerProductVerifier:
         rows, sizes, count = self._packed_rows(1, u, Ps, cs, ab, xs, lr, head, transcripts, None)
         return self._verify_packed(1, rows, sizes, count, weights)
 
-    def locate_packed2(self, us, Ps, ab, xs, lr, transcripts, starts=None):
-        """The sorted indices of the invalid proofs of a packed Protocol-2 batch: those the status bytes flag, and the rest found by
-        locate_by_bisection, every probe one native call over the gathered rows of the subset under fresh weights."""
+    def locate_packed2(self, us, Ps, ab, xs, lr, transcripts, starts=None, group=None):
+        """The sorted indices of the invalid proofs of a packed Protocol-2 batch.  group = None or an integer >= 1: the two levels of
+        rangeproofs.batch.locate_plan over group_values_packed2 -- level 1 is one call with `group` (None: default_group), level 2 one
+        call with group = 1 over the unflagged proofs of the groups whose value is not the identity; a valid batch costs one native
+        call, a rejected one two.  group = 0: locate_by_bisection over verify calls, every probe one native call over the gathered rows
+        of the subset under fresh weights (kept for comparison).  The indices are the same in every case."""
         rows, sizes, count = self._packed_rows(2, us, Ps, None, ab, xs, lr, None, transcripts, starts)
-        return self._locate_packed(2, rows, sizes, count)
+        return self._locate_packed(2, rows, sizes, count, group)
 
-    def locate_packed1(self, u, Ps, cs, ab, xs, lr, head, transcripts):
+    def locate_packed1(self, u, Ps, cs, ab, xs, lr, head, transcripts, group=None):
         """locate_packed2 for a packed Protocol-1 batch."""
         rows, sizes, count = self._packed_rows(1, u, Ps, cs, ab, xs, lr, head, transcripts, None)
-        return self._locate_packed(1, rows, sizes, count)
+        return self._locate_packed(1, rows, sizes, count, group)
 
 
 def batch_verify_inner_products(g, h, statements, h_scale=None, engine=None, rng=None):
