@@ -80,6 +80,7 @@ using namespace bpmi;
 #include "ipa_mixed_kernels.hpp"
 #include "host_tail.hpp"
 #include "msm_host.hpp"
+#include "ipa_verify_msm_host.hpp"
 #include "msm_fixed_host.hpp"
 #include "rp_batch_host.hpp"
 #include "ipa_packed_host.hpp"
@@ -873,26 +874,12 @@ int bpmi_ipa_verify_dev(bpmi_ctx *ctx, const void *d_g, const void *d_h, const v
   if (extra_on_host) { rc = pc.host(extra_pts, n_extra, "extra_pts"); if (rc) return rc; }
   rc = svector_launch(ctx, L, d_hscale, n, xs, xinvs, a, b);
   if (rc) return rc;
-  u32 *d_sa = L.sa, *d_sb = L.sb;
   char *d_ex = L.extra;
   if (n_extra) {
     HIPCHK(ctx, h2d(ctx, d_ex, extra_pts, 64 * n_extra, ctx->stream));
     HIPCHK(ctx, h2d(ctx, d_ex + o_es, extra_scalars, 32 * n_extra, ctx->stream));
   }
-  Segs s = segs_init();
-  s.pts[0] = (const u32 *)d_g; s.sc[0] = d_sa; s.n[0] = (u32)n;
-  s.pts[1] = (const u32 *)d_h; s.sc[1] = d_sb; s.n[1] = (u32)n;
-  s.pts[2] = (const u32 *)d_ex; s.sc[2] = (const u32 *)(d_ex + o_es); s.n[2] = (u32)n_extra;
-  s.total = (u32)(2 * n + n_extra);
-  if (ctx->opt_validate >= 2) { pc.queue(d_g, n, "d_g"); pc.queue(d_h, n, "d_h"); }
-  if (!extra_on_host) pc.queue(d_ex, n_extra, "extra_pts");
-  rc = pc.fetch();
-  if (rc) return rc;
-  rc = msm_run(ctx, s, out);
-  if (rc) return rc;
-  rc = pc.verdict();
-  if (rc) memset(out, 0xFF, 64);                // (never the identity, which a verifier reads as "valid")
-  return rc;
+  return ipa_verify_msm(ctx, pc, d_g, d_h, n, L.sa, L.sb, d_ex, d_ex + o_es, n_extra, !extra_on_host, false, out);
 }
 
 }  // extern "C"

@@ -8,19 +8,25 @@
 
 extern "C" {
 
+// the half tables of every proof, from the records in the workspace.  Queued inside the CALLER's StageTimer scope: no timer of its own
+static void ipab_tables_launch(bpmi_ctx *ctx, const IpabPlan &pl) {
+  char *base = (char *)ctx->stage_in;
+  const u32 P = (u32)pl.n_proofs, ntab = (u32)pl.tab_entries;
+  const u32 gy = P < IPAB_TABLE_GRID_Y ? P : IPAB_TABLE_GRID_Y;
+  hipLaunchKernelGGL(k_sc_svector_tables_batch, dim3((ntab + IPAB_THREADS - 1) / IPAB_THREADS, gy, (P + gy - 1) / gy), dim3(IPAB_THREADS), 0, ctx->stream,
+                     (const u32 *)(base + pl.o_rec), pl.rec_words, pl.k, pl.kl, P, (u32 *)(base + pl.o_tab));
+}
+
 // the three launches that leave SA and SB in the workspace, from the proofs' records (k pairs (x_j, x_j^-1), then a, b, w) that are
 // in the workspace already: uploaded by ipab_svector_sum, or written there by the preparation kernels (ipa_packed_dev_host.hpp)
 static int ipab_svector_launches(bpmi_ctx *ctx, const IpabPlan &pl, const void *d_scale) {
   char *base = (char *)ctx->stage_in;
-  const u32 k = pl.k;
   u32 *sa = (u32 *)(base + pl.o_sa), *sb = (u32 *)(base + pl.o_sb), *part = (u32 *)(base + pl.o_part);
   const u32 *tabs = (const u32 *)(base + pl.o_tab);
   const u32 n = (u32)pl.n, P = (u32)pl.n_proofs, ntab = (u32)pl.tab_entries;
   {
     StageTimer t(ctx, ST_SCFOLD);
-    const u32 gy = P < IPAB_TABLE_GRID_Y ? P : IPAB_TABLE_GRID_Y;
-    hipLaunchKernelGGL(k_sc_svector_tables_batch, dim3((ntab + IPAB_THREADS - 1) / IPAB_THREADS, gy, (P + gy - 1) / gy), dim3(IPAB_THREADS), 0, ctx->stream,
-                       (const u32 *)(base + pl.o_rec), pl.rec_words, k, pl.kl, P, (u32 *)(base + pl.o_tab));
+    ipab_tables_launch(ctx, pl);
     const dim3 grid((n + IPAB_THREADS - 1) / IPAB_THREADS, pl.parts);
     if (pl.direct) {
       hipLaunchKernelGGL(k_sc_svector_sum, grid, dim3(IPAB_THREADS), 0, ctx->stream, tabs, ntab, pl.kl, n, P, pl.per_part, sa, sb, (uint64_t)0);
@@ -95,20 +101,7 @@ int bpmi_ipa_verify_batch_dev(bpmi_ctx *ctx, const void *d_g, const void *d_h, c
     HIPCHK(ctx, h2d(ctx, base + pl.o_expt, extra_pts, 64 * n_extra, ctx->stream));
     HIPCHK(ctx, h2d(ctx, base + pl.o_exsc, extra_scalars, 32 * n_extra, ctx->stream));
   }
-  Segs s = segs_init();
-  s.pts[0] = (const u32 *)d_g; s.sc[0] = (const u32 *)(base + pl.o_sa); s.n[0] = (u32)n;
-  s.pts[1] = (const u32 *)d_h; s.sc[1] = (const u32 *)(base + pl.o_sb); s.n[1] = (u32)n;
-  s.pts[2] = (const u32 *)(base + pl.o_expt); s.sc[2] = (const u32 *)(base + pl.o_exsc); s.n[2] = (u32)n_extra;
-  s.total = (u32)pl.msm_pairs;
-  if (ctx->opt_validate >= 2) { pc.queue(d_g, n, "d_g"); pc.queue(d_h, n, "d_h"); }
-  if (!extra_on_host) pc.queue(base + pl.o_expt, n_extra, "extra_pts");
-  rc = pc.fetch();
-  if (rc) return rc;
-  rc = msm_run(ctx, s, out);                    // one MSM over the three segments, sliced as any large MSM is (msm_host.hpp)
-  if (rc) return rc;
-  rc = pc.verdict();
-  if (rc) memset(out, 0xFF, 64);
-  return rc;
+  return ipa_verify_msm(ctx, pc, d_g, d_h, n, base + pl.o_sa, base + pl.o_sb, base + pl.o_expt, base + pl.o_exsc, n_extra, !extra_on_host, false, out);
 }
 
 }  // extern "C"

@@ -1,9 +1,10 @@
 // ipa_group_dev_host.hpp -- part of libbpmi (included by bpmi.hip; one translation unit).  HOST code.
 // Which groups of a batch of PACKED inner-product proofs hold an invalid one: bpmi_ipa_group_values_packed_dev.  The preparation of
-// bpmi_ipa_verify_batch_packed_dev (ipap_run: upload, re-hash, inversion, weights -- once per batch) and its half tables, but the
-// s-vectors are summed per GROUP of `group` consecutive proofs (k_sc_svector_sum_groups) and the groups' MSMs over
-// [g | h | the group's extra pairs] run as ONE launch over (group, window) (k_msm_ipa_group) with a device tail (k_group_tail) -- the
-// counterpart of bpmi_rp_batch_group_values_dev.  Plan, argument errors and routes: ipa_group_plan_host.hpp.
+// bpmi_ipa_verify_batch_packed_dev (ipap_run: upload, re-hash, inversion, weights -- once per batch) and its half tables
+// (ipab_tables_launch, ipa_batch_host.hpp), but the s-vectors are summed per GROUP of `group` consecutive proofs
+// (k_sc_svector_sum_groups) and the groups' MSMs over [g | h | the group's extra pairs] (ipa_segs, ipa_verify_msm_host.hpp) run as ONE
+// launch over (group, window) (k_msm_ipa_group) with a device tail (k_group_tail) -- the counterpart of
+// bpmi_rp_batch_group_values_dev.  Plan, argument errors and routes: ipa_group_plan_host.hpp.
 #pragma once
 
 extern "C" {
@@ -39,9 +40,7 @@ int bpmi_ipa_group_values_packed_dev(bpmi_ctx *ctx, const void *d_g, const void 
   u32 *gsa = (u32 *)(base + gp.o_gsa), *gsb = (u32 *)(base + gp.o_gsb);
   {
     StageTimer t(ctx, ST_SCFOLD);
-    const u32 gy = Pn < IPAB_TABLE_GRID_Y ? Pn : IPAB_TABLE_GRID_Y;
-    hipLaunchKernelGGL(k_sc_svector_tables_batch, dim3((ntab + IPAB_THREADS - 1) / IPAB_THREADS, gy, (Pn + gy - 1) / gy), dim3(IPAB_THREADS), 0, st,
-                       (const u32 *)(base + bp.o_rec), bp.rec_words, bp.k, bp.kl, Pn, (u32 *)(base + bp.o_tab));
+    ipab_tables_launch(ctx, bp);
     const uint64_t elems = (uint64_t)gp.ngroups * n;                   // <= 2^25 (the plan's cap)
     hipLaunchKernelGGL(k_sc_svector_sum_groups, dim3((u32)((elems + 255) / 256)), dim3(256), 0, st, (const u32 *)(base + bp.o_tab), ntab, bp.k, bp.kl, Pn,
                        gp.group, gp.ngroups, (const u32 *)d_hscale, gsa, gsb);
@@ -69,11 +68,8 @@ int bpmi_ipa_group_values_packed_dev(bpmi_ctx *ctx, const void *d_g, const void 
     // groups beyond the one-launch kernel's capacity: one MSM each on the three segments (as rp_run_group_msms)
     for (u32 t = 0; t < gp.ngroups; t++) {
       const uint64_t g0 = (uint64_t)t * gp.group, cnt = std::min<uint64_t>(gp.group, n_proofs - g0);
-      Segs s = segs_init();
-      s.pts[0] = (const u32 *)d_g; s.sc[0] = gsa + 8 * (size_t)n * t; s.n[0] = nn;
-      s.pts[1] = (const u32 *)d_h; s.sc[1] = gsb + 8 * (size_t)n * t; s.n[1] = nn;
-      s.pts[2] = (const u32 *)(base + bp.o_expt) + 16 * gp.per * g0; s.sc[2] = (const u32 *)(base + bp.o_exsc) + 8 * gp.per * g0; s.n[2] = (u32)(cnt * gp.per);
-      s.total = s.n[0] + s.n[1] + s.n[2];
+      const Segs s = ipa_segs(d_g, d_h, n, gsa + 8 * (size_t)n * t, gsb + 8 * (size_t)n * t, (const u32 *)(base + bp.o_expt) + 16 * gp.per * g0,
+                              (const u32 *)(base + bp.o_exsc) + 8 * gp.per * g0, cnt * gp.per);
       rc = msm_run(ctx, s, values + 64 * (size_t)t);
       if (rc) { memset(values, 0xFF, vals_bytes); return rc; }
     }

@@ -113,20 +113,7 @@ int bpmi_ipa_verify_batch_mixed_dev(bpmi_ctx *ctx, const void *d_g, const void *
     HIPCHK(ctx, h2d(ctx, base + pl.o_expt, extra_pts, 64 * n_extra, ctx->stream));
     HIPCHK(ctx, h2d(ctx, base + pl.o_exsc, extra_scalars, 32 * n_extra, ctx->stream));
   }
-  Segs s = segs_init();
-  s.pts[0] = (const u32 *)d_g; s.sc[0] = (const u32 *)(base + pl.o_sa); s.n[0] = (u32)pl.n_top;
-  s.pts[1] = (const u32 *)d_h; s.sc[1] = (const u32 *)(base + pl.o_sb); s.n[1] = (u32)pl.n_top;
-  s.pts[2] = (const u32 *)(base + pl.o_expt); s.sc[2] = (const u32 *)(base + pl.o_exsc); s.n[2] = (u32)n_extra;
-  s.total = (u32)pl.msm_pairs;
-  if (ctx->opt_validate >= 2) { pc.queue(d_g, pl.n_top, "d_g"); pc.queue(d_h, pl.n_top, "d_h"); }
-  if (!extra_on_host) pc.queue(base + pl.o_expt, n_extra, "extra_pts");
-  rc = pc.fetch();
-  if (rc) return rc;
-  rc = msm_run(ctx, s, out);                    // one MSM over the three segments
-  if (rc) return rc;
-  rc = pc.verdict();
-  if (rc) memset(out, 0xFF, 64);
-  return rc;
+  return ipa_verify_msm(ctx, pc, d_g, d_h, pl.n_top, base + pl.o_sa, base + pl.o_sb, base + pl.o_expt, base + pl.o_exsc, n_extra, !extra_on_host, false, out);
 }
 
 }  // extern "C"

@@ -1,19 +1,52 @@
 // ipa_packed_dev_host.hpp -- part of libbpmi (included by bpmi.hip; one translation unit).  HOST code.
 // The batch verifier of PACKED inner-product proofs (what bpmi_ipa_prove_batch writes): bpmi_ipa_batch_prepare (the host twin,
 // ipa_packed_host.hpp), bpmi_ipa_batch_prepare_dev (the kernels of ipa_packed_kernels.hpp) and bpmi_ipa_verify_batch_packed_dev:
-// upload, preparation kernels, the s-vector launches of ipa_batch_host.hpp from the records the kernels left in the workspace, and
-// the one MSM over [g | h | extra] -- no host loop over proofs.  Plan and argument errors: ipa_packed_plan_host.hpp.
+// upload, preparation kernels, ipab_svector_launches (ipa_batch_host.hpp) from the records the kernels left in the workspace, and
+// the one MSM over [g | h | extra] (ipa_verify_msm_host.hpp) -- no host loop over proofs.  Plan and argument errors:
+// ipa_packed_plan_host.hpp.  The upload of a class and its transposition launch stand at the top: the mixed and the group calls
+// (ipa_packed_mixed_dev_host.hpp, ipa_group_dev_host.hpp) use them too.
 #pragma once
 
-extern "C" {
-
-static IpaPackedIn ipap_in(const uint8_t *ab, const uint8_t *xs, const uint8_t *LR, const uint8_t *transcripts, const uint64_t *tr_off, const uint32_t *start,
-                           const uint8_t *u, const uint8_t *P, const uint8_t *c, const uint8_t *head, const uint8_t *weights, const uint8_t *seed) {
-  IpaPackedIn in;
-  in.ab = ab; in.xs = xs; in.LR = LR; in.transcripts = transcripts; in.tr_off = tr_off; in.start = start;
-  in.u = u; in.P = P; in.c = c; in.head = head; in.weights = weights; in.seed = seed;
-  return in;
+// ---- what the uniform, the mixed and the group calls share: one class of proofs of one k on its way to the preparation kernels ----
+// Upload the class's packed arrays into its regions and describe them to the kernels in q: everything but the rows of a launch
+// (first, P_launch, Tstride) and, for a class of a mixed call, gbase.  d_records / d_exsc: where the class's records and extra
+// scalars go; in.weights: the class's slice of explicit weights, or NULL and in.seed.
+static int ipap_stage_class(bpmi_ctx *ctx, const IpapRegions &r, const IpaPackedIn &in, u32 k, int protocol, uint64_t n_proofs, uint64_t tr_bytes,
+                            u32 *d_records, u32 *d_exsc, ipad::Params &q) {
+  char *base = (char *)ctx->stage_in;
+  auto up = [&](uint64_t off, const void *src, uint64_t bytes) { return bytes ? h2d(ctx, base + off, src, bytes, ctx->stream) : hipSuccess; };
+  HIPCHK(ctx, up(r.o_ab, in.ab, r.b_ab));
+  HIPCHK(ctx, up(r.o_xs, in.xs, r.b_xs));
+  HIPCHK(ctx, up(r.o_lr, in.LR, r.b_lr));
+  HIPCHK(ctx, up(r.o_tr, in.transcripts + in.tr_off[0], tr_bytes));
+  HIPCHK(ctx, up(r.o_troff, in.tr_off, r.b_troff));
+  HIPCHK(ctx, up(r.o_start, in.start, r.b_start));
+  HIPCHK(ctx, up(r.o_u, in.u, r.b_u));
+  HIPCHK(ctx, up(r.o_P, in.P, r.b_P));
+  HIPCHK(ctx, up(r.o_c, in.c, r.b_c));
+  HIPCHK(ctx, up(r.o_head, in.head, r.b_head));
+  HIPCHK(ctx, up(r.o_w, in.weights, r.b_w));
+  memset(&q, 0, sizeof(q));
+  q.tr_off = (const u64 *)(base + r.o_troff);
+  q.start = in.start ? (const u32 *)(base + r.o_start) : nullptr;
+  q.ab = (const uint8_t *)base + r.o_ab; q.xs = (const uint8_t *)base + r.o_xs; q.LR = (const uint8_t *)base + r.o_lr;
+  q.u = (const uint8_t *)base + r.o_u; q.P = (const uint8_t *)base + r.o_P; q.c = (const uint8_t *)base + r.o_c; q.head = (const uint8_t *)base + r.o_head;
+  q.weights = in.weights ? (const uint8_t *)base + r.o_w : nullptr;
+  if (!in.weights)
+    for (int i = 0; i < 8; i++) q.seed[i] = ((u32)in.seed[4 * i] << 24) | ((u32)in.seed[4 * i + 1] << 16) | ((u32)in.seed[4 * i + 2] << 8) | in.seed[4 * i + 3];
+  q.k = k; q.protocol = (u32)protocol; q.Pall = (u32)n_proofs; q.validate = ctx->opt_validate >= 1 ? 1u : 0u;
+  q.records = d_records; q.extra_sc = d_exsc; q.roles = (uint8_t *)base + r.o_roles;
+  q.T = (const u64 *)(base + r.o_T);
+  return BPMI_OK;
 }
+// the class's transcripts of proofs [first, first + cnt) into its T region; tr_off0: the host's tr_off[0], where the upload began
+static void ipap_transpose_launch(bpmi_ctx *ctx, const IpapRegions &r, uint64_t tr_off0, uint64_t first, u32 cnt, u32 W) {
+  char *base = (char *)ctx->stage_in;
+  hipLaunchKernelGGL(ipad::k_ipap_transpose, dim3((cnt + 63) / 64, (W + 63) / 64), dim3(256), 0, ctx->stream, (const uint8_t *)base + r.o_tr,
+                     (const u64 *)(base + r.o_troff) + first, tr_off0, cnt, W, (u32)IPAP_MAX_TRANSCRIPT, (u64 *)(base + r.o_T));
+}
+
+extern "C" {
 
 int bpmi_ipa_batch_prepare(uint32_t k, int protocol, uint64_t n_proofs, const uint8_t *ab, const uint8_t *xs, const uint8_t *LR, const uint8_t *transcripts,
                            const uint64_t *tr_off, const uint32_t *start, const uint8_t *u, const uint8_t *P, const uint8_t *c, const uint8_t *head,
@@ -41,37 +74,15 @@ static int ipap_run(bpmi_ctx *ctx, const IpapPlan &pl, const IpaPackedIn &in, u3
   hipStream_t st = ctx->stream;
   const u32 k = pl.base.k;
   const uint64_t P = pl.base.n_proofs;
-  auto up = [&](uint64_t off, const void *src, uint64_t bytes) { return bytes ? h2d(ctx, base + off, src, bytes, st) : hipSuccess; };
-  HIPCHK(ctx, up(pl.o_ab, in.ab, pl.b_ab));
-  HIPCHK(ctx, up(pl.o_xs, in.xs, pl.b_xs));
-  HIPCHK(ctx, up(pl.o_lr, in.LR, pl.b_lr));
-  HIPCHK(ctx, up(pl.o_tr, in.transcripts + in.tr_off[0], pl.tr_bytes));
-  HIPCHK(ctx, up(pl.o_troff, in.tr_off, pl.b_troff));
-  HIPCHK(ctx, up(pl.o_start, in.start, pl.b_start));
-  HIPCHK(ctx, up(pl.o_u, in.u, pl.b_u));
-  HIPCHK(ctx, up(pl.o_P, in.P, pl.b_P));
-  HIPCHK(ctx, up(pl.o_c, in.c, pl.b_c));
-  HIPCHK(ctx, up(pl.o_head, in.head, pl.b_head));
-  HIPCHK(ctx, up(pl.o_w, in.weights, pl.b_w));
   ipad::Params q;
-  memset(&q, 0, sizeof(q));
-  q.tr_off = (const u64 *)(base + pl.o_troff);
-  q.start = in.start ? (const u32 *)(base + pl.o_start) : nullptr;
-  q.ab = (const uint8_t *)base + pl.o_ab; q.xs = (const uint8_t *)base + pl.o_xs; q.LR = (const uint8_t *)base + pl.o_lr;
-  q.u = (const uint8_t *)base + pl.o_u; q.P = (const uint8_t *)base + pl.o_P; q.c = (const uint8_t *)base + pl.o_c; q.head = (const uint8_t *)base + pl.o_head;
-  q.weights = in.weights ? (const uint8_t *)base + pl.o_w : nullptr;
-  if (!in.weights)
-    for (int i = 0; i < 8; i++) q.seed[i] = ((u32)in.seed[4 * i] << 24) | ((u32)in.seed[4 * i + 1] << 16) | ((u32)in.seed[4 * i + 2] << 8) | in.seed[4 * i + 3];
-  q.k = k; q.protocol = (u32)pl.protocol; q.Pall = (u32)P; q.validate = ctx->opt_validate >= 1 ? 1u : 0u;
-  q.records = d_records; q.extra_sc = d_exsc; q.roles = (uint8_t *)base + pl.o_roles;
-  q.T = (const u64 *)(base + pl.o_T);
+  const int rc = ipap_stage_class(ctx, pl, in, k, pl.protocol, P, pl.tr_bytes, d_records, d_exsc, q);
+  if (rc) return rc;
   {
     StageTimer t(ctx, ST_RPPREP);
     for (uint64_t first = 0; first < P; first += pl.rows) {
       const u32 cnt = (u32)(P - first < pl.rows ? P - first : pl.rows);
       q.first = first; q.P_launch = cnt; q.Tstride = cnt;
-      hipLaunchKernelGGL(ipad::k_ipap_transpose, dim3((cnt + 63) / 64, (pl.W + 63) / 64), dim3(256), 0, st, (const uint8_t *)base + pl.o_tr, q.tr_off + first,
-                         in.tr_off[0], cnt, pl.W, (u32)IPAP_MAX_TRANSCRIPT, (u64 *)(base + pl.o_T));
+      ipap_transpose_launch(ctx, pl, in.tr_off[0], first, cnt, pl.W);
       hipLaunchKernelGGL(ipad::k_ipap_roles, dim3(IPAP_ROLES * ((cnt + 63) / 64)), dim3(64), (size_t)k * 9 * 64 * 4, st, q);
     }
     const uint64_t pairs_all = P * pl.pairs;
@@ -134,20 +145,7 @@ int bpmi_ipa_verify_batch_packed_dev(bpmi_ctx *ctx, const void *d_g, const void 
   HIPCHK(ctx, hipMemcpyAsync(status, base + pl.o_status, n_proofs, hipMemcpyDeviceToHost, ctx->stream));
   rc = ipab_svector_launches(ctx, bp, d_hscale);
   if (rc) return rc;
-  Segs s = segs_init();
-  s.pts[0] = (const u32 *)d_g; s.sc[0] = (const u32 *)(base + bp.o_sa); s.n[0] = (u32)n;
-  s.pts[1] = (const u32 *)d_h; s.sc[1] = (const u32 *)(base + bp.o_sb); s.n[1] = (u32)n;
-  s.pts[2] = (const u32 *)(base + bp.o_expt); s.sc[2] = (const u32 *)(base + bp.o_exsc); s.n[2] = (u32)bp.n_extra;
-  s.total = (u32)bp.msm_pairs;
-  if (ctx->opt_validate >= 2) { pc.queue(d_g, n, "d_g"); pc.queue(d_h, n, "d_h"); }
-  rc = pc.fetch();
-  if (rc) return rc;
-  rc = msm_run(ctx, s, out);                    // one MSM over the three segments, sliced as any large MSM is (msm_host.hpp)
-  if (rc) return rc;
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  rc = pc.verdict();
-  if (rc) memset(out, 0xFF, 64);
-  return rc;
+  return ipa_verify_msm(ctx, pc, d_g, d_h, n, base + bp.o_sa, base + bp.o_sb, base + bp.o_expt, base + bp.o_exsc, bp.n_extra, false, true, out);
 }
 
 }  // extern "C"

@@ -140,28 +140,6 @@ static inline uint8_t prepare_one(u32 k, int protocol, uint64_t p, const IpaPack
   return 0;
 }
 
-// every proof of the call on `threads` host threads (contiguous ranges); the arguments have passed ipa_packed_plan
-static inline void prepare_all(u32 k, int protocol, uint64_t n_proofs, const IpaPackedIn &in, int threads, uint8_t *records, uint8_t *extra_pts,
-                               uint8_t *extra_scalars, uint8_t *status) {
-  const u32 pairs = ipap_pairs(k, protocol);
-  const size_t rec_bytes = 64 * (size_t)k + 96;
-  auto range = [&](uint64_t lo, uint64_t hi) {
-    rp::Items it;
-    for (uint64_t p = lo; p < hi; p++)
-      status[p] = prepare_one(k, protocol, p, in, records + rec_bytes * p, extra_pts + 64ull * pairs * p, extra_scalars + 32ull * pairs * p, it);
-  };
-  uint64_t T = threads < 1 ? 1 : (uint64_t)threads;
-  if (T > n_proofs) T = n_proofs ? n_proofs : 1;
-  if (T == 1) { range(0, n_proofs); return; }
-  std::vector<std::thread> pool;
-  const uint64_t per = (n_proofs + T - 1) / T;
-  for (uint64_t t = 0; t < T; t++) {
-    const uint64_t lo = t * per, hi = lo + per < n_proofs ? lo + per : n_proofs;
-    if (lo < hi) pool.emplace_back(range, lo, hi);
-  }
-  for (auto &th : pool) th.join();
-}
-
 // ---- a MIXED batch: classes of different k in one call (include/bpmi.h, bpmi_ipa_batch_prepare_mixed).  The specification the
 // kernels k_ipap_roles_mixed / k_ipap_finish_mixed are compared with byte for byte (tests/test_gpu_ipa_packed_mixed.py).
 // One class: its arrays (in.weights: the class's slice of the explicit weights, or null), where its blocks of the outputs begin, and
@@ -197,6 +175,13 @@ static inline void prepare_all_mixed(int protocol, const std::vector<MixedClass>
     if (lo < hi) pool.emplace_back(range, lo, hi);
   }
   for (auto &th : pool) th.join();
+}
+// a UNIFORM call (bpmi_ipa_batch_prepare): one class at gbase 0; the arguments have passed ipa_packed_plan
+static inline void prepare_all(u32 k, int protocol, uint64_t n_proofs, const IpaPackedIn &in, int threads, uint8_t *records, uint8_t *extra_pts,
+                               uint8_t *extra_scalars, uint8_t *status) {
+  MixedClass c;
+  c.k = k; c.n_proofs = n_proofs; c.in = in; c.rec = records; c.pts = extra_pts; c.sc = extra_scalars;
+  prepare_all_mixed(protocol, std::vector<MixedClass>(1, c), threads, status);
 }
 
 }  // namespace ipap

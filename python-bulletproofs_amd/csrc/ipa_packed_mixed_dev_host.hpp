@@ -13,36 +13,14 @@ static int ipapm_run(bpmi_ctx *ctx, const IpapmPlan &mp, const bpmi_ipa_packed_c
                      u32 *d_expts, u32 *d_exsc, std::vector<uint8_t> &tables) {
   char *base = (char *)ctx->stage_in;
   hipStream_t st = ctx->stream;
-  auto up = [&](uint64_t off, const void *src, uint64_t bytes) { return bytes ? h2d(ctx, base + off, src, bytes, st) : hipSuccess; };
   std::vector<ipad::Params> par(mp.n_classes);
   for (u32 c : mp.fin_cls) {
     const IpapmClass &m = mp.cls[c];
-    const bpmi_ipa_packed_class &in = classes[c];
     const uint8_t *w = weights ? weights + 32ull * ipap_weights(mp.protocol) * m.gbase : nullptr;      // the class's slice
-    HIPCHK(ctx, up(m.o_ab, in.ab, m.b_ab));
-    HIPCHK(ctx, up(m.o_xs, in.xs, m.b_xs));
-    HIPCHK(ctx, up(m.o_lr, in.LR, m.b_lr));
-    HIPCHK(ctx, up(m.o_tr, in.transcripts + in.tr_off[0], m.tr_bytes));
-    HIPCHK(ctx, up(m.o_troff, in.tr_off, m.b_troff));
-    HIPCHK(ctx, up(m.o_start, in.start, m.b_start));
-    HIPCHK(ctx, up(m.o_u, in.u, m.b_u));
-    HIPCHK(ctx, up(m.o_P, in.P, m.b_P));
-    HIPCHK(ctx, up(m.o_c, in.c, m.b_c));
-    HIPCHK(ctx, up(m.o_head, in.head, m.b_head));
-    HIPCHK(ctx, up(m.o_w, w, m.b_w));
-    ipad::Params &q = par[c];
-    memset(&q, 0, sizeof(q));
-    q.tr_off = (const u64 *)(base + m.o_troff);
-    q.start = in.start ? (const u32 *)(base + m.o_start) : nullptr;
-    q.ab = (const uint8_t *)base + m.o_ab; q.xs = (const uint8_t *)base + m.o_xs; q.LR = (const uint8_t *)base + m.o_lr;
-    q.u = (const uint8_t *)base + m.o_u; q.P = (const uint8_t *)base + m.o_P; q.c = (const uint8_t *)base + m.o_c; q.head = (const uint8_t *)base + m.o_head;
-    q.weights = w ? (const uint8_t *)base + m.o_w : nullptr;
-    if (!w)
-      for (int i = 0; i < 8; i++) q.seed[i] = ((u32)seed[4 * i] << 24) | ((u32)seed[4 * i + 1] << 16) | ((u32)seed[4 * i + 2] << 8) | seed[4 * i + 3];
-    q.k = m.k; q.protocol = (u32)mp.protocol; q.Pall = (u32)m.n_proofs; q.validate = ctx->opt_validate >= 1 ? 1u : 0u;
-    q.records = d_records + m.rec_off; q.extra_sc = d_exsc + 8 * m.extra_off; q.roles = (uint8_t *)base + m.o_roles;
-    q.T = (const u64 *)(base + m.o_T);
-    q.gbase = m.gbase;
+    const int rc = ipap_stage_class(ctx, m, ipapm_class_in(classes[c], w, seed), m.k, mp.protocol, m.n_proofs, m.tr_bytes, d_records + m.rec_off,
+                                    d_exsc + 8 * m.extra_off, par[c]);
+    if (rc) return rc;
+    par[c].gbase = m.gbase;
   }
   // the unit table (round-major), the class table of the finish and its pair offsets: one piece
   tables.assign(mp.total_bytes - mp.o_units, 0);
@@ -76,8 +54,7 @@ static int ipapm_run(bpmi_ctx *ctx, const IpapmPlan &mp, const bpmi_ipa_packed_c
         const IpapmClass &m = mp.cls[mp.unit[i].cls];
         uint64_t first; u32 cnt;
         rows_of(mp.unit[i], first, cnt);
-        hipLaunchKernelGGL(ipad::k_ipap_transpose, dim3((cnt + 63) / 64, (m.W + 63) / 64), dim3(256), 0, st, (const uint8_t *)base + m.o_tr,
-                           (const u64 *)(base + m.o_troff) + first, classes[mp.unit[i].cls].tr_off[0], cnt, m.W, (u32)IPAP_MAX_TRANSCRIPT, (u64 *)(base + m.o_T));
+        ipap_transpose_launch(ctx, m, classes[mp.unit[i].cls].tr_off[0], first, cnt, m.W);
       }
       hipLaunchKernelGGL(ipad::k_ipap_roles_mixed, dim3(rd.blocks), dim3(64), rd.lds_bytes, st, (const uint8_t *)base + mp.o_units + (size_t)IPAPM_UNIT_STRIDE * rd.first_unit,
                          rd.n_units);
@@ -183,20 +160,7 @@ int bpmi_ipa_verify_batch_packed_mixed_dev(bpmi_ctx *ctx, const void *d_g, const
   HIPCHK(ctx, hipMemcpyAsync(status, base + mp.o_status, mp.b_status, hipMemcpyDeviceToHost, ctx->stream));
   rc = ipam_svector_launches(ctx, bp, d_hscale);          // (waits for the stream: `tables` and the status are done with)
   if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-  Segs s = segs_init();
-  s.pts[0] = (const u32 *)d_g; s.sc[0] = (const u32 *)(base + bp.o_sa); s.n[0] = (u32)bp.n_top;
-  s.pts[1] = (const u32 *)d_h; s.sc[1] = (const u32 *)(base + bp.o_sb); s.n[1] = (u32)bp.n_top;
-  s.pts[2] = (const u32 *)(base + bp.o_expt); s.sc[2] = (const u32 *)(base + bp.o_exsc); s.n[2] = (u32)bp.n_extra;
-  s.total = (u32)bp.msm_pairs;
-  if (ctx->opt_validate >= 2) { pc.queue(d_g, bp.n_top, "d_g"); pc.queue(d_h, bp.n_top, "d_h"); }
-  rc = pc.fetch();
-  if (rc) return rc;
-  rc = msm_run(ctx, s, out);                    // one MSM over the three segments
-  if (rc) return rc;
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  rc = pc.verdict();
-  if (rc) memset(out, 0xFF, 64);
-  return rc;
+  return ipa_verify_msm(ctx, pc, d_g, d_h, bp.n_top, base + bp.o_sa, base + bp.o_sb, base + bp.o_expt, base + bp.o_exsc, bp.n_extra, false, true, out);
 }
 
 // test hook: the transposition budget of the mixed packed calls of this ctx (0: the default)

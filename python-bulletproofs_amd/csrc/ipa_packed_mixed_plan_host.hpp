@@ -33,7 +33,7 @@
 #define IPAPM_CLASSES_MAX 64u
 #define IPAPM_UNIT_STRIDE 256u                 // bytes of one slot of the unit table and of the class table (ipad::MixedUnit, ipa_packed_kernels.hpp)
 
-struct IpapmClass {
+struct IpapmClass : IpapRegions {              // its regions (the status is the call's, the T region follows the status)
   u32 k = 0, pairs = 0;
   uint64_t n_proofs = 0;                       // 0: skipped, nothing else is set
   uint64_t gbase = 0;                          // global index of its proof 0
@@ -41,9 +41,6 @@ struct IpapmClass {
   uint64_t extra_off = 0;                      // its first extra pair
   u32 W = 0, rows = 0, chunks = 0;             // 8-byte rows of T; proofs per round; rounds it takes part in
   uint64_t tr_bytes = 0;
-  // the regions of IpapPlan, per class (the status is the call's, the T region follows the status)
-  uint64_t o_ab = 0, o_xs = 0, o_lr = 0, o_tr = 0, o_troff = 0, o_start = 0, o_u = 0, o_P = 0, o_c = 0, o_head = 0, o_w = 0, o_roles = 0, o_T = 0;
-  uint64_t b_ab = 0, b_xs = 0, b_lr = 0, b_tr = 0, b_troff = 0, b_start = 0, b_u = 0, b_P = 0, b_c = 0, b_head = 0, b_w = 0, b_roles = 0, b_T = 0;
 };
 struct IpapmUnit { u32 cls, chunk, first_block; };      // rows [chunk rows, min(P, (chunk + 1) rows)) of class cls
 struct IpapmRound { u32 first_unit = 0, n_units = 0, blocks = 0, lds_bytes = 0, k_max = 0; };
@@ -65,11 +62,9 @@ struct IpapmPlan {
 };
 
 static inline IpapmPlan ipapm_plan_error(const std::string &msg) { IpapmPlan p; p.err = BPMI_E_ARG; p.msg = msg; return p; }
+// a class's arrays with the call's weights (the class's slice, or NULL) and seed
 static inline IpaPackedIn ipapm_class_in(const bpmi_ipa_packed_class &c, const uint8_t *weights, const uint8_t *seed) {
-  IpaPackedIn in;
-  in.ab = c.ab; in.xs = c.xs; in.LR = c.LR; in.transcripts = c.transcripts; in.tr_off = c.tr_off; in.start = c.start;
-  in.u = c.u; in.P = c.P; in.c = c.c; in.head = c.head; in.weights = weights; in.seed = seed;
-  return in;
+  return ipap_in(c.ab, c.xs, c.LR, c.transcripts, c.tr_off, c.start, c.u, c.P, c.c, c.head, weights, seed);
 }
 
 // K: the capacity, n_gens = 2^K.  weights / seed: the call's (their addresses are never followed).  has_scale: as ipa_mixed_plan (0 for
@@ -84,16 +79,15 @@ static inline IpapmPlan ipa_packed_mixed_plan(const BpmiOptions &opt, u32 K, int
   p.protocol = protocol; p.n_classes = n_classes;
   p.cls.resize(n_classes);
   uint64_t total = 0, n_extra = 0, tr_bytes = 0;
-  std::vector<IpapPlan> single(n_classes);
   for (u32 c = 0; c < n_classes; c++) {
     const bpmi_ipa_packed_class &in = classes[c];
     if (!in.n_proofs) continue;
     const std::string who = "class " + std::to_string(c) + ": ";
     if (in.k > K) return ipapm_plan_error(who + "k must be at most K (proofs of 2^k elements over n_gens = 2^K generators)");
-    single[c] = ipa_packed_plan(opt, in.k, protocol, in.n_proofs, ipapm_class_in(in, weights, seed), 0);
-    if (single[c].err) return ipapm_plan_error(who + single[c].msg);
+    const IpapPlan single = ipa_packed_plan(opt, in.k, protocol, in.n_proofs, ipapm_class_in(in, weights, seed), 0);      // the class's errors, W
+    if (single.err) return ipapm_plan_error(who + single.msg);
     IpapmClass &m = p.cls[c];
-    m.k = in.k; m.pairs = single[c].pairs; m.n_proofs = in.n_proofs; m.gbase = total; m.extra_off = n_extra; m.tr_bytes = single[c].tr_bytes; m.W = single[c].W;
+    m.k = in.k; m.pairs = single.pairs; m.n_proofs = in.n_proofs; m.gbase = total; m.extra_off = n_extra; m.tr_bytes = single.tr_bytes; m.W = single.W;
     total += in.n_proofs; n_extra += in.n_proofs * m.pairs; tr_bytes += m.tr_bytes;
     p.fin_cls.push_back(c);
   }
@@ -116,7 +110,6 @@ static inline IpapmPlan ipa_packed_mixed_plan(const BpmiOptions &opt, u32 K, int
   u32 n_rounds = 0;
   for (u32 c : p.fin_cls) {
     IpapmClass &m = p.cls[c];
-    const IpapPlan &s = single[c];
     m.first_sorted = where[(size_t)m.gbase];
     m.rec_off = p.base.desc[m.first_sorted].rec_off;
     uint64_t rows = share / (8ull * m.W) / 64 * 64;
@@ -124,10 +117,10 @@ static inline IpapmPlan ipa_packed_mixed_plan(const BpmiOptions &opt, u32 K, int
     m.rows = (u32)(rows < m.n_proofs ? rows : m.n_proofs);
     m.chunks = (u32)((m.n_proofs + m.rows - 1) / m.rows);
     if (m.chunks > n_rounds) n_rounds = m.chunks;
-    m.b_ab = s.b_ab; m.b_xs = s.b_xs; m.b_lr = s.b_lr; m.b_tr = s.b_tr; m.b_troff = s.b_troff; m.b_start = s.b_start; m.b_u = s.b_u; m.b_P = s.b_P;
-    m.b_c = s.b_c; m.b_head = s.b_head; m.b_w = s.b_w; m.b_roles = s.b_roles; m.b_T = 8ull * m.W * m.rows;
-    m.o_ab = take(m.b_ab); m.o_xs = take(m.b_xs); m.o_lr = take(m.b_lr); m.o_tr = take(m.b_tr); m.o_troff = take(m.b_troff); m.o_start = take(m.b_start);
-    m.o_u = take(m.b_u); m.o_P = take(m.b_P); m.o_c = take(m.b_c); m.o_head = take(m.b_head); m.o_w = take(m.b_w); m.o_roles = take(m.b_roles);
+    // (has_start / has_weights as ipapm_class_in gave them to the class's ipa_packed_plan above: for ONE class this is that plan's layout)
+    ipap_region_sizes(m, m.k, protocol, m.n_proofs, classes[c].start != nullptr, weights != nullptr, m.tr_bytes);
+    m.b_T = 8ull * m.W * m.rows;
+    ipap_place_regions(m, take);
   }
   p.b_status = total; p.o_status = take(p.b_status);
   for (u32 c : p.fin_cls) p.cls[c].o_T = take(p.cls[c].b_T);

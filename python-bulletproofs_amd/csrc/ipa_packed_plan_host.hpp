@@ -23,10 +23,42 @@ struct IpaPackedIn {
   const uint8_t *weights = nullptr, *seed = nullptr;
 };
 
+static inline IpaPackedIn ipap_in(const uint8_t *ab, const uint8_t *xs, const uint8_t *LR, const uint8_t *transcripts, const uint64_t *tr_off, const uint32_t *start,
+                                  const uint8_t *u, const uint8_t *P, const uint8_t *c, const uint8_t *head, const uint8_t *weights, const uint8_t *seed) {
+  IpaPackedIn in;
+  in.ab = ab; in.xs = xs; in.LR = LR; in.transcripts = transcripts; in.tr_off = tr_off; in.start = start;
+  in.u = u; in.P = P; in.c = c; in.head = head; in.weights = weights; in.seed = seed;
+  return in;
+}
+
 static inline u32 ipap_pairs(u32 k, int protocol) { return 2u * k + (protocol == 1 ? 4u : 2u); }       // extra pairs of one proof
 static inline u32 ipap_weights(int protocol) { return protocol == 1 ? 3u : 1u; }                       // explicit weights of one proof
 
-struct IpapPlan {
+// The upload regions of ONE class of proofs of one k (a whole uniform call, or a class of a mixed one): byte offsets into
+// ctx->stage_in and sizes, every region on a 256-byte line
+//   ab 64 P | xs 32 k P | LR 128 k P | transcripts (+ 8 bytes the transpose may read) | tr_off 8 (P + 1) | start 4 P (Protocol 2 with starts) |
+//   u 64 P or 64 | P 64 P | c 32 P | head 128 P (Protocol 1) | weights 32 P or 96 P (explicit) | role verdicts 4 P
+// and T, 8 W rows: the transposed transcripts of one launch, which the owner sizes (its rows) and places (behind its status)
+struct IpapRegions {
+  uint64_t o_ab = 0, o_xs = 0, o_lr = 0, o_tr = 0, o_troff = 0, o_start = 0, o_u = 0, o_P = 0, o_c = 0, o_head = 0, o_w = 0, o_roles = 0, o_T = 0;
+  uint64_t b_ab = 0, b_xs = 0, b_lr = 0, b_tr = 0, b_troff = 0, b_start = 0, b_u = 0, b_P = 0, b_c = 0, b_head = 0, b_w = 0, b_roles = 0, b_T = 0;
+};
+// the sizes, all but b_T
+static inline void ipap_region_sizes(IpapRegions &r, u32 k, int protocol, uint64_t n_proofs, bool has_start, bool has_weights, uint64_t tr_bytes) {
+  r.b_ab = 64 * n_proofs; r.b_xs = 32ull * k * n_proofs; r.b_lr = 128ull * k * n_proofs;
+  r.b_tr = tr_bytes + 8; r.b_troff = 8 * (n_proofs + 1); r.b_start = has_start ? 4 * n_proofs : 0;
+  r.b_u = protocol == 1 ? 64 : 64 * n_proofs; r.b_P = 64 * n_proofs;
+  r.b_c = protocol == 1 ? 32 * n_proofs : 0; r.b_head = protocol == 1 ? 128 * n_proofs : 0;
+  r.b_w = has_weights ? 32ull * ipap_weights(protocol) * n_proofs : 0;
+  r.b_roles = IPAP_ROLES * n_proofs;
+}
+// ab .. role verdicts in this order behind the cursor (take(bytes): the offset of the next region of `bytes`)
+template <class Take> static inline void ipap_place_regions(IpapRegions &r, Take &take) {
+  r.o_ab = take(r.b_ab); r.o_xs = take(r.b_xs); r.o_lr = take(r.b_lr); r.o_tr = take(r.b_tr); r.o_troff = take(r.b_troff); r.o_start = take(r.b_start);
+  r.o_u = take(r.b_u); r.o_P = take(r.b_P); r.o_c = take(r.b_c); r.o_head = take(r.b_head); r.o_w = take(r.b_w); r.o_roles = take(r.b_roles);
+}
+
+struct IpapPlan : IpapRegions {
   int err = 0; const char *msg = nullptr;      // an argument error: nothing else is set
   IpabPlan base;                               // the unchanged plan: SA, SB, records, tables, partial sums, extra pairs (, scale)
   int protocol = 0;
@@ -35,12 +67,8 @@ struct IpapPlan {
   u32 longest = 0;                             // the longest transcript, cut at IPAP_MAX_TRANSCRIPT
   u32 W = 0;                                   // 8-byte rows of the transposed array: ceil(longest / 8) + IPAP_T_PAD_WORDS
   u32 rows = 0;                                // proofs per launch of the preparation kernels (a multiple of 64, or all)
-  // the upload regions: byte offsets into ctx->stage_in behind base.total_bytes, every region on a 256-byte line
-  //   ab 64 P | xs 32 k P | LR 128 k P | transcripts (+ 8 bytes the transpose may read) | tr_off 8 (P + 1) | start 4 P (Protocol 2 with starts) |
-  //   u 64 P or 64 | P 64 P | c 32 P | head 128 P (Protocol 1) | weights 32 P or 96 P (explicit) | role verdicts 4 P | status P |
-  //   T 8 W rows
-  uint64_t o_ab = 0, o_xs = 0, o_lr = 0, o_tr = 0, o_troff = 0, o_start = 0, o_u = 0, o_P = 0, o_c = 0, o_head = 0, o_w = 0, o_roles = 0, o_status = 0, o_T = 0;
-  uint64_t b_ab = 0, b_xs = 0, b_lr = 0, b_tr = 0, b_troff = 0, b_start = 0, b_u = 0, b_P = 0, b_c = 0, b_head = 0, b_w = 0, b_roles = 0, b_status = 0, b_T = 0;
+  // behind base.total_bytes: the regions ab .. role verdicts | status P | T 8 W rows
+  uint64_t o_status = 0, b_status = 0;
   uint64_t total_bytes = 0;
 };
 
@@ -73,18 +101,13 @@ static inline IpapPlan ipa_packed_plan(const BpmiOptions &opt, u32 k, int protoc
   p.W = (p.longest + 7u) / 8u + IPAP_T_PAD_WORDS;
   uint64_t rows = IPAP_T_BYTES_MAX / (8ull * p.W) / 64 * 64;
   p.rows = (u32)(rows < n_proofs ? rows : n_proofs);
-  p.b_ab = 64 * n_proofs; p.b_xs = 32ull * k * n_proofs; p.b_lr = 128ull * k * n_proofs;
-  p.b_tr = p.tr_bytes + 8; p.b_troff = 8 * (n_proofs + 1); p.b_start = in.start ? 4 * n_proofs : 0;
-  p.b_u = protocol == 1 ? 64 : 64 * n_proofs; p.b_P = 64 * n_proofs;
-  p.b_c = protocol == 1 ? 32 * n_proofs : 0; p.b_head = protocol == 1 ? 128 * n_proofs : 0;
-  p.b_w = in.weights ? 32ull * ipap_weights(protocol) * n_proofs : 0;
-  p.b_roles = IPAP_ROLES * n_proofs; p.b_status = n_proofs;
+  ipap_region_sizes(p, k, protocol, n_proofs, in.start != nullptr, in.weights != nullptr, p.tr_bytes);
+  p.b_status = n_proofs;
   p.b_T = 8ull * p.W * p.rows;
   uint64_t at = p.base.total_bytes;
   auto take = [&at](uint64_t bytes) { const uint64_t o = at; at += align_up(bytes, 256); return o; };
-  p.o_ab = take(p.b_ab); p.o_xs = take(p.b_xs); p.o_lr = take(p.b_lr); p.o_tr = take(p.b_tr); p.o_troff = take(p.b_troff); p.o_start = take(p.b_start);
-  p.o_u = take(p.b_u); p.o_P = take(p.b_P); p.o_c = take(p.b_c); p.o_head = take(p.b_head); p.o_w = take(p.b_w);
-  p.o_roles = take(p.b_roles); p.o_status = take(p.b_status); p.o_T = take(p.b_T);
+  ipap_place_regions(p, take);
+  p.o_status = take(p.b_status); p.o_T = take(p.b_T);
   p.total_bytes = at;
   return p;
 }
