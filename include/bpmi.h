@@ -868,6 +868,28 @@ int bpmi_ipa_batch_prepare_mixed_dev(bpmi_ctx *ctx, uint32_t K, int protocol, ui
 int bpmi_ipa_verify_batch_packed_mixed_dev(bpmi_ctx *ctx, const void *d_g, const void *d_h, const void *d_hscale, uint64_t n_gens, int protocol,
                                            uint32_t n_classes, const bpmi_ipa_packed_class *classes, const uint8_t *weights, const uint8_t *seed,
                                            uint8_t out[64], uint8_t *status);
+/* Which GROUPS of a list of classes hold an invalid proof, in one call: bpmi_ipa_group_values_packed_dev for the mixed packed call.
+ * The preparation of bpmi_ipa_verify_batch_packed_mixed_dev and its half tables run once; the s-vectors are summed per group of
+ * consecutive proofs of ONE class (one launch over every class's rows), and the groups' MSMs over [g[:n_c] | h[:n_c] | the group's
+ * extra pairs] run as at most one launch per block shape over (group, window) with one device tail -- or, for a class whose
+ * 2 n_c + group x (2k + 2 | 2k + 4) pairs exceed 8 448, as one MSM per group.  Arguments up to `classes`, `weights`, `seed` and
+ * `status` (global class-major index, bits 0 and 1) as in bpmi_ipa_verify_batch_packed_mixed_dev.
+ *   group      n_classes entries, each >= 1 (not read for an empty class): class c is cut into groups of min(group[c], n_proofs_c)
+ *              consecutive proofs, the last one possibly short.  A group never straddles a class; an empty class has none.
+ *   value_off  HOST memory, n_classes + 1 entries: groups are numbered class-major and class c owns the values
+ *              [value_off[c], value_off[c + 1]); value_off[n_classes] is the number of groups
+ *   values     HOST memory, 64 B per group: values[t] = the combination over the unflagged proofs of group t over
+ *              [g[:n_c] | h[:n_c] | that group's extra pairs]; 64 zero bytes exactly when all of them verify.  The sum of all values is
+ *              the `out` of the verify call under the same weights
+ *   a flagged proof takes part in no group.  The call gives no verdict: the values and the status are the result.
+ * Every class empty: BPMI_OK, value_off all zero, values untouched.  BPMI_E_ARG before anything is read beyond tr_off, allocated or
+ * uploaded, and nothing is written: what the mixed packed verify call refuses, with its messages; group NULL or a group[c] = 0 on a
+ * non-empty class (the message names the class); values, value_off or status NULL; the sum over the classes of n_groups x 2 n_c
+ * above 2^26 (the rows of group scalars).  A call refused for a point (a class's u under protocol 1; one of the first n_top generators
+ * at "validate_points" = 2) leaves 0xFF in every byte of values.  bpmi_debug_ipap_t_budget applies.  One call at a time per ctx. */
+int bpmi_ipa_group_values_packed_mixed_dev(bpmi_ctx *ctx, const void *d_g, const void *d_h, const void *d_hscale, uint64_t n_gens, int protocol,
+                                           uint32_t n_classes, const bpmi_ipa_packed_class *classes, const uint64_t *group, const uint8_t *weights,
+                                           const uint8_t *seed, uint8_t *values, uint64_t *value_off, uint8_t *status);
 /* test hook (not part of the drop-in surface): the byte budget of the transposed transcripts of ONE round of the mixed packed calls
  * on this ctx (0: the default, 2^28) -- a small value makes a few hundred proofs run as several rounds.  It also bounds one preparation
  * launch of bpmi_ipa_group_values_packed_dev (at least 64 proofs).  Not an option. */

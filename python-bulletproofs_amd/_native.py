@@ -105,6 +105,8 @@ SIGNATURES = {
     "bpmi_ipa_batch_prepare_mixed": (_i, [ctypes.c_uint32, _i, ctypes.c_uint32, _vp, _cp, _cp, _i, _vp, _vp, _vp, _vp, _vp]),
     "bpmi_ipa_batch_prepare_mixed_dev": (_i, [_vp, ctypes.c_uint32, _i, ctypes.c_uint32, _vp, _cp, _cp, _vp, _vp, _vp, _vp, _vp]),
     "bpmi_ipa_verify_batch_packed_mixed_dev": (_i, [_vp, _vp, _vp, _vp, _u64, _i, ctypes.c_uint32, _vp, _cp, _cp, _vp, _vp]),
+    # ... classes, group (n_classes x uint64), weights, seed, values, value_off (n_classes + 1 x uint64), status
+    "bpmi_ipa_group_values_packed_mixed_dev": (_i, [_vp, _vp, _vp, _vp, _u64, _i, ctypes.c_uint32, _vp, _vp, _cp, _cp, _vp, _vp, _vp]),
     "bpmi_debug_ipap_t_budget": (_i, [_vp, _u64]),
     "bpmi_host_alloc": (_i, [_vp, ctypes.c_size_t, ctypes.POINTER(_vp)]),
     "bpmi_host_free": (_i, [_vp, _vp]),

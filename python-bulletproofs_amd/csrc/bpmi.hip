@@ -65,6 +65,7 @@ using namespace bpmi;
 #include "ipa_packed_plan_host.hpp"
 #include "ipa_packed_mixed_plan_host.hpp"
 #include "ipa_group_plan_host.hpp"
+#include "ipa_group_mixed_plan_host.hpp"
 #include "msm_batch_plan_host.hpp"
 #include "msm_fixed_plan_host.hpp"
 #include "context.hpp"
@@ -890,6 +891,7 @@ int bpmi_ipa_verify_dev(bpmi_ctx *ctx, const void *d_g, const void *d_h, const v
 #include "ipa_packed_dev_host.hpp"
 #include "ipa_packed_mixed_dev_host.hpp"
 #include "ipa_group_dev_host.hpp"
+#include "ipa_group_mixed_dev_host.hpp"
 #include "msm_batch_host.hpp"
 #include "rp_batch_dev_host.hpp"
 #include "rp_mixed_dev_host.hpp"

@@ -9,12 +9,9 @@
 
 extern "C" {
 
-// the three launches that leave SA and SB in the workspace, from the proofs' records (sorted order) that are in the workspace
-// already: uploaded by ipam_svector_sum, or written there by the preparation kernels (ipa_packed_mixed_dev_host.hpp).  Only the control
-// regions -- descriptors, C table, units, block index -- are uploaded here, as one piece.
-static int ipam_svector_launches(bpmi_ctx *ctx, const IpamPlan &pl, const void *d_scale) {
+// the control regions -- descriptors, C table, units, block index -- uploaded as one piece and waited for
+static int ipam_control_upload(bpmi_ctx *ctx, const IpamPlan &pl) {
   char *base = (char *)ctx->stage_in;
-  const u32 P = (u32)pl.n_proofs;
   std::vector<uint8_t> control(pl.o_tab - pl.o_desc);
   uint8_t *at = control.data();
   memcpy(at, pl.desc.data(), pl.b_desc);
@@ -23,14 +20,28 @@ static int ipam_svector_launches(bpmi_ctx *ctx, const IpamPlan &pl, const void *
   memcpy(at + (pl.o_blocks - pl.o_desc), pl.block_first.data(), pl.b_blocks);
   HIPCHK(ctx, h2d(ctx, base + pl.o_desc, control.data(), control.size(), ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));          // control (and the caller's records) are owned by host frames
+  return BPMI_OK;
+}
+// every proof's half tables from the records in the workspace: one launch (inside the caller's stage timer)
+static void ipam_tables_launch(bpmi_ctx *ctx, const IpamPlan &pl) {
+  char *base = (char *)ctx->stage_in;
+  const u32 n_records = (u32)pl.tab_entries;
+  hipLaunchKernelGGL(k_sc_svector_tables_mixed, dim3((n_records + IPAB_THREADS - 1) / IPAB_THREADS), dim3(IPAB_THREADS), 0, ctx->stream,
+                     (const u32 *)(base + pl.o_rec), (const u32 *)(base + pl.o_desc), (u32)pl.n_proofs, n_records, (u32 *)(base + pl.o_tab));
+}
+// the three launches that leave SA and SB in the workspace, from the proofs' records (sorted order) that are in the workspace
+// already: uploaded by ipam_svector_sum, or written there by the preparation kernels (ipa_packed_mixed_dev_host.hpp).  Only the control
+// regions are uploaded here.  (The group call, ipa_group_mixed_dev_host.hpp, takes the upload and the tables alone.)
+static int ipam_svector_launches(bpmi_ctx *ctx, const IpamPlan &pl, const void *d_scale) {
+  char *base = (char *)ctx->stage_in;
+  const int rc = ipam_control_upload(ctx, pl);
+  if (rc) return rc;
   const u32 *desc = (const u32 *)(base + pl.o_desc), *tabs = (const u32 *)(base + pl.o_tab);
   u32 *sa = (u32 *)(base + pl.o_sa), *sb = (u32 *)(base + pl.o_sb), *part = (u32 *)(base + pl.o_part);
   const u32 n_top = (u32)pl.n_top;
   {
     StageTimer t(ctx, ST_SCFOLD);
-    const u32 n_records = (u32)pl.tab_entries;
-    hipLaunchKernelGGL(k_sc_svector_tables_mixed, dim3((n_records + IPAB_THREADS - 1) / IPAB_THREADS), dim3(IPAB_THREADS), 0, ctx->stream,
-                       (const u32 *)(base + pl.o_rec), desc, P, n_records, (u32 *)(base + pl.o_tab));
+    ipam_tables_launch(ctx, pl);
     hipLaunchKernelGGL(k_sc_svector_sum_mixed, dim3(pl.n_units), dim3(IPAB_THREADS), 0, ctx->stream, tabs, desc, (const u32 *)(base + pl.o_ctab),
                        (const u32 *)(base + pl.o_units), n_top, pl.direct ? 1u : 0u, pl.direct ? sa : part, pl.direct ? sb : part);
     if (!pl.direct)

@@ -47,3 +47,15 @@ __global__ void __launch_bounds__(256) k_sc_svector_sum_finish_mixed(const u32 *
   store_words8(sa + 8ull * i, ra);
   store_words8(sb + 8ull * i, rb);
 }
+// The sums per GROUP of consecutive proofs of one class, for every class of a mixed packed batch in ONE launch
+// (bpmi_ipa_group_values_packed_mixed_dev; plan: ipa_group_mixed_plan_host.hpp): rows SA[t][i], SB[t][i] of n_c = 2^k_c scalars,
+// canonical, SB with the shared scale c_i -- k_sc_svector_sum_groups (scalar_kernels.hpp) over classes of different row lengths.  A
+// class's rows start at a multiple of 256 scalars, so a block belongs to one class and looks it up with its own index
+// (svm_group_row_element, svector_mixed.hpp); pad lanes behind a class's last row return.
+__global__ void __launch_bounds__(256) k_sc_svector_sum_groups_mixed(const u32 *__restrict__ tabs, const u32 *__restrict__ ctab, u32 n_cls,
+                                                                     const u32 *__restrict__ scale, u32 *__restrict__ sa, u32 *__restrict__ sb) {
+  u32 ra[8], rb[8], idx;
+  if (!svm_group_row_element(ra, rb, idx, tabs, ctab, n_cls, scale, blockIdx.x, threadIdx.x)) return;
+  store_words8(sa + 8ull * idx, ra);
+  store_words8(sb + 8ull * idx, rb);
+}

@@ -2026,6 +2026,41 @@ template <u32 THREADS, u32 NMAX> __global__ void __launch_bounds__(THREADS) k_ms
 template __global__ void k_msm_ipa_group<MID_THREADS, MID_NMAX>(IpaGroupMsm);
 template __global__ void k_msm_ipa_group<GROUP_LIGHT_THREADS, GROUP_LIGHT_NMAX>(IpaGroupMsm);
 
+// The groups of a list of CLASSES of packed inner-product proofs of different lengths (bpmi_ipa_group_values_packed_mixed_dev,
+// ipa_group_mixed_plan_host.hpp): k_msm_ipa_group where every group has its own n -- the prefixes g[:n_c], h[:n_c] of one generator
+// list --, its own row in the packed rows SA / SB and its own run of extra pairs, read from a table of four words per group (n_c, row
+// offset in scalars, first extra pair, extra pairs).  A launch runs the groups of `list` (those of one shape): block (slot, w) =
+// blockIdx.x runs window w of group list[slot]; its window sums go to E[group][w], so one k_group_tail serves both launches.  The
+// plan puts a group in a launch only where 2 n_c + its extra pairs fit NMAX.
+struct IpaGroupMixedMsm {
+  const u32 *g, *h;                   // the generator lists (a group reads the first n_c of either)
+  const u32 *sa, *sb;                 // the packed rows
+  const u32 *x_pts, *x_sc;            // extra points and their scalars of all classes, class-major, proof-major inside a class
+  const u32 *gtab, *list;             // four words per group; the groups of this launch
+  u32 W;
+  u32 *E;                             // [group][w]
+};
+template <u32 THREADS, u32 NMAX> __global__ void __launch_bounds__(THREADS) k_msm_ipa_group_mixed(IpaGroupMixedMsm J) {
+  const u32 slot = blockIdx.x / J.W, w = blockIdx.x - slot * J.W;
+  const u32 t = J.list[slot];
+  const u32 *d = J.gtab + 4ull * t;
+  const u32 n = d[0], row = d[1], x0 = d[2], xn = d[3];
+  Segs s;
+  s.pts[0] = J.g; s.sc[0] = J.sa + 8ull * row; s.n[0] = n;
+  s.pts[1] = J.h; s.sc[1] = J.sb + 8ull * row; s.n[1] = n;
+  s.pts[2] = J.x_pts + 16ull * x0; s.sc[2] = J.x_sc + 8ull * x0; s.n[2] = xn;
+  s.total = s.n[0] + s.n[1] + s.n[2];
+  s.hlog[0] = s.hlog[1] = s.hlog[2] = 0xFFu;
+  s.phase[0] = s.phase[1] = s.phase[2] = 0;
+  s.glv_sub = nullptr; s.glv_neg = nullptr; s.glv_bx = nullptr;
+  MsmGeom g = {};                                  // (the body reads n and W only)
+  g.n = s.total; g.c = MID_C; g.W = J.W; g.B = MID_B;
+  u32 *const Et = J.E + (u64)t * J.W * XYZZ_WORDS;
+  msm_mid_block<THREADS, NMAX>(s, g, w, 1u, 0u, Et);
+}
+template __global__ void k_msm_ipa_group_mixed<MID_THREADS, MID_NMAX>(IpaGroupMixedMsm);
+template __global__ void k_msm_ipa_group_mixed<GROUP_LIGHT_THREADS, GROUP_LIGHT_NMAX>(IpaGroupMixedMsm);
+
 // ---- tail: result = sum_w 2^(c w) sum_v 2^(off[v]) E[w][v], to canonical affine -------------
 BPMI_HD void msm_tail_combine(u32 out_words[16], const u32 *E, u32 W, u32 c, const TailOffs &to) {
   // ONE Horner chain over bit positions: E[w][v] carries weight 2^(start of window w + off[v]), so walking from the top bit down

@@ -95,4 +95,29 @@ BPMI_HD void svm_finish_element(u32 out_a[8], u32 out_b[8], const u32 *part, con
   for (int q = 0; q < 8; q++) { out_a[q] = A.v[q]; out_b[q] = B.v[q]; }
 }
 
+// Lane `lane` of block `block` of k_sc_svector_sum_groups_mixed (bpmi_ipa_group_values_packed_mixed_dev; ipa_group_mixed_plan_host.hpp):
+// the rows of every class's groups in one launch.  ctab: 8 words per class that has groups, in rising order of the block start -- block
+// start, row offset in scalars (256 block start), k, kl, table base and stride in records, proofs, group.  The block belongs to the last
+// class whose block start is <= block: a scan of at most 64 entries with the block's index, the same in every lane, so the entries
+// come by scalar loads and the class's eight words stay in scalar registers.  local = 256 (block - block start) + lane is the flat
+// (group, element) index of k_sc_svector_sum_groups inside the class: t = local >> k, i = local & (n - 1) -- for n < 64 several groups
+// share a wave.  Returns false for a pad lane (t beyond the class's groups), which writes nothing; else the two scalars of
+// svb_group_element over the class's own tables, and idx = row offset + local, the scalar they belong to in rows SA / rows SB.
+BPMI_HD bool svm_group_row_element(u32 out_a[8], u32 out_b[8], u32 &idx, const u32 *tabs, const u32 *ctab, u32 n_cls, const u32 *scale, u32 block, u32 lane) {
+  const u32 b = SVM_UNIFORM(block);
+  u32 c = 0;
+  for (u32 j = 1; j < n_cls; j++)
+    if (SVM_UNIFORM(ctab[8ull * j]) <= b) c = j;
+  const u32 *d = ctab + 8ull * c;
+  const u32 start = SVM_UNIFORM(d[0]), row_off = SVM_UNIFORM(d[1]), k = SVM_UNIFORM(d[2]), kl = SVM_UNIFORM(d[3]);
+  const u32 base = SVM_UNIFORM(d[4]), stride = SVM_UNIFORM(d[5]), count = SVM_UNIFORM(d[6]), group = SVM_UNIFORM(d[7]);
+  const u32 local = (b - start) * 256u + lane;
+  const u32 t = local >> k, i = local & ((1u << k) - 1u);
+  const u32 ngroups = (count + group - 1u) / group;
+  if (t >= ngroups) return false;
+  svb_group_element(out_a, out_b, tabs + 16ull * base, stride, kl, i, t, group, count, scale);
+  idx = row_off + local;
+  return true;
+}
+
 }  // namespace bpmi

@@ -392,6 +392,27 @@ class Engine:
         del keep
         return out.raw, status.raw[:total]
 
+    def ipa_group_values_packed_mixed_dev(self, d_g, d_h, n_gens, protocol, classes, groups, weights=None, seed=None, d_hscale=None):
+        """(values, value_off, status) of bpmi_ipa_group_values_packed_mixed_dev.  classes: as ipa_verify_batch_packed_mixed_dev; groups: one
+        group size per class.  values: one 64-byte string per group, class-major -- class c owns values[value_off[c]: value_off[c + 1]],
+        groups of min(groups[c], count_c) consecutive proofs, the last one possibly short; values[t] is the weighted combination over
+        the unflagged proofs of group t (identity = all of them verify).  status: one byte per proof, class-major."""
+        if len(groups) != len(classes):
+            raise ValueError("one group size per class")
+        arr, keep, total, _, _ = packed_class_array(protocol, classes)
+        ngroups = sum((cl[1] + min(max(int(g), 1), cl[1]) - 1) // min(max(int(g), 1), cl[1]) for cl, g in zip(classes, groups) if cl[1])
+        grp = (ctypes.c_uint64 * max(len(classes), 1))(*[int(g) for g in groups])
+        offs = (ctypes.c_uint64 * (len(classes) + 1))()
+        values, status = ctypes.create_string_buffer(max(64 * ngroups, 1)), ctypes.create_string_buffer(max(total, 1))
+        self._ck(self.lib.bpmi_ipa_group_values_packed_mixed_dev(self.ctx, _ptr(d_g), _ptr(d_h), None if d_hscale is None else _ptr(d_hscale), n_gens, protocol,
+                                                                 len(classes), ctypes.addressof(arr), ctypes.addressof(grp), weights, seed,
+                                                                 ctypes.cast(values, ctypes.c_void_p), ctypes.addressof(offs), ctypes.cast(status, ctypes.c_void_p)))
+        del keep
+        raw, offs = values.raw, list(offs)
+        if offs[-1] != ngroups:
+            raise RuntimeError("bpmi_ipa_group_values_packed_mixed_dev wrote %d groups where %d were expected" % (offs[-1], ngroups))
+        return [raw[64 * t: 64 * t + 64] for t in range(ngroups)], offs, status.raw[:total]
+
     def ipap_t_budget(self, nbytes):
         """bpmi_debug_ipap_t_budget (tests): the transposition budget of the mixed packed calls and of ipa_group_values_packed_dev on this engine; 0 restores
         the default."""

@@ -6,10 +6,11 @@ A generator list is a capacity: a statement of n_p = 2^k_p elements is made over
 verifier is Verifier2(g[:n_p], h[:n_p], ...).  Under the random weights of BatchInnerProductVerifier (batch.py: its soundness note
 applies unchanged) generator i collects the weighted s-vector entries of the proofs that reach it, so arguments of 64, 256 and 4 096
 elements are one MSM of 2 n_top + (extra pairs), n_top the longest length queued, instead of one batch per length plus a sum."""
+import math
 import secrets
 
 from ..ec import pack_points, pack_scalars
-from .batch import CALL_MAX, BatchInnerProductVerifier, Q, _Item, locate_by_bisection
+from .batch import CALL_MAX, GROUP_MAX_PAIRS, GROUP_ROWS_MAX, BatchInnerProductVerifier, Q, _Item, locate_by_bisection
 from .inner_product_verifier import Verifier2
 
 
@@ -194,14 +195,126 @@ class MixedBatchInnerProductVerifier:
         takes them; weights: three integers (w, r1, r2) per proof, class-major, instead of the random ones (tests)."""
         return self._verify_packed_mixed(1, classes, weights)
 
-    def locate_packed2(self, classes):
-        """The sorted GLOBAL (class-major) indices of the invalid proofs of a list of packed Protocol-2 classes: those the status bytes
-        flag, and the rest found by locate_by_bisection, every probe one mixed native call over the gathered rows of the subset."""
-        return self._locate_packed_mixed(2, classes)
+    # ---- packed classes, per GROUP of consecutive proofs of one class: one native call names the groups that hold an invalid proof --
+    # bpmi_ipa_group_values_packed_mixed_dev (csrc/ipa_group_mixed_dev_host.hpp): the mixed preparation and half tables once, the
+    # s-vector sums per group in one launch over every class's rows, the groups' MSMs over [g[:n_c] | h[:n_c] | the group's extra
+    # pairs] in at most one launch per block shape.  locate_packed*(classes, group=None | >= 1 | list) is two such calls
+    # (locate_plan_groups).
+    def default_groups(self, protocol, prepared):
+        """The group sizes locate_packed1 / locate_packed2 start with under group=None, one per class: the two rules of
+        BatchInnerProductVerifier.default_group with the class's own n_c = 2^k_c and count.  Where a group's MSM fits the one-launch
+        group kernel: the largest power of two with 2 n_c + group * per <= 8448 pairs (MID_NMAX), per = 2 k_c + 2 under Protocol 2 and
+        2 k_c + 4 under Protocol 1.  Where not even one proof fits (n_c >= 8192): the largest power of two <= sqrt(count).  prepared:
+        per class a tuple whose entry 0 is k_c and entry 3 the count (what _packed_classes returns).  As there, both are CAPACITY rules
+        -- what fits a launch, what balances the two levels -- and NOT measured optima: no other group size was timed against them for
+        a list of classes."""
+        out = []
+        for p in prepared:
+            k, count = p[0], p[3]
+            per = 2 * k + (4 if protocol == 1 else 2)
+            fit = (GROUP_MAX_PAIRS - 2 * (1 << k)) // per
+            if fit >= 1:
+                out.append(1 << (fit.bit_length() - 1))
+            else:
+                root = math.isqrt(count) if count and count > 0 else 1
+                out.append(1 << (max(root, 1).bit_length() - 1))
+        return out
 
-    def locate_packed1(self, classes):
+    @staticmethod
+    def _class_groups(group, n_classes):
+        """`group` as one integer >= 1 per class: an integer for every class, or a list with one per class."""
+        groups = [int(g) for g in group] if isinstance(group, (list, tuple)) else [int(group)] * n_classes
+        if len(groups) != n_classes or any(g < 1 for g in groups):
+            raise ValueError("group: an integer >= 1, or a list with one integer >= 1 per class")
+        return groups
+
+    def _group_values_mixed(self, protocol, prepared, sel, groups, wb):
+        """(values, value_off, status) over the proofs sel of the classes `prepared` -- sel: None for every proof, else per class the
+        sorted list of its local indices (an empty list: the class takes no part) -- in groups of groups[c] consecutive proofs of
+        sel[c].  values and status are class-major over the selected proofs; class c owns values[value_off[c]: value_off[c + 1]].  A
+        batch beyond one call's caps runs as consecutive calls cut at group boundaries (split_mixed_group_calls), each under its own
+        slice of the explicit weights wb or a fresh seed."""
+        counts = [p[3] if sel is None else len(sel[c]) for c, p in enumerate(prepared)]
+        pairs = [2 * p[0] + (4 if protocol == 1 else 2) for p in prepared]
+        per_w = 32 * (3 if protocol == 1 else 1)
+        values, status, at = [], b"", 0
+        for call in split_mixed_group_calls(counts, pairs, [1 << p[0] for p in prepared], groups):
+            cls, grp = [], []
+            for c, lo, hi in call:
+                k, rows, sizes, _ = prepared[c]
+                if sel is None:
+                    cut = lambda name: rows[name][sizes[name] * lo: sizes[name] * hi]
+                    loc = range(lo, hi)
+                else:
+                    loc = sel[c][lo:hi]
+                    cut = lambda name: b"".join(rows[name][sizes[name] * i: sizes[name] * (i + 1)] for i in loc)
+                trs = [rows["trs"][i] for i in loc]
+                starts = None if rows["starts"] is None else [rows["starts"][i] for i in loc]
+                u = rows["u"] if protocol == 1 else cut("u")
+                cls.append((k, hi - lo, cut("ab"), cut("xs"), cut("lr"), trs, starts, u, cut("P"), cut("c"), cut("head")))
+                grp.append(groups[c])
+            count = sum(hi - lo for _, lo, hi in call)
+            weights = None if wb is None else wb[per_w * at: per_w * (at + count)]
+            seed = None if weights is not None else secrets.token_bytes(32)
+            v, _, st = self.engine.ipa_group_values_packed_mixed_dev(self._d[0], self._d[1], self.n, protocol, cls, grp, weights, seed, self._d_scale)
+            values += v
+            status += st
+            at += count
+        value_off = [0]
+        for count, g in zip(counts, groups):
+            value_off.append(value_off[-1] + ((count + min(g, count) - 1) // min(g, count) if count else 0))
+        if len(values) != value_off[-1] or len(status) != sum(counts):
+            raise RuntimeError("the native calls returned %d values and %d status bytes for %d groups of %d proofs" % (len(values), len(status), value_off[-1], sum(counts)))
+        return values, value_off, status
+
+    def _group_values_packed_mixed(self, protocol, classes, group, weights):
+        prepared = self._packed_classes(protocol, classes)
+        total = sum(p[3] for p in prepared)
+        wb = BatchInnerProductVerifier._weights_bytes(self, protocol, weights, total)
+        return self._group_values_mixed(protocol, prepared, None, self._class_groups(group, len(prepared)), wb)
+
+    def group_values_packed2(self, classes, group=1, weights=None):
+        """(values, value_off, status) of a list of packed Protocol-2 classes (the argument of verify_packed2) per GROUP of consecutive
+        proofs of one class.  group: an integer for every class, or a list with one integer per class; class c is cut into groups of
+        min(group_c, count_c) proofs, the last one possibly short, and owns values[value_off[c]: value_off[c + 1]] -- a group never
+        straddles a class, an empty class has none.  values[t] = the 64-byte value of the weighted combination over the unflagged proofs
+        of group t over the prefix of its class's length -- 64 zero bytes when all of them verify --, status[i] (global, class-major
+        index) = bit 0: proof i fails a byte-level check, bit 1: it has an invalid point (a flagged proof takes part in no group).
+        Never a verdict: the values and the status are the result.  A batch beyond one native call's caps (2^16 proofs, 2^22 extra
+        pairs, 64 classes, sum of groups x 2 n_c <= 2^26) is cut into consecutive calls at group boundaries."""
+        return self._group_values_packed_mixed(2, classes, group, weights)
+
+    def group_values_packed1(self, classes, group=1, weights=None):
+        """group_values_packed2 for Protocol-1 classes (the argument of verify_packed1; weights: three per proof)."""
+        return self._group_values_packed_mixed(1, classes, group, weights)
+
+    def _locate_packed_mixed_groups(self, protocol, classes, group):
+        prepared = self._packed_classes(protocol, classes)
+        groups = self.default_groups(protocol, prepared) if group is None else self._class_groups(group, len(prepared))
+        return locate_plan_groups([p[3] for p in prepared], groups, lambda sel, grp: self._group_values_mixed(protocol, prepared, sel, grp, None))
+
+    def locate_packed2(self, classes, group=0):
+        """The sorted GLOBAL (class-major) indices of the invalid proofs of a list of packed Protocol-2 classes.
+        group = 0 (the default): those the status bytes flag, and the rest found by locate_by_bisection, every probe one mixed native
+        call over the gathered rows of the subset.  group = None, an integer >= 1 or a list with one integer per class: the two levels
+        of locate_plan_groups over group_values_packed2 -- level 1 is one call with those group sizes (None: default_groups), level 2
+        one call with group 1 over the unflagged proofs of the groups whose value is not the identity; a valid batch costs one native
+        call, a rejected one two.  The indices are the same in every case.
+        Which to call (measured: profiles/r19_ipa_locate_packed_mixed.txt): group=None.  At 4 096 x 64 + 1 024 x 256 +
+        256 x 1 024 + 16 x 2^16 it names one wrong statement in 10.8 ms against 37.0 for group=0 and 14.6 for one single-class
+        locate_packed2 per length, sixteen in 40.3 against 267 and 44.7, and it was ahead in every case measured (1.03-6.9x and 1.10-3.0x,
+        sixteen proofs of four lengths included).  group=0 stays the default because existing callers run these methods on engines
+        that have only the verify call, not because it measured faster.  A batch that is probably valid: verify_packed2 first (2.80 ms
+        against the plan's 6.28 over a valid batch) and locate on rejection."""
+        if group is not None and not isinstance(group, (list, tuple)) and int(group) == 0:
+            return self._locate_packed_mixed(2, classes)
+        return self._locate_packed_mixed_groups(2, classes, group)
+
+    def locate_packed1(self, classes, group=0):
         """locate_packed2 for Protocol-1 classes."""
-        return self._locate_packed_mixed(1, classes)
+        if group is not None and not isinstance(group, (list, tuple)) and int(group) == 0:
+            return self._locate_packed_mixed(1, classes)
+        return self._locate_packed_mixed_groups(1, classes, group)
 
 
 PAIRS_MAX = 1 << 22            # extra pairs per native call (IPAB_EXTRA_MAX)
@@ -251,6 +364,80 @@ def split_mixed_ranges(counts, pairs, proofs_max=CALL_MAX, pairs_max=PAIRS_MAX, 
     if cur:
         calls.append(cur)
     return calls
+
+
+def split_mixed_group_calls(counts, pairs, ns, groups, proofs_max=CALL_MAX, pairs_max=PAIRS_MAX, classes_max=CLASSES_MAX, rows_max=GROUP_ROWS_MAX):
+    """split_mixed_ranges for the group call: classes of counts[c] proofs with pairs[c] extra pairs each and n = ns[c] elements, cut into
+    groups of min(groups[c], counts[c]) consecutive proofs.  Per native call the list of (class, lo, hi) row ranges, class-major, each
+    call as long as the caps allow -- proofs_max proofs, pairs_max extra pairs, classes_max classes, rows_max group scalars (the sum of
+    groups x 2 n) -- and every cut inside a class at a multiple of its group size, so that no group straddles two calls.  A single
+    group beyond a call's caps cannot be computed and is refused."""
+    calls, cur, n, pr, rows = [], [], 0, 0, 0
+    for c, (count, pp, nc, group) in enumerate(zip(counts, pairs, ns, groups)):
+        g = min(group, count)
+        if count and (g < 1 or g > proofs_max or g * pp > pairs_max or 2 * nc > rows_max):
+            raise ValueError("class %d: a group of %d proofs does not fit one native call" % (c, g))
+        lo = 0
+        while lo < count:
+            fit = min((proofs_max - n) // g, (pairs_max - pr) // (g * pp), (rows_max - rows) // (2 * nc))       # whole groups
+            if cur and (len(cur) == classes_max or fit < 1):
+                calls.append(cur)
+                cur, n, pr, rows = [], 0, 0, 0
+                continue
+            take = min(count - lo, fit * g)
+            cur.append((c, lo, lo + take))
+            n, pr, rows, lo = n + take, pr + take * pp, rows + (take + g - 1) // g * 2 * nc, lo + take
+    if cur:
+        calls.append(cur)
+    return calls
+
+
+_ZERO64 = bytes(64)
+
+
+def locate_plan_groups(counts, groups, group_values):
+    """The two levels of locate_packed* over a list of classes, free of any GPU -- the counterpart of rangeproofs.batch.locate_plan for
+    per-class group sizes.  counts[c]: the proofs of class c; groups[c] >= 1: its group size.  group_values(sel, groups) ->
+    (values, value_off, status) is group_values_packed* over the sub-batch sel: None = every proof, else per class the sorted list of
+    its local indices (possibly empty); values and status class-major over sel, class c's groups at values[value_off[c]: value_off[c + 1]].
+    Level 1 is group_values(None, groups) over everything; level 2 -- only when some group's value is not the identity -- is ONE call
+    group_values(sub, [1, ...]) over the unflagged proofs of those groups, class by class (a flagged proof is already located and
+    takes part in no value; a class whose level-1 groups were single proofs is already located too and takes no part).  Returns the
+    sorted GLOBAL (class-major) indices of the proofs flagged at level 1 or with a non-identity value at level 2."""
+    n_classes = len(counts)
+    if len(groups) != n_classes or any(g < 1 for g in groups):
+        raise ValueError("one group size >= 1 per class")
+    total = sum(counts)
+    if total <= 0:
+        return []
+    gbase = [0]
+    for count in counts:
+        gbase.append(gbase[-1] + count)
+    eff = [min(g, count) if count else 1 for g, count in zip(groups, counts)]
+    want = [0]
+    for g, count in zip(eff, counts):
+        want.append(want[-1] + (count + g - 1) // g)
+    values, value_off, status = group_values(None, list(groups))
+    if len(status) != total or len(values) != want[-1] or list(value_off) != want:
+        raise ValueError("group_values returned %d values (offsets %r) and %d status bytes for %d proofs in %d groups" % (len(values), list(value_off), len(status), total, want[-1]))
+    bad = [i for i in range(total) if status[i]]
+    sub = [[] for _ in counts]
+    for c, (g, count) in enumerate(zip(eff, counts)):
+        for t in range(want[c + 1] - want[c]):
+            if values[want[c] + t] != _ZERO64:
+                hit = [i for i in range(t * g, min((t + 1) * g, count)) if not status[gbase[c] + i]]
+                if g == 1:                         # level 1 was already one proof per group
+                    bad += [gbase[c] + i for i in hit]
+                else:
+                    sub[c] += hit
+    if any(sub):
+        values2, value_off2, status2 = group_values(sub, [1] * n_classes)
+        n_sub = sum(len(s) for s in sub)
+        if len(values2) != n_sub or len(status2) != n_sub:
+            raise ValueError("group_values returned %d values for a sub-batch of %d proofs" % (len(values2), n_sub))
+        flat = [gbase[c] + i for c, s in enumerate(sub) for i in s]
+        bad += [i for i, v, st in zip(flat, values2, status2) if v != _ZERO64 or st]
+    return sorted(bad)
 
 
 def batch_verify_inner_products_mixed(g, h, statements, h_scale=None, engine=None, rng=None):
