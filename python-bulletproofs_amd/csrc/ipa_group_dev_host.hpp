@@ -2,9 +2,10 @@
 // Which groups of a batch of PACKED inner-product proofs hold an invalid one: bpmi_ipa_group_values_packed_dev.  The preparation of
 // bpmi_ipa_verify_batch_packed_dev (ipap_run: upload, re-hash, inversion, weights -- once per batch) and its half tables
 // (ipab_tables_launch, ipa_batch_host.hpp), but the s-vectors are summed per GROUP of `group` consecutive proofs
-// (k_sc_svector_sum_groups) and the groups' MSMs over [g | h | the group's extra pairs] (ipa_segs, ipa_verify_msm_host.hpp) run as ONE
-// launch over (group, window) (k_msm_ipa_group) with a device tail (k_group_tail) -- the counterpart of
-// bpmi_rp_batch_group_values_dev.  Plan, argument errors and routes: ipa_group_plan_host.hpp.
+// (k_sc_svector_sum_groups) and the groups' MSMs over [g | h | the group's extra pairs] run as ONE launch over (group, window)
+// (k_msm_ipa_group) with a device tail (k_group_tail) -- the counterpart of bpmi_rp_batch_group_values_dev.  This file holds the
+// call's preparation, its sum launch and its order of copies and waits; the launch lines, the msm_run of one group and the ending
+// are the group calls' shared pieces (ipa_verify_msm_host.hpp).  Plan, argument errors and routes: ipa_group_plan_host.hpp.
 #pragma once
 
 extern "C" {
@@ -49,35 +50,28 @@ int bpmi_ipa_group_values_packed_dev(bpmi_ctx *ctx, const void *d_g, const void 
   if (ctx->opt_validate >= 2) { pc.queue(d_g, n, "d_g"); pc.queue(d_h, n, "d_h"); }
   rc = pc.fetch();
   if (rc) return rc;
+  const u32 *x_pts = (const u32 *)(base + bp.o_expt), *x_sc = (const u32 *)(base + bp.o_exsc);
   if (gp.route != IPAG_ROUTE_MSM_RUN) {
     IpaGroupMsm J;
-    J.g = (const u32 *)d_g; J.h = (const u32 *)d_h; J.sa = gsa; J.sb = gsb;
-    J.x_pts = (const u32 *)(base + bp.o_expt); J.x_sc = (const u32 *)(base + bp.o_exsc);
+    J.g = (const u32 *)d_g; J.h = (const u32 *)d_h; J.sa = gsa; J.sb = gsb; J.x_pts = x_pts; J.x_sc = x_sc;
     J.n = nn; J.per = gp.per; J.group = gp.group; J.P = Pn; J.W = gp.W; J.E = (u32 *)(base + gp.o_E);
     u32 *d_vals = (u32 *)(base + gp.o_vals);
     {
       StageTimer t(ctx, ST_ACCUM);
-      if (gp.route == IPAG_ROUTE_LIGHT)
-        hipLaunchKernelGGL((k_msm_ipa_group<GROUP_LIGHT_THREADS, GROUP_LIGHT_NMAX>), dim3(gp.ngroups * gp.W), dim3(GROUP_LIGHT_THREADS), 0, st, J);
-      else hipLaunchKernelGGL((k_msm_ipa_group<MID_THREADS, MID_NMAX>), dim3(gp.ngroups * gp.W), dim3(MID_THREADS), 0, st, J);
-      hipLaunchKernelGGL(k_group_tail, dim3((gp.ngroups + 63) / 64), dim3(64), 0, st, (const u32 *)J.E, gp.W, (u32)MID_C, gp.ngroups, d_vals);
+      group_msm_launch(ctx, gp.route == IPAG_ROUTE_LIGHT, k_msm_ipa_group<GROUP_LIGHT_THREADS, GROUP_LIGHT_NMAX>, k_msm_ipa_group<MID_THREADS, MID_NMAX>, gp.ngroups, gp.W, J);
+      group_tail_launch(ctx, J.E, gp.W, gp.ngroups, d_vals);
     }
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(values, d_vals, vals_bytes, hipMemcpyDeviceToHost, st));
   } else {
-    // groups beyond the one-launch kernel's capacity: one MSM each on the three segments (as rp_run_group_msms)
+    // no values copy and no wait in front of the loop on this route: msm_run writes `values` itself (as rp_run_group_msms)
     for (u32 t = 0; t < gp.ngroups; t++) {
       const uint64_t g0 = (uint64_t)t * gp.group, cnt = std::min<uint64_t>(gp.group, n_proofs - g0);
-      const Segs s = ipa_segs(d_g, d_h, n, gsa + 8 * (size_t)n * t, gsb + 8 * (size_t)n * t, (const u32 *)(base + bp.o_expt) + 16 * gp.per * g0,
-                              (const u32 *)(base + bp.o_exsc) + 8 * gp.per * g0, cnt * gp.per);
-      rc = msm_run(ctx, s, values + 64 * (size_t)t);
+      rc = ipag_msm_run_group(ctx, d_g, d_h, gsa, gsb, x_pts, x_sc, n, n * t, gp.per * g0, cnt * gp.per, values + 64 * (size_t)t);
       if (rc) { memset(values, 0xFF, vals_bytes); return rc; }
     }
   }
-  HIPCHK(ctx, hipStreamSynchronize(st));
-  rc = pc.verdict();
-  if (rc) memset(values, 0xFF, vals_bytes);
-  return rc;
+  return ipag_finish(ctx, pc, st, values, vals_bytes);
 }
 
 }  // extern "C"

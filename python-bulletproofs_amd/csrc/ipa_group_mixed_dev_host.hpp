@@ -5,7 +5,8 @@
 // the s-vectors are summed per GROUP of consecutive proofs of one class (k_sc_svector_sum_groups_mixed, one launch over every class's
 // rows) and the groups' MSMs over [g[:n_c] | h[:n_c] | the group's extra pairs] run as at most one launch per block shape over
 // (group, window) (k_msm_ipa_group_mixed) with ONE device tail (k_group_tail); the groups of a class beyond the kernel's capacity go
-// through msm_run one by one.  The counterpart of bpmi_ipa_group_values_packed_dev (ipa_group_dev_host.hpp) for a list of classes.
+// through msm_run one by one.  The counterpart of bpmi_ipa_group_values_packed_dev (ipa_group_dev_host.hpp) for a list of classes:
+// its own preparation, sum launch and order of copies and waits here, the shared pieces in ipa_verify_msm_host.hpp.
 // Plan, argument errors and routes: ipa_group_mixed_plan_host.hpp.
 #pragma once
 
@@ -61,41 +62,34 @@ int bpmi_ipa_group_values_packed_mixed_dev(bpmi_ctx *ctx, const void *d_g, const
   rc = pc.fetch();
   if (rc) return rc;
   u32 *d_E = (u32 *)(base + gp.o_E), *d_vals = (u32 *)(base + gp.o_vals);
+  const u32 *x_pts = (const u32 *)(base + bp.o_expt), *x_sc = (const u32 *)(base + bp.o_exsc);
   {
     IpaGroupMixedMsm J;
-    J.g = (const u32 *)d_g; J.h = (const u32 *)d_h; J.sa = gsa; J.sb = gsb;
-    J.x_pts = (const u32 *)(base + bp.o_expt); J.x_sc = (const u32 *)(base + bp.o_exsc);
+    J.g = (const u32 *)d_g; J.h = (const u32 *)d_h; J.sa = gsa; J.sb = gsb; J.x_pts = x_pts; J.x_sc = x_sc;
     J.gtab = (const u32 *)(base + gp.o_gtab); J.W = gp.W; J.E = d_E;
     StageTimer t(ctx, ST_ACCUM);
     // the groups that msm_run takes leave no window sums: theirs are the identity for the tail, and msm_run writes their values below
     if (!gp.run.empty()) HIPCHK(ctx, hipMemsetAsync(d_E, 0, gp.b_E, st));
-    if (!gp.light.empty()) {
-      J.list = (const u32 *)(base + gp.o_light);
-      hipLaunchKernelGGL((k_msm_ipa_group_mixed<GROUP_LIGHT_THREADS, GROUP_LIGHT_NMAX>), dim3((u32)gp.light.size() * gp.W), dim3(GROUP_LIGHT_THREADS), 0, st, J);
+    for (const bool is_light : {true, false}) {                  // at most one launch per block shape, over that shape's list
+      const std::vector<u32> &list = is_light ? gp.light : gp.mid;
+      if (list.empty()) continue;
+      J.list = (const u32 *)(base + (is_light ? gp.o_light : gp.o_mid));
+      group_msm_launch(ctx, is_light, k_msm_ipa_group_mixed<GROUP_LIGHT_THREADS, GROUP_LIGHT_NMAX>, k_msm_ipa_group_mixed<MID_THREADS, MID_NMAX>, (u32)list.size(), gp.W, J);
     }
-    if (!gp.mid.empty()) {
-      J.list = (const u32 *)(base + gp.o_mid);
-      hipLaunchKernelGGL((k_msm_ipa_group_mixed<MID_THREADS, MID_NMAX>), dim3((u32)gp.mid.size() * gp.W), dim3(MID_THREADS), 0, st, J);
-    }
-    hipLaunchKernelGGL(k_group_tail, dim3((gp.ngroups + 63) / 64), dim3(64), 0, st, (const u32 *)d_E, gp.W, (u32)MID_C, gp.ngroups, d_vals);
+    group_tail_launch(ctx, d_E, gp.W, gp.ngroups, d_vals);
   }
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipMemcpyAsync(values, d_vals, vals_bytes, hipMemcpyDeviceToHost, st));
   if (!gp.run.empty()) {
-    // groups beyond the one-launch kernel's capacity: one MSM each over the class's prefix (as ipa_group_dev_host.hpp), behind the copy
+    // groups beyond the one-launch kernel's capacity, behind the copy and a wait of this call's own (the uniform call has neither)
     HIPCHK(ctx, hipStreamSynchronize(st));
     for (const u32 t : gp.run) {
-      const u32 *d = gp.group_tab.data() + (size_t)IPAGM_GROUP_WORDS * t;
-      const Segs s = ipa_segs(d_g, d_h, d[0], gsa + 8 * (size_t)d[1], gsb + 8 * (size_t)d[1], (const u32 *)(base + bp.o_expt) + 16 * (size_t)d[2],
-                              (const u32 *)(base + bp.o_exsc) + 8 * (size_t)d[2], d[3]);
-      rc = msm_run(ctx, s, values + 64 * (size_t)t);
+      const u32 *d = gp.group_tab.data() + (size_t)IPAGM_GROUP_WORDS * t;          // n_c, row offset, first extra pair, extra pairs
+      rc = ipag_msm_run_group(ctx, d_g, d_h, gsa, gsb, x_pts, x_sc, d[0], d[1], d[2], d[3], values + 64 * (size_t)t);
       if (rc) { memset(values, 0xFF, vals_bytes); return rc; }
     }
   }
-  HIPCHK(ctx, hipStreamSynchronize(st));
-  rc = pc.verdict();
-  if (rc) memset(values, 0xFF, vals_bytes);
-  return rc;
+  return ipag_finish(ctx, pc, st, values, vals_bytes);
 }
 
 }  // extern "C"

@@ -3,14 +3,14 @@
 // weighted combination is taken per GROUP of consecutive proofs of ONE class, so that one call says which groups hold an invalid
 // proof.  It is the unchanged ipa_packed_mixed_plan (the uploads, the preparation's rounds, the mixed half tables; its plain SA / SB,
 // units and partial sums are laid out and not used) followed by the groups' regions, and per class what ipa_group_plan decides for a
-// batch of one length.  tests/test_ipa_group_mixed_plan_cpu.py checks it without a GPU; ipa_group_mixed_dev_host.hpp consumes it.
+// batch of one length: both plans call ipag_shape, ipag_rows_fit and ipag_place of ipa_group_plan_host.hpp, which hold those rules
+// once.  tests/test_ipa_group_mixed_plan_cpu.py checks it without a GPU; ipa_group_mixed_dev_host.hpp consumes it.
 // Kernels: k_sc_svector_sum_groups_mixed (ipa_mixed_kernels.hpp), k_msm_ipa_group_mixed (msm_kernels.hpp).
 //
 // Groups.  Class c (n_c = 2^k_c elements, P_c proofs) is cut into groups of group_c = min(group[c], P_c) consecutive proofs, the last
 // one possibly short; a group never straddles a class and an empty class has none.  Groups are numbered class-major, in the caller's
-// order: class c owns the groups [first_group, first_group + ngroups).  The MSM of a full group has pairs = 2 n_c + group_c per_c
-// (per_c = 2 k_c + 2 extra pairs of a proof under Protocol 2, 2 k_c + 4 under Protocol 1) and takes the route of ipa_group_plan by
-// that number, class by class: LIGHT (<= GROUP_LIGHT_NMAX), MID (<= MID_NMAX), else msm_run group by group.
+// order: class c owns the groups [first_group, first_group + ngroups).  Clamp, group count, pairs of a full group's MSM and its
+// route are ipag_shape's, class by class.
 //
 // Proofs and tables.  ipa_mixed_plan sorts the class-major list of proofs by descending k, STABLE: a class's proofs have one k, so
 // they stay contiguous and in their own order (two classes of one k follow each other in the caller's order).  Its descriptors give
@@ -58,19 +58,19 @@ struct IpagmClass {
   uint64_t extra_off = 0;                      // its first extra pair
 };
 
-struct IpagmPlan {
+struct IpagmPlan : IpagRegions {               // (rows SA / rows SB / E / values and W: ipag_place)
   int err = 0; std::string msg;                // an argument error: nothing else is set
   bool empty = false;                          // every class is empty: value_off is all zero, nothing to do
   IpapmPlan packed;                            // the unchanged plan of the mixed packed verifier
   std::vector<IpagmClass> cls;                 // n_classes, caller's order
   std::vector<uint64_t> value_off;             // n_classes + 1: class c owns the values [value_off[c], value_off[c + 1])
-  u32 ngroups = 0, W = 0;
+  u32 ngroups = 0;
   u32 n_blocks = 0;                            // of the sum kernel
   uint64_t rows_total = 0;
   std::vector<u32> class_tab, group_tab, light, mid;
   std::vector<u32> run;                        // the groups on the msm_run route
-  uint64_t o_gsa = 0, o_gsb = 0, o_E = 0, o_vals = 0, o_ctab = 0, o_gtab = 0, o_light = 0, o_mid = 0;
-  uint64_t b_gsa = 0, b_gsb = 0, b_E = 0, b_vals = 0, b_ctab = 0, b_gtab = 0, b_light = 0, b_mid = 0;
+  uint64_t o_ctab = 0, o_gtab = 0, o_light = 0, o_mid = 0;
+  uint64_t b_ctab = 0, b_gtab = 0, b_light = 0, b_mid = 0;
   uint64_t total_bytes = 0;
 };
 
@@ -94,11 +94,9 @@ static inline IpagmPlan ipa_group_mixed_plan(const BpmiOptions &opt, u32 K, int 
   for (u32 c : mp.fin_cls) {
     if (group[c] < 1) return ipagm_plan_error("class " + std::to_string(c) + ": group must be at least 1");
     const IpapmClass &m = mp.cls[c];
-    const uint64_t g = group[c] < m.n_proofs ? group[c] : m.n_proofs;
-    row_scalars += (m.n_proofs + g - 1) / g * (1ull << m.k);
+    row_scalars += (uint64_t)ipag_shape(m.n_proofs, group[c], m.k, m.pairs).ngroups << m.k;
   }
-  if (2 * row_scalars > IPAG_ROWS_MAX) return ipagm_plan_error("too many groups: the sum over the classes of n_groups x 2 n must not exceed 2^26");
-  p.W = 255u / MID_C + 1u;
+  if (!ipag_rows_fit(row_scalars)) return ipagm_plan_error("too many groups: the sum over the classes of n_groups x 2 n must not exceed 2^26");
   u32 first_group = 0, block = 0;
   for (u32 c = 0; c < n_classes; c++) {
     p.value_off[c] = first_group;
@@ -106,12 +104,10 @@ static inline IpagmPlan ipa_group_mixed_plan(const BpmiOptions &opt, u32 K, int 
     if (!m.n_proofs) continue;
     IpagmClass &q = p.cls[c];
     const u32 n = 1u << m.k;
+    const IpagShape s = ipag_shape(m.n_proofs, group[c], m.k, m.pairs);
     q.k = m.k; q.kl = m.k / 2; q.per = m.pairs; q.count = (u32)m.n_proofs;
-    q.group = (u32)(group[c] < m.n_proofs ? group[c] : m.n_proofs);
-    q.ngroups = (q.count + q.group - 1) / q.group;
+    q.group = s.group; q.ngroups = s.ngroups; q.pairs = s.pairs; q.route = s.route;
     q.first_group = first_group;
-    q.pairs = 2ull * n + (uint64_t)q.group * q.per;
-    q.route = q.pairs <= GROUP_LIGHT_NMAX ? IPAG_ROUTE_LIGHT : (q.pairs <= MID_NMAX ? IPAG_ROUTE_MID : IPAG_ROUTE_MSM_RUN);
     q.tab_base = mp.base.desc[m.first_sorted].tab_off;
     q.tab_stride = (1u << q.kl) + (1u << (q.k - q.kl));
     q.block_start = block; q.row_off = block * IPAGM_BLOCK;
@@ -132,15 +128,11 @@ static inline IpagmPlan ipa_group_mixed_plan(const BpmiOptions &opt, u32 K, int 
   }
   p.value_off[n_classes] = first_group;
   p.ngroups = first_group; p.n_blocks = block;
-  p.b_gsa = p.b_gsb = 32 * p.rows_total;
-  p.b_E = 4ull * XYZZ_WORDS * p.W * p.ngroups;
-  p.b_vals = 64ull * p.ngroups;
   p.b_ctab = 4ull * p.class_tab.size(); p.b_gtab = 4ull * p.group_tab.size();
   p.b_light = 4ull * p.light.size(); p.b_mid = 4ull * p.mid.size();
   uint64_t at = mp.total_bytes;
-  auto take = [&at](uint64_t bytes) { const uint64_t o = at; at += align_up(bytes, 256); return o; };
-  p.o_gsa = take(p.b_gsa); p.o_gsb = take(p.b_gsb); p.o_E = take(p.b_E); p.o_vals = take(p.b_vals);
-  p.o_ctab = take(p.b_ctab); p.o_gtab = take(p.b_gtab); p.o_light = take(p.b_light); p.o_mid = take(p.b_mid);
+  ipag_place(p, at, p.rows_total, p.ngroups);
+  p.o_ctab = ipag_take(at, p.b_ctab); p.o_gtab = ipag_take(at, p.b_gtab); p.o_light = ipag_take(at, p.b_light); p.o_mid = ipag_take(at, p.b_mid);
   p.total_bytes = at;
   return p;
 }

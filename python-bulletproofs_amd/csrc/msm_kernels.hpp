@@ -1970,6 +1970,19 @@ __device__ __forceinline__ void msm_mid_block(const Segs &segs, const MsmGeom &g
   }
 }
 
+// The common end of the three group kernels: window w of group t's MSM over the three filled segments of s (pts, sc, n), plain
+// scalars and no GLV, by msm_mid_block; its window sum goes to E[t][w].
+template <u32 THREADS, u32 NMAX> __device__ __forceinline__ void group_msm_block(Segs &s, u32 t, u32 w, u32 W, u32 *E) {
+  s.total = s.n[0] + s.n[1] + s.n[2];
+  s.hlog[0] = s.hlog[1] = s.hlog[2] = 0xFFu;
+  s.phase[0] = s.phase[1] = s.phase[2] = 0;
+  s.glv_sub = nullptr; s.glv_neg = nullptr; s.glv_bx = nullptr;
+  MsmGeom g = {};                                  // (the body reads n and W only)
+  g.n = s.total; g.c = MID_C; g.W = W; g.B = MID_B;
+  u32 *const Et = E + (u64)t * W * XYZZ_WORDS;
+  msm_mid_block<THREADS, NMAX>(s, g, w, 1u, 0u, Et);
+}
+
 // (GROUP_LIGHT_THREADS, GROUP_LIGHT_NMAX: shared_defs.hpp)
 struct GroupMsm {
   const u32 *gens, *gsc;              // the 3 + 2n shared generators; their scalars, one row of `nshared` per group
@@ -1985,14 +1998,7 @@ template <u32 THREADS, u32 NMAX> __global__ void __launch_bounds__(THREADS) k_ms
   s.pts[0] = J.gens; s.sc[0] = J.gsc + 8ull * J.nshared * t; s.n[0] = J.nshared;
   s.pts[1] = J.v_pts + 16ull * J.m * g0; s.sc[1] = J.v_sc + 8ull * J.m * g0; s.n[1] = cnt * J.m;
   s.pts[2] = J.p_pts + 16ull * J.per * g0; s.sc[2] = J.p_sc + 8ull * J.per * g0; s.n[2] = cnt * J.per;
-  s.total = s.n[0] + s.n[1] + s.n[2];
-  s.hlog[0] = s.hlog[1] = s.hlog[2] = 0xFFu;
-  s.phase[0] = s.phase[1] = s.phase[2] = 0;
-  s.glv_sub = nullptr; s.glv_neg = nullptr; s.glv_bx = nullptr;
-  MsmGeom g = {};                                  // (the body reads n and W only)
-  g.n = s.total; g.c = MID_C; g.W = J.W; g.B = MID_B;
-  u32 *const Et = J.E + (u64)t * J.W * XYZZ_WORDS;
-  msm_mid_block<THREADS, NMAX>(s, g, w, 1u, 0u, Et);
+  group_msm_block<THREADS, NMAX>(s, t, w, J.W, J.E);
 }
 template __global__ void k_msm_group<MID_THREADS, MID_NMAX>(GroupMsm);
 template __global__ void k_msm_group<GROUP_LIGHT_THREADS, GROUP_LIGHT_NMAX>(GroupMsm);
@@ -2014,14 +2020,7 @@ template <u32 THREADS, u32 NMAX> __global__ void __launch_bounds__(THREADS) k_ms
   s.pts[0] = J.g; s.sc[0] = J.sa + 8ull * J.n * t; s.n[0] = J.n;
   s.pts[1] = J.h; s.sc[1] = J.sb + 8ull * J.n * t; s.n[1] = J.n;
   s.pts[2] = J.x_pts + 16ull * J.per * g0; s.sc[2] = J.x_sc + 8ull * J.per * g0; s.n[2] = cnt * J.per;
-  s.total = s.n[0] + s.n[1] + s.n[2];
-  s.hlog[0] = s.hlog[1] = s.hlog[2] = 0xFFu;
-  s.phase[0] = s.phase[1] = s.phase[2] = 0;
-  s.glv_sub = nullptr; s.glv_neg = nullptr; s.glv_bx = nullptr;
-  MsmGeom g = {};                                  // (the body reads n and W only)
-  g.n = s.total; g.c = MID_C; g.W = J.W; g.B = MID_B;
-  u32 *const Et = J.E + (u64)t * J.W * XYZZ_WORDS;
-  msm_mid_block<THREADS, NMAX>(s, g, w, 1u, 0u, Et);
+  group_msm_block<THREADS, NMAX>(s, t, w, J.W, J.E);
 }
 template __global__ void k_msm_ipa_group<MID_THREADS, MID_NMAX>(IpaGroupMsm);
 template __global__ void k_msm_ipa_group<GROUP_LIGHT_THREADS, GROUP_LIGHT_NMAX>(IpaGroupMsm);
@@ -2049,14 +2048,7 @@ template <u32 THREADS, u32 NMAX> __global__ void __launch_bounds__(THREADS) k_ms
   s.pts[0] = J.g; s.sc[0] = J.sa + 8ull * row; s.n[0] = n;
   s.pts[1] = J.h; s.sc[1] = J.sb + 8ull * row; s.n[1] = n;
   s.pts[2] = J.x_pts + 16ull * x0; s.sc[2] = J.x_sc + 8ull * x0; s.n[2] = xn;
-  s.total = s.n[0] + s.n[1] + s.n[2];
-  s.hlog[0] = s.hlog[1] = s.hlog[2] = 0xFFu;
-  s.phase[0] = s.phase[1] = s.phase[2] = 0;
-  s.glv_sub = nullptr; s.glv_neg = nullptr; s.glv_bx = nullptr;
-  MsmGeom g = {};                                  // (the body reads n and W only)
-  g.n = s.total; g.c = MID_C; g.W = J.W; g.B = MID_B;
-  u32 *const Et = J.E + (u64)t * J.W * XYZZ_WORDS;
-  msm_mid_block<THREADS, NMAX>(s, g, w, 1u, 0u, Et);
+  group_msm_block<THREADS, NMAX>(s, t, w, J.W, J.E);
 }
 template __global__ void k_msm_ipa_group_mixed<MID_THREADS, MID_NMAX>(IpaGroupMixedMsm);
 template __global__ void k_msm_ipa_group_mixed<GROUP_LIGHT_THREADS, GROUP_LIGHT_NMAX>(IpaGroupMixedMsm);

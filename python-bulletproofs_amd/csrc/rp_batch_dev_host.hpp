@@ -447,9 +447,8 @@ static int rp_queue_group_msms(bpmi_ctx *ctx, const RpGroups &G, const RpBatchDi
   J.nshared = d.nshared; J.m = m; J.per = d.per; J.group = G.group; J.P = (u32)n_proofs; J.W = W; J.E = G.d_E;
   {
     StageTimer t(ctx, ST_ACCUM);
-    if (G.route == RP_GROUPS_LIGHT) hipLaunchKernelGGL((k_msm_group<GROUP_LIGHT_THREADS, GROUP_LIGHT_NMAX>), dim3(G.ngroups * W), dim3(GROUP_LIGHT_THREADS), 0, ctx->stream, J);
-    else hipLaunchKernelGGL((k_msm_group<MID_THREADS, MID_NMAX>), dim3(G.ngroups * W), dim3(MID_THREADS), 0, ctx->stream, J);
-    hipLaunchKernelGGL(k_group_tail, dim3((G.ngroups + 63) / 64), dim3(64), 0, ctx->stream, (const u32 *)G.d_E, W, (u32)MID_C, G.ngroups, G.d_vals);
+    group_msm_launch(ctx, G.route == RP_GROUPS_LIGHT, k_msm_group<GROUP_LIGHT_THREADS, GROUP_LIGHT_NMAX>, k_msm_group<MID_THREADS, MID_NMAX>, G.ngroups, W, J);
+    group_tail_launch(ctx, G.d_E, W, G.ngroups, G.d_vals);                         // (both: ipa_verify_msm_host.hpp)
   }
   if (hipGetLastError() != hipSuccess) return fail(ctx, BPMI_E_HIP, "launch of the group MSMs failed");
   if (hipMemcpyAsync(ctx->pin, G.d_vals, vals_bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return fail(ctx, BPMI_E_HIP, "copy of the group values failed");

@@ -355,8 +355,7 @@ class Engine:
         """(values, status) of bpmi_ipa_group_values_packed_dev: values[t] = the 64-byte value of the weighted combination over the
         unflagged proofs of [t group, (t + 1) group) (identity = all of them verify) -- what ipa_verify_batch_packed_dev returns for that
         sub-batch under the same weights -- and one status byte per proof.  One preparation and one launch of the groups' MSMs."""
-        per = max(1, min(int(group), count))             # (group = 0 is the native call's argument error)
-        ngroups = (count + per - 1) // per
+        ngroups = group_count(count, group)
         values, status = ctypes.create_string_buffer(max(64 * ngroups, 1)), ctypes.create_string_buffer(max(count, 1))
         self._ck(self.lib.bpmi_ipa_group_values_packed_dev(self.ctx, _ptr(d_g), _ptr(d_h), None if d_hscale is None else _ptr(d_hscale), n, protocol, count,
                                                            *packed_proof_args(count, ab, xs, lr, transcripts, starts, u, P, c, head), weights, seed, group,
@@ -400,7 +399,7 @@ class Engine:
         if len(groups) != len(classes):
             raise ValueError("one group size per class")
         arr, keep, total, _, _ = packed_class_array(protocol, classes)
-        ngroups = sum((cl[1] + min(max(int(g), 1), cl[1]) - 1) // min(max(int(g), 1), cl[1]) for cl, g in zip(classes, groups) if cl[1])
+        ngroups = sum(group_count(cl[1], g) for cl, g in zip(classes, groups))
         grp = (ctypes.c_uint64 * max(len(classes), 1))(*[int(g) for g in groups])
         offs = (ctypes.c_uint64 * (len(classes) + 1))()
         values, status = ctypes.create_string_buffer(max(64 * ngroups, 1)), ctypes.create_string_buffer(max(total, 1))
@@ -571,6 +570,13 @@ def _pack_messages(msgs, offsets):
 
 def sc_bytes(k):
     return (int(k) % Q).to_bytes(32, "little")
+
+
+def group_count(count, group):
+    """The groups of min(group, count) consecutive proofs that `count` proofs make, the last one possibly short (none for no proof):
+    the clamp of the native group calls.  (group < 1 counts as 1 here; it is the native call's argument error.)"""
+    g = min(max(int(group), 1), count)
+    return (count + g - 1) // g if count else 0
 
 
 def packed_proof_args(count, ab, xs, lr, transcripts, starts, u, P, c=None, head=None):

@@ -17,6 +17,7 @@ import secrets
 
 from .. import engine as _engine
 from ..ec import PackedPoints, pack_points, pack_scalars, secp256k1
+from ..locate import locate_by_bisection, locate_plan        # noqa: F401  (locate_by_bisection: also this module's old export)
 from ..utils.utils import mod_hash
 from .inner_product_verifier import Verifier2
 
@@ -26,31 +27,37 @@ GROUP_MAX_PAIRS = 8448         # MID_NMAX (csrc/shared_defs.hpp): the pairs of o
 GROUP_ROWS_MAX = 1 << 26       # group scalars per native call: groups x 2 n (IPAG_ROWS_MAX, csrc/ipa_group_plan_host.hpp)
 
 
-def locate_by_bisection(count, subset_is_valid):
-    """The sorted indices in range(count) of the invalid items, found with subset probes: subset_is_valid(indices) is True iff
-    every item of the (sorted, non-empty) index list is valid.  One probe over everything; then every subset known to hold an
-    invalid item is halved: the left half is probed, and the right half only when the left one was invalid (a valid left half
-    proves the right one invalid).  At most 1 + 2 bad ceil(log2 count) probes."""
-    if count <= 0:
-        return []
-    everything = list(range(count))
-    if subset_is_valid(everything):
-        return []
-    bad, todo = [], [everything]          # todo: subsets known to hold an invalid item
-    while todo:
-        sub = todo.pop()
-        if len(sub) == 1:
-            bad.append(sub[0])
-            continue
-        mid = (len(sub) + 1) // 2
-        left, right = sub[:mid], sub[mid:]
-        if subset_is_valid(left):
-            todo.append(right)
-        else:
-            todo.append(left)
-            if not subset_is_valid(right):
-                todo.append(right)
-    return sorted(bad)
+def extra_pairs(protocol, k):
+    """The extra pairs a packed proof of 2^k elements brings to the MSM (ipap_pairs, csrc/ipa_packed_plan_host.hpp)."""
+    return 2 * k + (4 if protocol == 1 else 2)
+
+
+def weight_bytes(protocol):
+    """The bytes of a proof's explicit weights: one scalar under Protocol 2, three (w, r1, r2) under Protocol 1."""
+    return 32 * (3 if protocol == 1 else 1)
+
+
+def default_group_for(protocol, k, count=None):
+    """The two rules of default_group / default_groups for `count` packed proofs of 2^k elements."""
+    fit = (GROUP_MAX_PAIRS - 2 * (1 << k)) // extra_pairs(protocol, k)
+    if fit >= 1:
+        return 1 << (fit.bit_length() - 1)
+    root = math.isqrt(count) if count and count > 0 else 1
+    return 1 << (max(root, 1).bit_length() - 1)
+
+
+def packed_rows_cut(protocol, rows, sizes, idx):
+    """(ab, xs, lr, trs, starts, u, P, c, head) of the rows idx of one packed class (rows, sizes: what _packed_rows returns) -- the
+    per-class arguments of the packed native calls, in their order.  idx: a range of step 1 (sliced) or a sorted list (gathered): the
+    same bytes either way.  starts stays None where the class has none; under Protocol 1 u is the class's ONE shared point."""
+    if isinstance(idx, range) and idx.step == 1:
+        cut = lambda name: rows[name][sizes[name] * idx.start: sizes[name] * idx.stop]
+        pick = lambda lst: lst[idx.start: idx.stop]
+    else:
+        cut = lambda name: b"".join(rows[name][sizes[name] * i: sizes[name] * (i + 1)] for i in idx)
+        pick = lambda lst: [lst[i] for i in idx]
+    return (cut("ab"), cut("xs"), cut("lr"), pick(rows["trs"]), None if rows["starts"] is None else pick(rows["starts"]),
+            rows["u"] if protocol == 1 else cut("u"), cut("P"), cut("c"), cut("head"))
 
 
 class _Item:
@@ -219,26 +226,20 @@ class BatchInnerProductVerifier:
 
     def _packed_call(self, protocol, rows, sizes, idx, weights):
         """(out, status) of one native call over the rows idx (a range or a sorted list; at most 2^16)."""
-        if isinstance(idx, range) and idx.step == 1:
-            cut = lambda name: rows[name][sizes[name] * idx.start: sizes[name] * idx.stop]
-        else:
-            cut = lambda name: b"".join(rows[name][sizes[name] * i: sizes[name] * (i + 1)] for i in idx)
-        u = rows["u"] if protocol == 1 else cut("u")
-        starts = None if rows["starts"] is None else [rows["starts"][i] for i in idx]
         seed = None if weights is not None else secrets.token_bytes(32)
-        return self.engine.ipa_verify_batch_packed_dev(self._d[0], self._d[1], self.n, protocol, len(idx), cut("ab"), cut("xs"), cut("lr"),
-                                                       [rows["trs"][i] for i in idx], starts, u, cut("P"), cut("c"), cut("head"), weights, seed, self._d_scale)
+        return self.engine.ipa_verify_batch_packed_dev(self._d[0], self._d[1], self.n, protocol, len(idx), *packed_rows_cut(protocol, rows, sizes, idx),
+                                                       weights, seed, self._d_scale)
 
     def _weights_bytes(self, protocol, weights, count):
         if weights is None:
             return None
         flat = [int(w) % Q for row in weights for w in (row if isinstance(row, (tuple, list)) else (row,))]
-        if len(flat) != (3 if protocol == 1 else 1) * count:
+        if len(flat) != weight_bytes(protocol) // 32 * count:
             raise ValueError("one weight per proof under Protocol 2, three (w, r1, r2) under Protocol 1")
         return pack_scalars(flat, Q)
 
     def _verify_packed(self, protocol, rows, sizes, count, weights):
-        per = 32 * (3 if protocol == 1 else 1)
+        per = weight_bytes(protocol)
         wb = self._weights_bytes(protocol, weights, count)
         for lo in range(0, count, CALL_MAX):               # consecutive calls of at most 2^16 proofs; valid iff every call is
             hi = min(lo + CALL_MAX, count)
@@ -249,7 +250,6 @@ class BatchInnerProductVerifier:
 
     def _locate_packed(self, protocol, rows, sizes, count, group=None):
         if group is None or int(group) >= 1:
-            from ..rangeproofs.batch import locate_plan          # (here: rangeproofs.batch imports this package)
             grp = self.default_group(protocol, count) if group is None else int(group)
             return locate_plan(count, grp, lambda idx, g: self._group_values_packed(protocol, rows, sizes, range(count) if idx is None else idx, g, None))
         if int(group) != 0:
@@ -281,12 +281,7 @@ class BatchInnerProductVerifier:
         without a count).  Both are CAPACITY rules -- what fits a launch, what balances the two levels -- and NOT measured optima:
         profiles/r18_ipa_locate_packed.txt has the first rule ahead of the bisection in every case it measured (2^14 x 64 and
         2^10 x 1024 proofs), but no other group size was timed against it, and the second rule was not measured at all."""
-        per = 2 * self.k + (4 if protocol == 1 else 2)
-        fit = (GROUP_MAX_PAIRS - 2 * self.n) // per
-        if fit >= 1:
-            return 1 << (fit.bit_length() - 1)
-        root = math.isqrt(count) if count and count > 0 else 1
-        return 1 << (max(root, 1).bit_length() - 1)
+        return default_group_for(protocol, self.k, count)
 
     def _group_values_packed(self, protocol, rows, sizes, idx, group, wb):
         """(values, status) over the rows idx (a range or a sorted list) in groups of `group` consecutive rows of idx.  A batch beyond
@@ -297,24 +292,16 @@ class BatchInnerProductVerifier:
             raise ValueError("group must be at least 1")
         count = len(idx)
         group = min(group, max(count, 1))
-        per_w = 32 * (3 if protocol == 1 else 1)
+        per_w = weight_bytes(protocol)
         groups_per_call = min(max(CALL_MAX // group, 1), max(GROUP_ROWS_MAX // (2 * self.n), 1))
         chunk = groups_per_call * group
         values, status = [], b""
         for lo in range(0, count, chunk):
             hi = min(lo + chunk, count)
-            sub = idx[lo:hi]
-            if isinstance(sub, range) and sub.step == 1:
-                cut = lambda name: rows[name][sizes[name] * sub.start: sizes[name] * sub.stop]
-            else:
-                cut = lambda name: b"".join(rows[name][sizes[name] * i: sizes[name] * (i + 1)] for i in sub)
-            u = rows["u"] if protocol == 1 else cut("u")
-            starts = None if rows["starts"] is None else [rows["starts"][i] for i in sub]
             weights = None if wb is None else wb[per_w * lo: per_w * hi]
             seed = None if weights is not None else secrets.token_bytes(32)
-            v, st = self.engine.ipa_group_values_packed_dev(self._d[0], self._d[1], self.n, protocol, hi - lo, cut("ab"), cut("xs"), cut("lr"),
-                                                            [rows["trs"][i] for i in sub], starts, u, cut("P"), cut("c"), cut("head"), weights, seed,
-                                                            self._d_scale, group)
+            v, st = self.engine.ipa_group_values_packed_dev(self._d[0], self._d[1], self.n, protocol, hi - lo, *packed_rows_cut(protocol, rows, sizes, idx[lo:hi]),
+                                                            weights, seed, self._d_scale, group)
             values += v
             status += st
         return values, status
@@ -350,7 +337,7 @@ class BatchInnerProductVerifier:
 
     def locate_packed2(self, us, Ps, ab, xs, lr, transcripts, starts=None, group=None):
         """The sorted indices of the invalid proofs of a packed Protocol-2 batch.  group = None or an integer >= 1: the two levels of
-        rangeproofs.batch.locate_plan over group_values_packed2 -- level 1 is one call with `group` (None: default_group), level 2 one
+        locate.locate_plan over group_values_packed2 -- level 1 is one call with `group` (None: default_group), level 2 one
         call with group = 1 over the unflagged proofs of the groups whose value is not the identity; a valid batch costs one native
         call, a rejected one two.  group = 0: locate_by_bisection over verify calls, every probe one native call over the gathered rows
         of the subset under fresh weights (kept for comparison).  The indices are the same in every case."""

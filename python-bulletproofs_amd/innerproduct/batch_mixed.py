@@ -6,11 +6,12 @@ A generator list is a capacity: a statement of n_p = 2^k_p elements is made over
 verifier is Verifier2(g[:n_p], h[:n_p], ...).  Under the random weights of BatchInnerProductVerifier (batch.py: its soundness note
 applies unchanged) generator i collects the weighted s-vector entries of the proofs that reach it, so arguments of 64, 256 and 4 096
 elements are one MSM of 2 n_top + (extra pairs), n_top the longest length queued, instead of one batch per length plus a sum."""
-import math
 import secrets
 
+from .. import engine as _engine
 from ..ec import pack_points, pack_scalars
-from .batch import CALL_MAX, GROUP_MAX_PAIRS, GROUP_ROWS_MAX, BatchInnerProductVerifier, Q, _Item, locate_by_bisection
+from ..locate import locate_by_bisection, locate_plan_groups        # noqa: F401  (locate_plan_groups: also this module's old export)
+from .batch import CALL_MAX, GROUP_ROWS_MAX, BatchInnerProductVerifier, Q, _Item, default_group_for, extra_pairs, packed_rows_cut, weight_bytes
 from .inner_product_verifier import Verifier2
 
 
@@ -99,28 +100,22 @@ class MixedBatchInnerProductVerifier:
         out = []
         for args in classes:
             if protocol == 2:
-                us, Ps, ab, xs, lr, trs = args[:6]
+                (u, Ps, ab, xs, lr, trs), cs, head = args[:6], None, None
                 starts = args[6] if len(args) > 6 else None
-                count = len(trs)
-                k = packed_class_k(count, xs, lr)
-                if k > self.k:
-                    raise ValueError("a class of 2^%d elements over a capacity of 2^%d generators" % (k, self.k))
-                out.append((k,) + BatchInnerProductVerifier._packed_rows(self, 2, us, Ps, None, ab, xs, lr, None, trs, starts, k))
             else:
-                u, Ps, cs, ab, xs, lr, head, trs = args
-                count = len(trs)
-                k = packed_class_k(count, xs, lr)
-                if k > self.k:
-                    raise ValueError("a class of 2^%d elements over a capacity of 2^%d generators" % (k, self.k))
-                out.append((k,) + BatchInnerProductVerifier._packed_rows(self, 1, u, Ps, cs, ab, xs, lr, head, trs, None, k))
+                (u, Ps, cs, ab, xs, lr, head, trs), starts = args, None
+            k = packed_class_k(len(trs), xs, lr)
+            if k > self.k:
+                raise ValueError("a class of 2^%d elements over a capacity of 2^%d generators" % (k, self.k))
+            out.append((k,) + BatchInnerProductVerifier._packed_rows(self, protocol, u, Ps, cs, ab, xs, lr, head, trs, starts, k))
         return out
 
     def _mixed_calls(self, protocol, prepared, idx, weights):
         """[(out, status)] of the native calls over the proofs idx (sorted global, class-major indices; None: every proof, cut class
         by class without a loop over proofs): consecutive calls cut where a cap of the ABI (2^16 proofs, 2^22 extra pairs, 64 classes)
         would be passed.  weights: packed bytes for exactly idx, or None."""
-        pairs = [2 * k + (4 if protocol == 1 else 2) for k, _, _, _ in prepared]
-        per = 32 * (3 if protocol == 1 else 1)
+        pairs = [extra_pairs(protocol, k) for k, _, _, _ in prepared]
+        per = weight_bytes(protocol)
         if idx is None:
             calls = [[(c, range(lo, hi)) for c, lo, hi in call] for call in split_mixed_ranges([p[3] for p in prepared], pairs)]
         else:
@@ -139,19 +134,7 @@ class MixedBatchInnerProductVerifier:
                 calls.append(groups)
         results, at = [], 0
         for groups in calls:
-            cls = []
-            for c, loc in groups:
-                k, rows, sizes, _ = prepared[c]
-                if isinstance(loc, range):
-                    cut = lambda name: rows[name][sizes[name] * loc.start: sizes[name] * loc.stop]
-                    trs = rows["trs"][loc.start: loc.stop]
-                    starts = None if rows["starts"] is None else rows["starts"][loc.start: loc.stop]
-                else:
-                    cut = lambda name: b"".join(rows[name][sizes[name] * i: sizes[name] * (i + 1)] for i in loc)
-                    trs = [rows["trs"][i] for i in loc]
-                    starts = None if rows["starts"] is None else [rows["starts"][i] for i in loc]
-                u = rows["u"] if protocol == 1 else cut("u")
-                cls.append((k, len(loc), cut("ab"), cut("xs"), cut("lr"), trs, starts, u, cut("P"), cut("c"), cut("head")))
+            cls = [(prepared[c][0], len(loc)) + packed_rows_cut(protocol, prepared[c][1], prepared[c][2], loc) for c, loc in groups]
             count = sum(len(loc) for _, loc in groups)
             seed = None if weights is not None else secrets.token_bytes(32)
             results.append(self.engine.ipa_verify_batch_packed_mixed_dev(self._d[0], self._d[1], self.n, protocol, cls,
@@ -202,23 +185,12 @@ class MixedBatchInnerProductVerifier:
     # (locate_plan_groups).
     def default_groups(self, protocol, prepared):
         """The group sizes locate_packed1 / locate_packed2 start with under group=None, one per class: the two rules of
-        BatchInnerProductVerifier.default_group with the class's own n_c = 2^k_c and count.  Where a group's MSM fits the one-launch
-        group kernel: the largest power of two with 2 n_c + group * per <= 8448 pairs (MID_NMAX), per = 2 k_c + 2 under Protocol 2 and
-        2 k_c + 4 under Protocol 1.  Where not even one proof fits (n_c >= 8192): the largest power of two <= sqrt(count).  prepared:
-        per class a tuple whose entry 0 is k_c and entry 3 the count (what _packed_classes returns).  As there, both are CAPACITY rules
-        -- what fits a launch, what balances the two levels -- and NOT measured optima: no other group size was timed against them for
-        a list of classes."""
-        out = []
-        for p in prepared:
-            k, count = p[0], p[3]
-            per = 2 * k + (4 if protocol == 1 else 2)
-            fit = (GROUP_MAX_PAIRS - 2 * (1 << k)) // per
-            if fit >= 1:
-                out.append(1 << (fit.bit_length() - 1))
-            else:
-                root = math.isqrt(count) if count and count > 0 else 1
-                out.append(1 << (max(root, 1).bit_length() - 1))
-        return out
+        BatchInnerProductVerifier.default_group (default_group_for: the same code) with the class's own n_c = 2^k_c and count.
+        prepared: per class a tuple whose entry 0 is k_c and entry 3 the count (what _packed_classes returns).  As there, both are
+        CAPACITY rules -- what fits a launch, what balances the two levels -- and NOT measured optima: no other group size was timed
+        against them for a list of classes (profiles/r19_ipa_locate_packed_mixed.txt has the plan under these sizes against the
+        bisection and against one single-class plan per length, nothing else)."""
+        return [default_group_for(protocol, p[0], p[3]) for p in prepared]
 
     @staticmethod
     def _class_groups(group, n_classes):
@@ -235,24 +207,13 @@ class MixedBatchInnerProductVerifier:
         batch beyond one call's caps runs as consecutive calls cut at group boundaries (split_mixed_group_calls), each under its own
         slice of the explicit weights wb or a fresh seed."""
         counts = [p[3] if sel is None else len(sel[c]) for c, p in enumerate(prepared)]
-        pairs = [2 * p[0] + (4 if protocol == 1 else 2) for p in prepared]
-        per_w = 32 * (3 if protocol == 1 else 1)
+        pairs = [extra_pairs(protocol, p[0]) for p in prepared]
+        per_w = weight_bytes(protocol)
         values, status, at = [], b"", 0
         for call in split_mixed_group_calls(counts, pairs, [1 << p[0] for p in prepared], groups):
-            cls, grp = [], []
-            for c, lo, hi in call:
-                k, rows, sizes, _ = prepared[c]
-                if sel is None:
-                    cut = lambda name: rows[name][sizes[name] * lo: sizes[name] * hi]
-                    loc = range(lo, hi)
-                else:
-                    loc = sel[c][lo:hi]
-                    cut = lambda name: b"".join(rows[name][sizes[name] * i: sizes[name] * (i + 1)] for i in loc)
-                trs = [rows["trs"][i] for i in loc]
-                starts = None if rows["starts"] is None else [rows["starts"][i] for i in loc]
-                u = rows["u"] if protocol == 1 else cut("u")
-                cls.append((k, hi - lo, cut("ab"), cut("xs"), cut("lr"), trs, starts, u, cut("P"), cut("c"), cut("head")))
-                grp.append(groups[c])
+            cls = [(prepared[c][0], hi - lo) + packed_rows_cut(protocol, prepared[c][1], prepared[c][2], range(lo, hi) if sel is None else sel[c][lo:hi])
+                   for c, lo, hi in call]
+            grp = [groups[c] for c, _, _ in call]
             count = sum(hi - lo for _, lo, hi in call)
             weights = None if wb is None else wb[per_w * at: per_w * (at + count)]
             seed = None if weights is not None else secrets.token_bytes(32)
@@ -262,7 +223,7 @@ class MixedBatchInnerProductVerifier:
             at += count
         value_off = [0]
         for count, g in zip(counts, groups):
-            value_off.append(value_off[-1] + ((count + min(g, count) - 1) // min(g, count) if count else 0))
+            value_off.append(value_off[-1] + _engine.group_count(count, g))
         if len(values) != value_off[-1] or len(status) != sum(counts):
             raise RuntimeError("the native calls returned %d values and %d status bytes for %d groups of %d proofs" % (len(values), len(status), value_off[-1], sum(counts)))
         return values, value_off, status
@@ -288,7 +249,10 @@ class MixedBatchInnerProductVerifier:
         """group_values_packed2 for Protocol-1 classes (the argument of verify_packed1; weights: three per proof)."""
         return self._group_values_packed_mixed(1, classes, group, weights)
 
-    def _locate_packed_mixed_groups(self, protocol, classes, group):
+    def _locate_packed_by_group(self, protocol, classes, group):
+        """locate_packed* by `group`: the integer 0 is the bisection, None, an integer >= 1 or a list the two-level plan."""
+        if group is not None and not isinstance(group, (list, tuple)) and int(group) == 0:
+            return self._locate_packed_mixed(protocol, classes)
         prepared = self._packed_classes(protocol, classes)
         groups = self.default_groups(protocol, prepared) if group is None else self._class_groups(group, len(prepared))
         return locate_plan_groups([p[3] for p in prepared], groups, lambda sel, grp: self._group_values_mixed(protocol, prepared, sel, grp, None))
@@ -306,15 +270,11 @@ class MixedBatchInnerProductVerifier:
         sixteen proofs of four lengths included).  group=0 stays the default because existing callers run these methods on engines
         that have only the verify call, not because it measured faster.  A batch that is probably valid: verify_packed2 first (2.80 ms
         against the plan's 6.28 over a valid batch) and locate on rejection."""
-        if group is not None and not isinstance(group, (list, tuple)) and int(group) == 0:
-            return self._locate_packed_mixed(2, classes)
-        return self._locate_packed_mixed_groups(2, classes, group)
+        return self._locate_packed_by_group(2, classes, group)
 
     def locate_packed1(self, classes, group=0):
         """locate_packed2 for Protocol-1 classes."""
-        if group is not None and not isinstance(group, (list, tuple)) and int(group) == 0:
-            return self._locate_packed_mixed(1, classes)
-        return self._locate_packed_mixed_groups(1, classes, group)
+        return self._locate_packed_by_group(1, classes, group)
 
 
 PAIRS_MAX = 1 << 22            # extra pairs per native call (IPAB_EXTRA_MAX)
@@ -390,54 +350,6 @@ def split_mixed_group_calls(counts, pairs, ns, groups, proofs_max=CALL_MAX, pair
     if cur:
         calls.append(cur)
     return calls
-
-
-_ZERO64 = bytes(64)
-
-
-def locate_plan_groups(counts, groups, group_values):
-    """The two levels of locate_packed* over a list of classes, free of any GPU -- the counterpart of rangeproofs.batch.locate_plan for
-    per-class group sizes.  counts[c]: the proofs of class c; groups[c] >= 1: its group size.  group_values(sel, groups) ->
-    (values, value_off, status) is group_values_packed* over the sub-batch sel: None = every proof, else per class the sorted list of
-    its local indices (possibly empty); values and status class-major over sel, class c's groups at values[value_off[c]: value_off[c + 1]].
-    Level 1 is group_values(None, groups) over everything; level 2 -- only when some group's value is not the identity -- is ONE call
-    group_values(sub, [1, ...]) over the unflagged proofs of those groups, class by class (a flagged proof is already located and
-    takes part in no value; a class whose level-1 groups were single proofs is already located too and takes no part).  Returns the
-    sorted GLOBAL (class-major) indices of the proofs flagged at level 1 or with a non-identity value at level 2."""
-    n_classes = len(counts)
-    if len(groups) != n_classes or any(g < 1 for g in groups):
-        raise ValueError("one group size >= 1 per class")
-    total = sum(counts)
-    if total <= 0:
-        return []
-    gbase = [0]
-    for count in counts:
-        gbase.append(gbase[-1] + count)
-    eff = [min(g, count) if count else 1 for g, count in zip(groups, counts)]
-    want = [0]
-    for g, count in zip(eff, counts):
-        want.append(want[-1] + (count + g - 1) // g)
-    values, value_off, status = group_values(None, list(groups))
-    if len(status) != total or len(values) != want[-1] or list(value_off) != want:
-        raise ValueError("group_values returned %d values (offsets %r) and %d status bytes for %d proofs in %d groups" % (len(values), list(value_off), len(status), total, want[-1]))
-    bad = [i for i in range(total) if status[i]]
-    sub = [[] for _ in counts]
-    for c, (g, count) in enumerate(zip(eff, counts)):
-        for t in range(want[c + 1] - want[c]):
-            if values[want[c] + t] != _ZERO64:
-                hit = [i for i in range(t * g, min((t + 1) * g, count)) if not status[gbase[c] + i]]
-                if g == 1:                         # level 1 was already one proof per group
-                    bad += [gbase[c] + i for i in hit]
-                else:
-                    sub[c] += hit
-    if any(sub):
-        values2, value_off2, status2 = group_values(sub, [1] * n_classes)
-        n_sub = sum(len(s) for s in sub)
-        if len(values2) != n_sub or len(status2) != n_sub:
-            raise ValueError("group_values returned %d values for a sub-batch of %d proofs" % (len(values2), n_sub))
-        flat = [gbase[c] + i for c, s in enumerate(sub) for i in s]
-        bad += [i for i, v, st in zip(flat, values2, status2) if v != _ZERO64 or st]
-    return sorted(bad)
 
 
 def batch_verify_inner_products_mixed(g, h, statements, h_scale=None, engine=None, rng=None):

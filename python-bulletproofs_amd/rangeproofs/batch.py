@@ -31,6 +31,7 @@ import secrets
 from .. import engine as _engine
 from ..ec import Point, secp256k1
 from ..innerproduct.inner_product_verifier import Verifier1, Verifier2
+from ..locate import locate_plan        # (the two levels of locate_wire; also this module's old export)
 from .rangeproof_verifier import RangeVerifier
 
 Q = secp256k1.q
@@ -575,7 +576,7 @@ class BatchRangeVerifier:
         Level 1: one group_values_wire call with `group` (default: default_group(m) -- the largest power of two with
         3 + 2 n + group * (m + 6 + 2 log2 n) <= 8448, the pairs one launch of the group kernel holds).  Level 2: one call with
         group = 1 over the unflagged proofs of the groups whose value is not the identity.  Result: the proofs flagged at level 1 and
-        the proofs with a non-identity value at level 2 (locate_plan).  Vs / blobs / offsets as for partial_wire."""
+        the proofs with a non-identity value at level 2 (locate.locate_plan).  Vs / blobs / offsets as for partial_wire."""
         count = len(blobs) if offsets is None else len(offsets) - 1
         if count <= 0:
             return []
@@ -698,32 +699,6 @@ class BatchRangeVerifier:
 
 
 LOCATE_MAX_PAIRS = 8448          # MID_NMAX (csrc/msm_kernels.hpp): the pairs of one group's MSM in the one-launch group kernel
-
-
-def locate_plan(count, group, group_values):
-    """The two levels of BatchRangeVerifier.locate_wire, free of any GPU: group_values(indices, group) -> (values, status) is
-    group_values_wire over the sub-batch `indices` (a list of batch indices in ascending order; None = the whole batch).
-    Level 1 is group_values(None, group); level 2 -- only when some group's value is not the identity -- is ONE call
-    group_values(sub, 1) over the unflagged proofs of those groups (a flagged proof is already located and takes part in no value).
-    Returns the sorted indices of the proofs flagged at level 1 or with a non-identity value at level 2."""
-    if count <= 0:
-        return []
-    if group < 1:
-        raise ValueError("group must be at least 1")
-    group = min(group, count)
-    values, status = group_values(None, group)
-    if len(status) != count or len(values) != (count + group - 1) // group:
-        raise ValueError("group_values returned %d values and %d status bytes for %d proofs in groups of %d" % (len(values), len(status), count, group))
-    bad = [i for i in range(count) if status[i]]
-    sub = [i for t, v in enumerate(values) if v != _ZERO64 for i in range(t * group, min((t + 1) * group, count)) if not status[i]]
-    if sub and group == 1:                 # level 1 was already one proof per group
-        bad += sub
-    elif sub:
-        values2, status2 = group_values(sub, 1)
-        if len(values2) != len(sub) or len(status2) != len(sub):
-            raise ValueError("group_values returned %d values for a sub-batch of %d proofs" % (len(values2), len(sub)))
-        bad += [i for i, v, st in zip(sub, values2, status2) if v != _ZERO64 or st]
-    return sorted(bad)
 
 
 def batch_verify(Vs, proofs, g, h, gs, hs, u, **kw):
