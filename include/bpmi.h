@@ -631,6 +631,29 @@ typedef struct bpmi_rp_class {
 } bpmi_rp_class;
 int bpmi_rp_batch_verify_mixed_dev(bpmi_ctx *ctx, uint32_t n_classes, const bpmi_rp_class *classes, uint32_t n_gens_max, const uint8_t *weights,
                                    const uint8_t *seed, const void *d_gens, void *d_points, void *d_scalars, uint8_t out[64], int64_t *first_bad);
+/* Which GROUPS of a mixed batch hold an invalid proof, in one call: bpmi_rp_batch_verify_mixed_dev cut the way
+ * bpmi_rp_batch_group_values_dev cuts a batch of one size.  The arguments up to d_scalars are those of bpmi_rp_batch_verify_mixed_dev
+ * (classes, class-major global numbering, weights by global index or derived from the seed by global index, d_gens = g h u gs[0..N)
+ * hs[0..N), the scratch sizes).
+ *   group      n_classes entries, each >= 1: class c is cut into groups of min(group[c], n_proofs_c) consecutive proofs, the last one
+ *              possibly short; a group never straddles a class
+ *   value_off  HOST n_classes + 1 entries: groups are numbered class-major, class c owns values[value_off[c] .. value_off[c + 1]),
+ *              value_off[n_classes] = the number of groups
+ *   values     HOST 64 B per group: values[t] = the value of group t's combination over its UNFLAGGED proofs over
+ *              [g h u gs[:n_c] hs[:n_c] | the group's commitments | the group's proof points]; 64 zero bytes exactly when all of them
+ *              verify.  The same 64 bytes bpmi_rp_batch_group_values_dev writes for that class over gs[:n_c], hs[:n_c] under the same
+ *              per-proof weights; with no proof flagged the sum of all values is the `out` of bpmi_rp_batch_verify_mixed_dev
+ *   status     HOST one byte per proof by GLOBAL index: bit 0 = a byte-level check failed, bit 1 = an invalid point encoding (wire
+ *              format 3: a wrong y), as in bpmi_rp_batch_group_values_dev.  A flagged proof takes part in no group.
+ * BPMI_E_ARG, decided before anything is read beyond the offset tables, allocated or uploaded, with nothing written: everything
+ * bpmi_rp_batch_verify_mixed_dev refuses, with its messages; group, values, value_off or status NULL; a group[c] = 0 (the message names
+ * the class); sum_c n_groups_c x (3 + 2 n_c) > 2^26.  A call refused for a point (a commitment, a generator at validation level 2) leaves
+ * 0xFF in every byte of `values`.  A well-formed proof of another wire format at a class's smallest flagged index is BPMI_E_ARG ("mixed
+ * wire formats", naming the class); under option "rp_only_role" >= 0 every status is non-zero.  A group of more than 8 448 pairs
+ * (3 + 2 n_c + group (m_c + 6 + 2 k_c)) runs as an MSM of its own: the same 64 bytes.  One call at a time per ctx. */
+int bpmi_rp_batch_group_values_mixed_dev(bpmi_ctx *ctx, uint32_t n_classes, const bpmi_rp_class *classes, uint32_t n_gens_max, const uint64_t *group,
+                                         const uint8_t *weights, const uint8_t *seed, const void *d_gens, void *d_points, void *d_scalars, uint8_t *values,
+                                         uint64_t *value_off, uint8_t *status);
 /* ---- a BATCH of single-value range proofs, proved on the device in one call (csrc/rp_prove_kernels.hpp, rp_prove_host.hpp) -------------
  * Replaces a LOOP of NIRangeProver(v, n, g, h, gs, hs, gamma, u, group, seed).prove() (/root/reference/src/rangeproofs/
  * rangeproof_prover.py:35-91) with NIProver.prove / FastNIProver2.prove inside (/root/reference/src/innerproduct/

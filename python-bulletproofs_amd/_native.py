@@ -82,6 +82,8 @@ SIGNATURES = {
     "bpmi_rp_batch_verify_dev": (_i, [_vp, ctypes.c_uint32, ctypes.c_uint32, _u64, _vp, _u64, _vp, _cp, _cp, _vp, _vp, _vp, _vp, _cp, _vp]),      # (v_points: bytes or a page-locked address)
     "bpmi_rp_batch_group_values_dev": (_i, [_vp, ctypes.c_uint32, ctypes.c_uint32, _u64, _vp, _u64, _vp, _cp, _cp, _vp, _vp, _vp, _vp, _u64, _vp, _vp]),
     "bpmi_rp_batch_verify_mixed_dev": (_i, [_vp, ctypes.c_uint32, _vp, ctypes.c_uint32, _cp, _cp, _vp, _vp, _vp, _cp, _vp]),      # (classes: an array of RpClass)
+    # ctx, n_classes, classes, n_gens_max, group (n_classes x uint64), weights, seed, d_gens, d_points, d_scalars, values, value_off, status
+    "bpmi_rp_batch_group_values_mixed_dev": (_i, [_vp, ctypes.c_uint32, _vp, ctypes.c_uint32, _vp, _cp, _cp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bpmi_rp_prover_create": (_i, [_vp, ctypes.c_uint32, _cp, _cp, _cp, _cp, _cp, ctypes.POINTER(_vp)]),
     "bpmi_rp_prover_create_aggregated": (_i, [_vp, ctypes.c_uint32, ctypes.c_uint32, _cp, _cp, _cp, _cp, _cp, ctypes.POINTER(_vp)]),
     "bpmi_rp_prover_destroy": (None, [_vp]),

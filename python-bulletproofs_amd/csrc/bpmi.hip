@@ -58,6 +58,7 @@ using namespace bpmi;
 #include "msm_plan_host.hpp"
 #include "rp_batch_plan_host.hpp"
 #include "rp_mixed_plan_host.hpp"
+#include "rp_group_mixed_plan_host.hpp"
 #include "rp_prove_plan_host.hpp"
 #include "ipa_prove_plan_host.hpp"
 #include "ipa_batch_plan_host.hpp"
@@ -895,6 +896,7 @@ int bpmi_ipa_verify_dev(bpmi_ctx *ctx, const void *d_g, const void *d_h, const v
 #include "msm_batch_host.hpp"
 #include "rp_batch_dev_host.hpp"
 #include "rp_mixed_dev_host.hpp"
+#include "rp_group_mixed_dev_host.hpp"
 
 extern "C" {
 

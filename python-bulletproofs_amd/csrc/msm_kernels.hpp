@@ -2003,6 +2003,36 @@ template <u32 THREADS, u32 NMAX> __global__ void __launch_bounds__(THREADS) k_ms
 template __global__ void k_msm_group<MID_THREADS, MID_NMAX>(GroupMsm);
 template __global__ void k_msm_group<GROUP_LIGHT_THREADS, GROUP_LIGHT_NMAX>(GroupMsm);
 
+// The groups of a MIXED batch of range proofs (bpmi_rp_batch_group_values_mixed_dev, rp_group_mixed_plan_host.hpp): k_msm_group where
+// every group has its own sizes, read from a table of eight words per group: the points offset of its contiguous generator copy
+// [g h u gs[:n_c] hs[:n_c]] inside `copies` (GENS_DIRECT: n_c = N, the list `gens` itself), 3 + 2 n_c, the word offset of its row of
+// scalars in `gfin`, its first commitment pair and their count, its first proof-point pair and their count (pairs of pts / sc), 0.
+// A launch runs the groups of `list` (those of one shape): block (slot, w) = blockIdx.x runs window w of group list[slot]; its window
+// sums go to E[group][w], so one k_group_tail serves both launches.  The table row is the same for every lane of the block: plain
+// loads the compiler keeps scalar.  The plan puts a group in a launch only where its pairs fit NMAX.
+struct GroupMixedMsm {
+  static constexpr u32 GENS_DIRECT = 0xFFFFFFFFu;
+  const u32 *gens, *copies;           // g h u gs[0..N) hs[0..N); the contiguous copies for the shorter prefixes
+  const u32 *gfin;                    // the classes' rows of scalars of the shared generators
+  const u32 *pts, *sc;                // every class's [commitments | proof points] and their scalars
+  const u32 *gtab, *list;             // eight words per group; the groups of this launch
+  u32 W;
+  u32 *E;                             // [group][w]
+};
+template <u32 THREADS, u32 NMAX> __global__ void __launch_bounds__(THREADS) k_msm_group_mixed(GroupMixedMsm J) {
+  const u32 slot = blockIdx.x / J.W, w = blockIdx.x - slot * J.W;
+  const u32 t = J.list[slot];
+  const u32 *d = J.gtab + 8ull * t;
+  const u32 gen = d[0], nshared = d[1], row = d[2], v0 = d[3], vn = d[4], p0 = d[5], pn = d[6];
+  Segs s;
+  s.pts[0] = gen == GroupMixedMsm::GENS_DIRECT ? J.gens : J.copies + 16ull * gen; s.sc[0] = J.gfin + (u64)row; s.n[0] = nshared;
+  s.pts[1] = J.pts + 16ull * v0; s.sc[1] = J.sc + 8ull * v0; s.n[1] = vn;
+  s.pts[2] = J.pts + 16ull * p0; s.sc[2] = J.sc + 8ull * p0; s.n[2] = pn;
+  group_msm_block<THREADS, NMAX>(s, t, w, J.W, J.E);
+}
+template __global__ void k_msm_group_mixed<MID_THREADS, MID_NMAX>(GroupMixedMsm);
+template __global__ void k_msm_group_mixed<GROUP_LIGHT_THREADS, GROUP_LIGHT_NMAX>(GroupMixedMsm);
+
 // The groups of a batch of packed inner-product proofs (bpmi_ipa_group_values_packed_dev, ipa_group_plan_host.hpp): the shared
 // generators are TWO arrays of n points, and each group has its own row of scalars over either one (k_sc_svector_sum_groups); the
 // third segment is the extra pairs of the group's proofs, `per` per proof, proof-major.  Block (t, w) as in k_msm_group.

@@ -66,6 +66,10 @@ static inline RpGroupShape rp_group_shape(uint64_t group, uint64_t n_proofs) {
   s.ngroups = (u32)((n_proofs + s.group - 1) / s.group);
   return s;
 }
+// the route of a class by the pairs of a FULL group's MSM, 3 + 2 n + group (m + 6 + 2k)
+static inline RpGroupRoute rp_group_route(uint64_t pairs) {
+  return pairs <= GROUP_LIGHT_NMAX ? RP_GROUPS_LIGHT : (pairs <= MID_NMAX ? RP_GROUPS_MID : RP_GROUPS_MSM_RUN);
+}
 // k_rp_group_colsum over the proofs [base, base + cnt): the groups [t0, t0 + nt) have proofs among them; lpg lanes per group, gpb groups per wave
 struct RpGroupChunk { u32 t0, nt, lpg, gpb, nblk; };
 static inline RpGroupChunk rp_group_chunk(u32 group, u32 base, u32 cnt) {
@@ -166,7 +170,7 @@ static inline RpPlan rp_prepare_plan(const BpmiOptions &o, uint32_t n_gens, uint
     p.group = gs.group; p.ngroups = gs.ngroups;
     p.msm_windows = 255u / MID_C + 1u;
     const uint64_t pairs = 3 + 2 * (uint64_t)n_gens + (uint64_t)p.group * (m + p.per);          // of a full group
-    p.route = pairs <= GROUP_LIGHT_NMAX ? RP_GROUPS_LIGHT : (pairs <= MID_NMAX ? RP_GROUPS_MID : RP_GROUPS_MSM_RUN);
+    p.route = rp_group_route(pairs);
   }
   rp_plan_layout(p, o, blobs_len, has_weights);
   rp_plan_slices(p, o, blobs_len, blob_off);

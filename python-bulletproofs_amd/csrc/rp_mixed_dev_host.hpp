@@ -4,6 +4,8 @@
 // the ctx's two lanes with no host wait between classes: per class the stages of rp_batch_dev_host.hpp in the class's own regions
 // (uploads, word-major proofs, point decoding on the second lane, column sums, shared scalars), per ROUND one launch of each of the two
 // chain kernels over every class's row chunk (k_rp_roles_mixed, k_rp_elements_mixed), then k_rp_shared_merge and one msm_run.
+// rp_mixed_enqueue also has a GROUP mode -- verdict bytes and per-group sums in place of the column sums, nothing merged -- for
+// bpmi_rp_batch_group_values_mixed_dev (rp_group_mixed_dev_host.hpp).
 #pragma once
 
 // the unit table of the whole call: slot i = plan.unit[i]; host copy in `table` (RP_MIXED_UNIT_STRIDE bytes per slot)
@@ -40,10 +42,16 @@ static void rp_mixed_round_blocks(const RpMixedPlan &mp, const RpMixedRound &rd,
   }
 }
 
-// everything up to the merged scalars, queued; `table` must live until the lanes have been waited for
+// everything up to the merged scalars, queued; `table` must live until the lanes have been waited for.
+// gm: group mode (bpmi_rp_batch_group_values_mixed_dev, rp_group_mixed_dev_host.hpp; mp is then gm->mixed) -- the two buffers hold the
+// groups' regions behind the mixed plan's, every class's cells are summed per group behind a per-proof verdict (rp_queue_group_rows in
+// place of k_rp_colsum) and folded into the scalars of the groups' MSMs (k_rp_group_scalars), nothing is merged, and under
+// rp_overlap = 0 the plan asks for the decoding in front of the rounds (RP_DECODE_FIRST).  groups: one RpGroups per class, filled here
+// (d_E / d_vals / route / W stay unset: the call has one E and one tail); it must live as long as `table`.  nullptr: the batch as one.
 static int rp_mixed_enqueue(bpmi_ctx *ctx, const RpMixedPlan &mp, const bpmi_rp_class *classes, const uint8_t *weights, const uint8_t *seed, void *d_points,
-                            void *d_scalars, PointCheck &pc, const void *d_gens, std::vector<uint8_t> &table, u32 *&d_merged, unsigned long long *&d_bad) {
-  int rc = rp_ensure_sizes(ctx, mp.stage_bytes, mp.pin_bytes, mp.need);
+                            void *d_scalars, PointCheck &pc, const void *d_gens, std::vector<uint8_t> &table, u32 *&d_merged, unsigned long long *&d_bad,
+                            const RpgmPlan *gm = nullptr, std::vector<RpGroups> *groups = nullptr) {
+  int rc = rp_ensure_sizes(ctx, mp.stage_bytes, gm ? gm->pin_bytes : mp.pin_bytes, gm ? gm->need : mp.need);
   if (rc) return rc;
   char *din = (char *)ctx->stage_in, *buf = (char *)ctx->rp_buf;
   d_merged = (u32 *)(buf + mp.merged.off);
@@ -60,14 +68,23 @@ static int rp_mixed_enqueue(bpmi_ctx *ctx, const RpMixedPlan &mp, const bpmi_rp_
   for (u32 c = 0; c < mp.n_classes; c++)
     HIPCHK(ctx, hipMemcpyAsync((char *)d_points + 64 * mp.cls[c].pair_off, d_vstage + 64 * mp.cls[c].v_off, 64 * mp.cls[c].nv, hipMemcpyDeviceToDevice, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(d_bad, 0xFF, 8, ctx->stream));
+  if (gm) {
+    groups->assign(mp.n_classes, RpGroups{});
+    for (u32 c = 0; c < mp.n_classes; c++) {
+      const RpgmClass &q = gm->cls[c];
+      RpGroups &G = (*groups)[c];
+      G.group = q.group; G.ngroups = q.ngroups;
+      G.d_gsum = (u32 *)(buf + q.gsum.off); G.d_gfin = (u32 *)(buf + q.gfin.off); G.d_verdict = (uint8_t *)(buf + q.o_verdict); G.d_ptflag = (uint8_t *)(buf + q.ptflag.off);
+    }
+  }
   std::vector<RpRun> runs;
   runs.reserve(mp.n_classes);
   for (u32 c = 0; c < mp.n_classes; c++) {
     const RpMixedClass &m = mp.cls[c];
     const bpmi_rp_class &k = classes[c];
     char *sc = (char *)d_scalars + 32 * m.pair_off;
-    runs.push_back(RpRun{m.pl, k.blobs, weights ? weights + 128 * m.first : nullptr, seed, k.blob_off, sc, sc + 32 * m.nv, (char *)d_points + 64 * (m.pair_off + m.nv), nullptr,
-                         din + m.in_base, buf + m.buf_base, d_bad, m.first});
+    runs.push_back(RpRun{m.pl, k.blobs, weights ? weights + 128 * m.first : nullptr, seed, k.blob_off, sc, sc + 32 * m.nv, (char *)d_points + 64 * (m.pair_off + m.nv),
+                         gm ? &(*groups)[c] : nullptr, din + m.in_base, buf + m.buf_base, d_bad, m.first});
   }
   rp_mixed_units(ctx, mp, runs, classes, table);
   if (!table.empty()) HIPCHK(ctx, h2d(ctx, d_units, table.data(), table.size(), ctx->stream));
@@ -78,6 +95,12 @@ static int rp_mixed_enqueue(bpmi_ctx *ctx, const RpMixedPlan &mp, const bpmi_rp_
     rc = rp_queue_words(ctx, runs[c]);
     if (rc) return rc;
   }
+  // group mode under rp_overlap = 0: the verdicts of the first round read every point flag
+  for (u32 c = 0; c < mp.n_classes; c++)
+    if (mp.cls[c].pl.decode == RP_DECODE_FIRST) rp_queue_decode(ctx, runs[c], ctx->stream, 0, mp.cls[c].pl.P);
+  // The second lane's last record is behind every class's decoding: one wait in front of the first group rows (rp_queue_group_rows waits
+  // again at every class's first chunk -- for the same, by then reached, record)
+  if (gm) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
   // per round: the two chain kernels over every class's row chunk in one launch each, then the classes' column sums
   for (const RpMixedRound &rd : mp.round) {
     u32 roles, elems;
@@ -91,17 +114,36 @@ static int rp_mixed_enqueue(bpmi_ctx *ctx, const RpMixedPlan &mp, const bpmi_rp_
       StageTimer t(ctx, ST_RPELEM);
       hipLaunchKernelGGL(rpd::k_rp_elements_mixed, dim3(elems), dim3(64), 0, ctx->stream, tab, rd.n_units);
       for (u32 i = rd.first_unit; i < rd.first_unit + rd.n_units; i++) {
+        if (gm) break;
         const RpMixedUnit &u = mp.unit[i];
         const RpPlan &pl = mp.cls[u.cls].pl;
         const u32 cnt = std::min(pl.rows, pl.P - u.chunk * pl.rows);
         hipLaunchKernelGGL(rpd::k_rp_colsum, dim3(pl.ncols), dim3(256), 0, ctx->stream, (const u32 *)runs[u.cls].d_contrib(), cnt, runs[u.cls].d_shared());
       }
     }
+    if (!gm) continue;
+    // group mode: per unit the verdict bytes and the per-group column sums of that class's chunk (its own timed section)
+    for (u32 i = rd.first_unit; i < rd.first_unit + rd.n_units; i++) {
+      const RpMixedUnit &u = mp.unit[i];
+      const RpPlan &pl = mp.cls[u.cls].pl;
+      const u32 first = u.chunk * pl.rows;
+      rc = rp_queue_group_rows(ctx, runs[u.cls], first, std::min(pl.rows, pl.P - first));
+      if (rc) return rc;
+    }
   }
   for (u32 c = 0; c < mp.n_classes; c++)
-    if (mp.cls[c].pl.decode != RP_DECODE_BESIDE) rp_queue_decode(ctx, runs[c], ctx->stream, 0, mp.cls[c].pl.P);      // option rp_overlap = 0: behind the preparation
-  // every class's constants folded into its own prefix, then the prefixes summed into the scalars of g, h, u, gs[0..N), hs[0..N)
-  {
+    if (mp.cls[c].pl.decode == RP_DECODE_LAST) rp_queue_decode(ctx, runs[c], ctx->stream, 0, mp.cls[c].pl.P);      // option rp_overlap = 0: behind the preparation
+  if (gm) {
+    // every group's constants folded into its own row of scalars, class by class
+    StageTimer t(ctx, ST_RPELEM);
+    for (u32 c = 0; c < mp.n_classes; c++) {
+      const u32 n = classes[c].n_gens;
+      const RpGroups &G = (*groups)[c];
+      hipLaunchKernelGGL(rpd::k_rp_group_scalars, dim3((u32)(((uint64_t)G.ngroups * (3 + 2 * n) + 255) / 256)), dim3(256), 0, ctx->stream, (const u32 *)G.d_gsum, n, G.ngroups,
+                         G.d_gfin);
+    }
+  } else {
+    // every class's constants folded into its own prefix, then the prefixes summed into the scalars of g, h, u, gs[0..N), hs[0..N)
     StageTimer t(ctx, ST_RPELEM);
     rpd::MergeArgs ma;
     memset(&ma, 0, sizeof(ma));
