@@ -698,6 +698,32 @@ int bpmi_rp_prover_last_ms(const bpmi_rp_prover *pv, double ms[7]);
  * out: count x 64 B affine (x, y little-endian; the identity is 64 zero bytes).  count <= 2^24; count = 0 is BPMI_OK.  Shares the
  * prover's buffers: one call at a time per prover, like proving. */
 int bpmi_rp_prover_commit_batch(bpmi_rp_prover *pv, uint64_t count, const uint8_t *values, const uint8_t *gammas, uint8_t *out);
+/* Proofs of DIFFERENT sizes from one prover, one table and one call (csrc/rp_prove_mixed_plan_host.hpp, rp_prove_mixed_kernels.hpp,
+ * rp_prove_mixed_host.hpp).  A prover created for (nbits, M) over gs, hs of N = nbits M points is a CAPACITY: a class of m values per
+ * proof -- m a power of two, 1 <= m <= M, nbits m >= 2 -- runs over gs[:nbits m], hs[:nbits m], the generators a loop of
+ * AggregNIRangeProver(vs, nbits, g, h, gs[:nbits m], hs[:nbits m], gammas, u, group, seed).prove()
+ * (/root/reference/src/rangeproofs/rangeproof_aggreg_prover.py:36-146; m = 1: NIRangeProver, rangeproof_prover.py:35-91) would be given:
+ * every proof is byte for byte what a prover created over that prefix writes.  The blocks bpmi_rp_batch_verify_mixed_dev verifies.
+ *   bpmi_rp_prove_class     one class: n_proofs x m values and gammas, seeds and seed_off (n_proofs + 1 entries) as bpmi_rp_prove_batch takes them
+ *   bpmi_rp_prove_batch_proof_bytes_class   bytes of a proof of a class of m values with a seed of seed_len bytes (0: m is no class of the prover)
+ *   bpmi_rp_prove_batch_mixed   proves classes[0 .. n_classes) in the caller's order; the proofs are numbered class-major, proof j of the call
+ *                           = out[out_off[j] .. out_off[j+1]), out_off has (sum of n_proofs) + 1 entries.  Every step of the protocol is one launch
+ *                           per kernel over ALL classes (a class of k rounds leaves the rounds beyond its own out).  Two classes may
+ *                           have the same m.  At most 64 classes, 2^20 proofs and 2^27 elements (sum of n_proofs x nbits x m) per call;
+ *                           a class of 0 proofs, an m that is no class, a seed above 65 535 bytes, a scalar not below q (the message
+ *                           names the class, the array and the first index), a cap below the sum of the proofs' bytes: BPMI_E_ARG, the
+ *                           caps before anything is read or allocated, and neither out nor out_off is written.  n_classes = 0 is BPMI_OK
+ *                           with out_off[0] = 0.  Options "prover_wire_format" and "prover_job_lanes" cover the whole call (a class's
+ *                           lanes per job by the jobs of the whole launch); "prover_split" does not apply.  bpmi_rp_prover_last_ms
+ *                           reports the same seven phases.  One window width serves every class: the capacity's. */
+typedef struct {
+  uint32_t m;                  /* values per proof */
+  uint64_t n_proofs;
+  const uint8_t *values, *gammas, *seeds;
+  const uint64_t *seed_off;
+} bpmi_rp_prove_class;
+uint64_t bpmi_rp_prove_batch_proof_bytes_class(const bpmi_rp_prover *pv, uint32_t m, uint64_t seed_len);
+int bpmi_rp_prove_batch_mixed(bpmi_rp_prover *pv, uint32_t n_classes, const bpmi_rp_prove_class *classes, uint8_t *out, uint64_t cap, uint64_t *out_off);
 
 /* ---- batched inner-product prover ------------------------------------------ */
 /* Many inner-product arguments over ONE generator set (g, h of n points each, one u), proved in one device call: a loop of

@@ -91,6 +91,9 @@ SIGNATURES = {
     "bpmi_rp_prove_batch": (_i, [_vp, _u64, _cp, _cp, _cp, _vp, _vp, _u64, _vp]),
     "bpmi_rp_prover_commit_batch": (_i, [_vp, _u64, _cp, _cp, _vp]),
     "bpmi_rp_prover_last_ms": (_i, [_vp, ctypes.POINTER(ctypes.c_double)]),
+    "bpmi_rp_prove_batch_proof_bytes_class": (_u64, [_vp, ctypes.c_uint32, _u64]),
+    # pv, n_classes, classes (RpProveClass array), out, cap, out_off
+    "bpmi_rp_prove_batch_mixed": (_i, [_vp, ctypes.c_uint32, _vp, _vp, _u64, _vp]),
     "bpmi_ipa_batch_prover_create": (_i, [_vp, ctypes.c_uint32, _cp, _cp, _cp, _cp, ctypes.POINTER(_vp)]),
     "bpmi_ipa_batch_prover_destroy": (None, [_vp]),
     "bpmi_ipa_prove_batch_transcript_bytes": (_u64, [_vp, _i, _u64]),
@@ -131,6 +134,12 @@ class RpClass(ctypes.Structure):
     structure keeps the objects behind them alive for the call."""
     _fields_ = [("n_gens", ctypes.c_uint32), ("values_per_proof", ctypes.c_uint32), ("n_proofs", ctypes.c_uint64), ("blobs", ctypes.c_void_p),
                 ("blobs_len", ctypes.c_uint64), ("blob_off", ctypes.c_void_p), ("v_points", ctypes.c_void_p)]
+
+
+class RpProveClass(ctypes.Structure):
+    """bpmi_rp_prove_class (include/bpmi.h): one class of bpmi_rp_prove_batch_mixed.  Plain addresses, as RpClass."""
+    _fields_ = [("m", ctypes.c_uint32), ("n_proofs", ctypes.c_uint64), ("values", ctypes.c_void_p), ("gammas", ctypes.c_void_p), ("seeds", ctypes.c_void_p),
+                ("seed_off", ctypes.c_void_p)]
 
 
 class IpaPackedClass(ctypes.Structure):

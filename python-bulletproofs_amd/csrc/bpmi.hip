@@ -60,6 +60,7 @@ using namespace bpmi;
 #include "rp_mixed_plan_host.hpp"
 #include "rp_group_mixed_plan_host.hpp"
 #include "rp_prove_plan_host.hpp"
+#include "rp_prove_mixed_plan_host.hpp"
 #include "ipa_prove_plan_host.hpp"
 #include "ipa_batch_plan_host.hpp"
 #include "ipa_mixed_plan_host.hpp"
@@ -93,6 +94,7 @@ using namespace bpmi;
 #include "rp_batch_kernels.hpp"
 #include "ipa_packed_kernels.hpp"
 #include "rp_prove_kernels.hpp"
+#include "rp_prove_mixed_kernels.hpp"
 #include "ipa_prove_kernels.hpp"
 #include "h2c.hpp"
 #include "h2c_kernels.hpp"
@@ -1014,4 +1016,5 @@ const char *bpmi_profile_stage_name(int stage) {
 }  // extern "C"
 
 #include "rp_prove_host.hpp"
+#include "rp_prove_mixed_host.hpp"
 #include "ipa_prove_host.hpp"

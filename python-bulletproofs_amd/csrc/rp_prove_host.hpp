@@ -15,6 +15,7 @@ struct bpmi_rp_prover {
   u32 tw = 16, wt = 16, bt = 32768;            // table windows: tw bits, wt = ceil(256 / tw) per scalar, bt = 2^(tw-1) entries each
   unsigned short *bases = nullptr;             // device: the base lists of every job kind (offsets below, in entries)
   u32 off_S = 0, off_T = 0, off_P = 0, off_round = 0;
+  unsigned short *mixed_bases = nullptr;       // device: the base lists of every class of this capacity (bpmi_rp_prove_batch_mixed: made by its first call)
   rpp::sc x_ip;                                // mod_hash(b"&", q): the Protocol-1 challenge of an empty seed (the same for every proof)
   std::string ip_prefix;                       // "&&" str(x_ip) "&"
   unsigned char *d_ip_prefix = nullptr;
@@ -95,6 +96,7 @@ void bpmi_rp_prover_destroy(bpmi_rp_prover *pv) {
   if (pv->ctx) { (void)hipSetDevice(pv->ctx->device); (void)hipStreamSynchronize(pv->ctx->stream); }
   if (pv->table) (void)hipFree(pv->table);
   if (pv->bases) (void)hipFree(pv->bases);
+  if (pv->mixed_bases) (void)hipFree(pv->mixed_bases);
   if (pv->d_ip_prefix) (void)hipFree(pv->d_ip_prefix);
   if (pv->buf) (void)hipFree(pv->buf);
   if (pv->pin) (void)hipHostFree(pv->pin);
@@ -298,7 +300,7 @@ static int rp_prove_batch_impl(bpmi_rp_prover *pv, uint64_t n_proofs, const uint
   HIPCHK(ctx, hipMemcpyAsync(d, hp, in_bytes, hipMemcpyHostToDevice, st));
   rpp::Batch B;
   memset(&B, 0, sizeof(B));
-  B.P = P; B.n = n; B.k = k; B.nb = pv->nb; B.m = pv->m; B.table = rpp::Tab{pv->table, pv->tw, pv->wt, pv->bt};
+  B.P = P; B.n = n; B.k = k; B.nb = pv->nb; B.m = pv->m; B.hs0 = 3 + n; B.table = rpp::Tab{pv->table, pv->tw, pv->wt, pv->bt};
   B.dig0 = (const unsigned char *)(d + o_dig0); B.dig0_stride = dig0_stride; B.dig0_len = (const u32 *)(d + o_dlen);
   B.values = (const u32 *)(d + o_val); B.gammas = (const u32 *)(d + o_gam);
   B.ip_prefix = pv->d_ip_prefix; B.ip_prefix_len = (u32)pv->ip_prefix.size(); B.x_ip = pv->x_ip;

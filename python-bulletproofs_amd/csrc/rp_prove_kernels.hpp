@@ -197,6 +197,8 @@ struct Batch {
   u32 *jsc;                  // job scalars: P x (2n + 1) (P_new), or 2P x (n + 1) (the L / R of a round)
   u32 *jout;                 // job results, XYZZ: up to 2P x 36 words
   u32 *pts;                  // P x (6 + 2k) affine points in wire order: T1 T2 A S u_new P_new L_0.. R_0..
+  u32 hs0;                   // base of hs_0: 3 + n; a class of a mixed call (rp_prove_mixed_kernels.hpp) runs over a prefix of N generators: 3 + N
+  u32 p0;                    // a class of a mixed call: the call-wide index of its proof 0 (its rows of the seed and output offsets); else 0
 };
 #define PV_PT_T1 0u
 #define PV_PT_T2 1u
@@ -269,8 +271,9 @@ __device__ __forceinline__ sc z_pow2p(const sc &z, const sc &zz, u32 e) {
 // lane (p, i): i < 2n: s_i = mod_hash(str(i) || digest) (rangeproof_prover.py:50-57); i = 2n: rho = mod_hash(str(2 nb) || digest) (:58 -- the
 // aggregated prover hashes str(2 * n) with n the bits PER VALUE, rangeproof_aggreg_prover.py:62: rho then equals one of the s_i; kept as it is);
 // i = 2n + 1: alpha = mod_hash(b"alpha" || digest) (:48)
-__global__ void __launch_bounds__(256) k_pv_blind(Batch B) {
-  const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+// (the body of block `blk` of a batch: k_pv_blind runs it for its own blocks, k_pv_blind_mixed for the blocks of a unit -- so every body below)
+__device__ __forceinline__ void pv_blind_block(const Batch &B, const u32 blk) {
+  const u32 t = blk * blockDim.x + threadIdx.x;
   const u32 per = 2u * B.n + 2u;
   if (t >= B.P * per) return;
   const u32 p = t / per, i = t % per;
@@ -285,6 +288,7 @@ __global__ void __launch_bounds__(256) k_pv_blind(Batch B) {
   const u64 tag = tag_of_index(i == 2u * B.n ? 2u * B.nb : i, tl);
   st_sc(B.slr + 8ull * ((size_t)p * (2u * B.n + 1u) + i), mod_hash_q(tag, tl, dg, dl));
 }
+__global__ void __launch_bounds__(256) k_pv_blind(Batch B) { pv_blind_block(B, blockIdx.x); }
 
 // ---- fixed-base multi-scalar multiplication: one job = 2^GL lanes ---------------------------------------------------------------------------
 struct MsmJobs {
@@ -299,6 +303,7 @@ struct MsmJobs {
 // Round 6: the terms that do not fill a last round of the job's lanes (T mod 2^GL of them: ONE for every job of the prover -- the u term of
 // 2^k + 1 terms) are shared out by WINDOWS, lane l taking the windows l, l + 2^GL, ... of each: with whole terms round-robin lane 0 of a
 // round's 16 lanes walked 5 terms and the other 15 lanes 4 -- the job took 5 x wt additions for 4.06 x wt of work per lane (81 %).
+// (k_pv_msm_mixed runs a COPY of this body, pv_msm_block in rp_prove_mixed_kernels.hpp: shared as a function it moved this kernel's registers)
 template <int GL> __global__ void __launch_bounds__(256) k_pv_msm(MsmJobs J, Tab T) {
   const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
   const u32 job = t >> GL, l = t & ((1u << GL) - 1u);
@@ -361,8 +366,8 @@ template <int GL> __global__ void __launch_bounds__(256) k_pv_msm(MsmJobs J, Tab
 
 // A = sum_i (bit_i ? gs_i : -hs_i) + alpha h (rangeproof_prover.py:40-49: aL the bits, aR = aL - 1): 16 lanes per proof, n / 16 bit
 // positions and every sixteenth window of alpha h each
-__global__ void __launch_bounds__(256) k_pv_commit_A(Batch B, u32 *__restrict__ out) {
-  const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void pv_commit_A_block(const Batch &B, u32 *__restrict__ out, const u32 blk) {
+  const u32 t = blk * blockDim.x + threadIdx.x;
   const u32 p = t >> 4, l = t & 15u;
   const bool live = p < B.P;
   xyzz acc;
@@ -370,7 +375,7 @@ __global__ void __launch_bounds__(256) k_pv_commit_A(Batch B, u32 *__restrict__ 
   if (live) {
     for (u32 i = l; i < B.n; i += 16u) {
       const u32 bit = bit_of(B, p, i);
-      const u32 base = bit ? 3u + i : 3u + B.n + i;
+      const u32 base = bit ? 3u + i : B.hs0 + i;
       affine Pt;
       ::load_affine(Pt, B.table.p + 16ull * ((size_t)base * B.table.wt * B.table.bt));          // window 0, d = 1: the generator itself
       bpmi::xyzz_madd_signed(acc, Pt, bit == 0u);
@@ -395,10 +400,11 @@ __global__ void __launch_bounds__(256) k_pv_commit_A(Batch B, u32 *__restrict__ 
   }
   if (live && l == 0) ::xyzz_store_g(out + 36ull * p, acc);
 }
+__global__ void __launch_bounds__(256) k_pv_commit_A(Batch B, u32 *__restrict__ out) { pv_commit_A_block(B, out, blockIdx.x); }
 
 // XYZZ results -> affine points: result j goes to pts[(j / per) * pt_stride + slot0 + (j % per) * slot_step]
-__global__ void __launch_bounds__(256) k_pv_affine(const u32 *__restrict__ in, u32 count, u32 per, u32 *__restrict__ pts, u32 pt_stride, u32 slot0, u32 slot_step) {
-  const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void pv_affine_block(const u32 *__restrict__ in, u32 count, u32 per, u32 *__restrict__ pts, u32 pt_stride, u32 slot0, u32 slot_step, const u32 blk) {
+  const u32 j = blk * blockDim.x + threadIdx.x;
   if (j >= count) return;
   xyzz a;
   ::xyzz_load_g(a, in + 36ull * j);
@@ -407,6 +413,9 @@ __global__ void __launch_bounds__(256) k_pv_affine(const u32 *__restrict__ in, u
   u32 w[16];
   bpmi::affine_to_words(w, r);
   ::store_words16(pts + 16ull * ((size_t)(j / per) * pt_stride + slot0 + (j % per) * slot_step), w);
+}
+__global__ void __launch_bounds__(256) k_pv_affine(const u32 *__restrict__ in, u32 count, u32 per, u32 *__restrict__ pts, u32 pt_stride, u32 slot0, u32 slot_step) {
+  pv_affine_block(in, count, per, pts, pt_stride, slot0, slot_step, blockIdx.x);
 }
 
 // ---- commitments from the prover's tables (bpmi_rp_prover_commit_batch): job i of k_pv_msm<1> over the base list T (g, h) takes the
@@ -418,8 +427,8 @@ __global__ void __launch_bounds__(256) k_pv_commit_pairs(const u32 *__restrict__
 }
 
 // ---- challenges y, z and the blinding factors of T1, T2 (rangeproof_prover.py:60-67) ------------------------------------------------------
-__global__ void __launch_bounds__(64) k_pv_chal_yz(Batch B) {
-  const u32 p = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void pv_chal_yz_block(const Batch &B, const u32 blk) {
+  const u32 p = blk * blockDim.x + threadIdx.x;
   if (p >= B.P) return;
   u8 *tr = B.tr + (size_t)p * B.tr_stride;
   const u8 *dg = B.dig0 + (size_t)p * B.dig0_stride;
@@ -439,6 +448,7 @@ __global__ void __launch_bounds__(64) k_pv_chal_yz(Batch B) {
   st_sc(B.tau + 16ull * p, mod_hash_q(t1, 4, tr, len));
   st_sc(B.tau + 16ull * p + 8, mod_hash_q(t2, 4, tr, len));
 }
+__global__ void __launch_bounds__(64) k_pv_chal_yz(Batch B) { pv_chal_yz_block(B, blockIdx.x); }
 
 // ---- the vector steps with n lanes per proof (block = NT threads = NT / n proofs; n <= 1024 a power of two, NT = 256 for n <= 256, else n:
 // rp_prove_plan_host.hpp) ----------------------------------------------------------------------------------------------------------------
@@ -472,10 +482,10 @@ __device__ __forceinline__ sc sc_pow2(u32 e) {                // 2^e, e < 256 (t
 }
 // ---- t1, t2 (rangeproof_prover.py:93-101) -------------------------------------------------------------------------------------------------
 //   t1 = sum sL_i (y^i (aR_i + z) + z^(2 + i / nb) 2^(i % nb)) + sum (aL_i - z) y^i sR_i,   t2 = sum sL_i y^i sR_i;   y^j is left in cg_j for k_pv_final_wide
-template <u32 NT> __global__ void __launch_bounds__(NT) k_pv_poly(Batch B) {
+template <u32 NT> __device__ __forceinline__ void pv_poly_block(const Batch &B, const u32 blk) {
   __shared__ u32 s_v[NT * 8], s_w[NT * 8];
   const u32 n = B.n, tid = threadIdx.x;
-  const u32 p = blockIdx.x * (NT / n) + tid / n, j = tid & (n - 1u);
+  const u32 p = blk * (NT / n) + tid / n, j = tid & (n - 1u);
   const bool live = p < B.P;
   const size_t pc = live ? p : 0;                             // (lanes past the batch compute on proof 0 and store nothing)
   const sc y = ld_sc(B.chal + 32ull * pc), z = ld_sc(B.chal + 32ull * pc + 8);
@@ -497,12 +507,13 @@ template <u32 NT> __global__ void __launch_bounds__(NT) k_pv_poly(Batch B) {
     st_sc(o, t1); st_sc(o + 8, ld_sc(B.tau + 16ull * p)); st_sc(o + 16, t2); st_sc(o + 24, ld_sc(B.tau + 16ull * p + 8));
   }
 }
+template <u32 NT> __global__ void __launch_bounds__(NT) k_pv_poly(Batch B) { pv_poly_block<NT>(B, blockIdx.x); }
 
 // ---- x; l, r, t_hat, taux, mu; the scalars of P_new and the state of Protocol 2 (rangeproof_prover.py:68-90, inner_product_prover.py:33-37)
 //   P + (-mu) h = <l, gs> + <r, hsp>,  hsp_i = y^-i hs_i   ->   P_new = sum l_i gs_i + sum (r_i y^-i) hs_i + (x_ip t_hat) u
 // k_pv_final_chal, one lane per proof: the hash, 1 / y, taux, mu, the Protocol-2 transcript's start; k_pv_final_wide: the vectors
-__global__ void __launch_bounds__(64) k_pv_final_chal(Batch B) {
-  const u32 p = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void pv_final_chal_block(const Batch &B, const u32 blk) {
+  const u32 p = blk * blockDim.x + threadIdx.x;
   if (p >= B.P) return;
   u8 *tr = B.tr + (size_t)p * B.tr_stride;
   u32 len = B.tr_len[p];
@@ -529,10 +540,11 @@ __global__ void __launch_bounds__(64) k_pv_final_chal(Batch B) {
   for (u32 i = 0; i < B.ip_prefix_len; i++) tr[i] = B.ip_prefix[i];
   B.tr_len[p] = B.ip_prefix_len;
 }
-template <u32 NT> __global__ void __launch_bounds__(NT) k_pv_final_wide(Batch B) {
+__global__ void __launch_bounds__(64) k_pv_final_chal(Batch B) { pv_final_chal_block(B, blockIdx.x); }
+template <u32 NT> __device__ __forceinline__ void pv_final_wide_block(const Batch &B, const u32 blk) {
   __shared__ u32 s_v[NT * 8];
   const u32 n = B.n, tid = threadIdx.x;
-  const u32 p = blockIdx.x * (NT / n) + tid / n, j = tid & (n - 1u);
+  const u32 p = blk * (NT / n) + tid / n, j = tid & (n - 1u);
   const bool live = p < B.P;
   const size_t pc = live ? p : 0;
   const sc y_inv = ld_sc(B.chal + 32ull * pc + 24), z = ld_sc(B.chal + 32ull * pc + 8), x = ld_sc(B.chal + 32ull * pc + 16);
@@ -556,6 +568,7 @@ template <u32 NT> __global__ void __launch_bounds__(NT) k_pv_final_wide(Batch B)
     st_sc(B.res + 40ull * p + 16, t_hat);
   }
 }
+template <u32 NT> __global__ void __launch_bounds__(NT) k_pv_final_wide(Batch B) { pv_final_wide_block<NT>(B, blockIdx.x); }
 
 // ---- one round of Protocol 2 (inner_product_prover.py:94-110) over the UNFOLDED generators ----------------------------------------------------
 // State of length len = n >> round, half = len / 2; generator j of the original n sits in folded position j mod len with coefficient
@@ -567,8 +580,8 @@ template <u32 NT> __global__ void __launch_bounds__(NT) k_pv_final_wide(Batch B)
 // proof for everything a round cost 1.4 ms beside its 3.1 ms of additions (profiles/r05_batch_prover_first_run.txt).
 
 // L, R -> transcript -> x, 1 / x (inner_product_prover.py:100-106)
-__global__ void __launch_bounds__(64) k_pv_round_chal(Batch B, u32 round) {
-  const u32 p = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void pv_round_chal_block(const Batch &B, const u32 round, const u32 blk) {
+  const u32 p = blk * blockDim.x + threadIdx.x;
   if (p >= B.P) return;
   const u32 npt = 6u + 2u * B.k;
   u8 *tr = B.tr + (size_t)p * B.tr_stride;
@@ -583,13 +596,14 @@ __global__ void __launch_bounds__(64) k_pv_round_chal(Batch B, u32 round) {
   st_sc(B.xr + 16ull * p, x);
   st_sc(B.xr + 16ull * p + 8, invq(x));
 }
+__global__ void __launch_bounds__(64) k_pv_round_chal(Batch B, u32 round) { pv_round_chal_block(B, round, blockIdx.x); }
 // n lanes per proof (block = NT threads = NT / n proofs; NT = 1024: 4 x 32 KB of LDS, a block per CU).  round = the round whose challenge was just drawn: the state is
 // folded with it (:107-110), then the scalars of the NEXT round's L and R are written; first = 1: no fold, the state is the one
 // k_pv_final left (the scalars of round 0).  After the last fold a[0], b[0] are the proof's scalars.
-template <u32 NT> __global__ void __launch_bounds__(NT) k_pv_round_wide(Batch B, u32 round, u32 first) {
+template <u32 NT> __device__ __forceinline__ void pv_round_wide_block(const Batch &B, const u32 round, const u32 first, const u32 blk) {
   __shared__ u32 s_a[NT * 8], s_b[NT * 8], s_l[NT * 8], s_r[NT * 8];
   const u32 n = B.n, tid = threadIdx.x;
-  const u32 p = blockIdx.x * (NT / n) + tid / n, j = tid & (n - 1u);
+  const u32 p = blk * (NT / n) + tid / n, j = tid & (n - 1u);
   const bool live = p < B.P;
   const u32 base = tid - j;                                  // first thread of this proof in the block
   u32 len = first ? n : (n >> round);                        // length BEFORE this call's fold
@@ -648,12 +662,14 @@ template <u32 NT> __global__ void __launch_bounds__(NT) k_pv_round_wide(Batch B,
   st_sc((up ? jl : jr) + 8ull * rank, mulq(ga, cgj));                       // L: a_(i-half) cg_j for i >= half; R: a_(i+half) cg_j for i < half
   st_sc((up ? jr : jl) + 8ull * ((n >> 1) + rank), mulq(hb, hfj));          // L: b_(i+half) hf_j for i < half; R: b_(i-half) hf_j for i >= half
 }
+template <u32 NT> __global__ void __launch_bounds__(NT) k_pv_round_wide(Batch B, u32 round, u32 first) { pv_round_wide_block<NT>(B, round, first, blockIdx.x); }
 
 // ---- the proofs as wire format 2 or 3 (rangeproofs/codec.py; option "prover_wire_format"): "BPRP2" k | taux mu t_hat a b | xs | 6 + 2k compressed points | y z x x_ip |
 // len seed | len Protocol-1 seed (empty) ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void put_be32(u8 *dst, const sc &v) {
   for (int i = 0; i < 32; i++) dst[i] = (u8)(v.v[7 - (i >> 2)] >> (8 * (3 - (i & 3))));
 }
+// (k_pv_emit_mixed runs a COPY of this body, pv_emit_block in rp_prove_mixed_kernels.hpp, for the same reason as k_pv_msm's)
 __global__ void __launch_bounds__(64) k_pv_emit(Batch B, const u8 *__restrict__ seeds, const u64 *__restrict__ seed_off, u8 *__restrict__ out, const u64 *__restrict__ out_off,
                                                 u32 fmt) {
   const u32 p = blockIdx.x * blockDim.x + threadIdx.x;

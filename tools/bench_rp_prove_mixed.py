@@ -1,0 +1,140 @@
+#!/usr/bin/env python3
+"""One mixed call of the batched range-proof prover (MixedBatchRangeProver.prove_classes_packed, bpmi_rp_prove_batch_mixed) against the
+loop of one BatchRangeProver per class, on blocks of 64-bit values in classes m = 1 / 2 / 4 / 8 / 16.
+
+    python tools/bench_rp_prove_mixed.py [proofs per class, comma separated ...]
+
+Default blocks: 2048,1024,512,256,256 (the block of profiles/r13 and r20), 64 per class, 4 per class.  Three set-ups in ONE process:
+  mixed   one prover over the 1 024 generators, one table (the capacity's window width), one call per block;
+  loop_a  five provers over the prefixes at the SAME window width as the shared table: isolates the launch structure;
+  loop_b  five provers at each class's default width (rpp_default_table_bits): what a user ran before the mixed call.
+Per block: a warm-up of each, a check that all three write the same bytes, then 9 rounds that run the three alternately; printed are
+the median and range of the wall time (host clock around the call: it ends in a synchronise) and of the device time (last_ms()["total"],
+summed over the loop's calls).  Table bytes and build times of the set-ups come first.  RPM_TW: window bits of the shared table (0: the
+default of 1 024 elements).  One JSON line per result."""
+import ctypes
+import hashlib
+import json
+import os
+import statistics
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+import bulletproofs_amd  # noqa: F401,E402
+from bulletproofs_amd.engine import default_engine  # noqa: E402
+from bulletproofs_amd.ec import Point, secp256k1  # noqa: E402
+from bulletproofs_amd.rangeproofs import BatchRangeProver, MixedBatchRangeProver  # noqa: E402
+
+Q = secp256k1.q
+NB, MS = 64, (1, 2, 4, 8, 16)
+N = NB * MS[-1]
+ROUNDS = 9
+eng = default_engine()
+
+
+def table_bytes(elems, w):
+    return (3 + 2 * elems) * ((256 + w - 1) // w) * (1 << (w - 1)) * 64
+
+
+def default_bits(elems):
+    return 16 if elems <= 128 else max(b for b in range(4, 17) if table_bytes(elems, b) <= table_bytes(128, 16))
+
+
+def points(count):
+    ks = b"".join((int.from_bytes(hashlib.sha256(b"rpm/%d" % i).digest(), "big") % Q).to_bytes(32, "little") for i in range(count))
+    out = eng.ec_mul_batch_bytes(secp256k1.G.to_le64() * count, ks, count)
+    return [Point.from_le64(out[64 * i: 64 * i + 64]) for i in range(count)]
+
+
+def timed(make):
+    eng.sync()
+    t = time.perf_counter()
+    obj = make()
+    eng.sync()
+    return obj, (time.perf_counter() - t) * 1e3
+
+
+def with_bits(bits, make):
+    eng.set_option("prover_table_bits", bits)
+    try:
+        return timed(make)
+    finally:
+        eng.set_option("prover_table_bits", 0)
+
+
+pts = points(2 * N + 3)
+g, h, u, gs, hs = pts[0], pts[1], pts[2], pts[3:3 + N], pts[3 + N:]
+TW = int(os.environ.get("RPM_TW", "0")) or default_bits(N)
+mixed, ms_mixed = with_bits(TW, lambda: MixedBatchRangeProver(NB, g, h, gs, hs, u))
+loop_a, loop_b, ms_a, ms_b = {}, {}, 0.0, 0.0
+for m in MS:
+    loop_a[m], dt = with_bits(TW, lambda: BatchRangeProver(NB, g, h, gs[:NB * m], hs[:NB * m], u, m=m))
+    ms_a += dt
+    loop_b[m], dt = with_bits(0, lambda: BatchRangeProver(NB, g, h, gs[:NB * m], hs[:NB * m], u, m=m))
+    ms_b += dt
+print(json.dumps({"setups": {
+    "mixed": {"window_bits": TW, "table_GB": round(table_bytes(N, TW) / 1e9, 2), "build_ms": round(ms_mixed, 1)},
+    "loop_a": {"window_bits": TW, "table_GB": round(sum(table_bytes(NB * m, TW) for m in MS) / 1e9, 2), "build_ms": round(ms_a, 1)},
+    "loop_b": {"window_bits": [default_bits(NB * m) for m in MS], "table_GB": round(sum(table_bytes(NB * m, default_bits(NB * m)) for m in MS) / 1e9, 2),
+               "build_ms": round(ms_b, 1)}}}), flush=True)
+
+
+def inputs(m, count, tag):
+    vs = b"".join((int.from_bytes(hashlib.sha256(b"v%d/%d/%d" % (tag, m, i)).digest()[:8], "big")).to_bytes(32, "little") for i in range(count * m))
+    gammas = b"".join((int.from_bytes(hashlib.sha256(b"g%d/%d/%d" % (tag, m, i)).digest(), "big") % Q).to_bytes(32, "little") for i in range(count * m))
+    seeds = [b"seed-%d-%d" % (m, i) for i in range(count)]
+    off = (ctypes.c_uint64 * (count + 1))()
+    pos = 0
+    for i, sd in enumerate(seeds):
+        off[i] = pos
+        pos += len(sd)
+    off[count] = pos
+    return vs, gammas, (b"".join(seeds), off)
+
+
+def run_mixed(classes):
+    t = time.perf_counter()
+    out = mixed.prove_classes_packed(classes, copy=False)
+    wall = (time.perf_counter() - t) * 1e3
+    return wall, mixed.last_ms()["total"], out
+
+
+def run_loop(provers, classes):
+    t = time.perf_counter()
+    out, dev = [], 0.0
+    for m, vs, gammas, seeds in classes:
+        packed, off = provers[m].prove_wire_packed(vs, gammas, seeds, copy=False)
+        out.append(bytes(packed))
+        dev += provers[m].last_ms()["total"]            # (read inside the window: the loop's user would not, and it costs microseconds)
+    return (time.perf_counter() - t) * 1e3, dev, out
+
+
+def summary(xs):
+    return {"median": round(statistics.median(xs), 3), "min": round(min(xs), 3), "max": round(max(xs), 3)}
+
+
+blocks = [[int(x) for x in a.split(",")] for a in sys.argv[1:]] or [[2048, 1024, 512, 256, 256], [64] * 5, [4] * 5]
+for tag, counts in enumerate(blocks):
+    assert len(counts) == len(MS)
+    classes = [(m,) + inputs(m, c, tag) for m, c in zip(MS, counts)]
+    runs = {"mixed": lambda: run_mixed(classes), "loop_a": lambda: run_loop(loop_a, classes), "loop_b": lambda: run_loop(loop_b, classes)}
+    warm = {name: fn() for name, fn in runs.items()}
+    same = [bytes(p) for _, p, _ in warm["mixed"][2]] == warm["loop_a"][2] == warm["loop_b"][2]
+    wall, dev = {name: [] for name in runs}, {name: [] for name in runs}
+    for _ in range(ROUNDS):
+        for name, fn in runs.items():
+            w, d, _ = fn()
+            wall[name].append(w)
+            dev[name].append(d)
+    line = {"proofs_per_class": counts, "proofs": sum(counts), "same_bytes": same, "rounds": ROUNDS}
+    for name in runs:
+        line[name] = {"wall_ms": summary(wall[name]), "device_ms": summary(dev[name])}
+    for base in ("loop_a", "loop_b"):
+        line["mixed_over_" + base] = {"wall": round(statistics.median(wall["mixed"]) / statistics.median(wall[base]), 3),
+                                      "device": round(statistics.median(dev["mixed"]) / statistics.median(dev[base]), 3)}
+    print(json.dumps(line), flush=True)
+mixed.close()
+for p in list(loop_a.values()) + list(loop_b.values()):
+    p.close()
