@@ -1015,6 +1015,7 @@ const char *bpmi_profile_stage_name(int stage) {
 
 }  // extern "C"
 
+#include "prove_shared_host.hpp"
 #include "rp_prove_host.hpp"
 #include "rp_prove_mixed_host.hpp"
 #include "ipa_prove_host.hpp"

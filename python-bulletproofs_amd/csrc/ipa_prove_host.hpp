@@ -15,8 +15,7 @@ struct bpmi_ipa_batch_prover {
   unsigned short *cbases = nullptr;            // device: the base lists of a statement's job (ipp_commit_bases_all)
   u32 off_head = 0, off_round = 0;
   u32 *hscale = nullptr;                       // device: n scalars, or nullptr
-  void *buf = nullptr; size_t buf_bytes = 0;   // the batch's device arrays (grown on demand)
-  void *pin = nullptr; size_t pin_bytes = 0;   // page-locked staging of the inputs / the proofs
+  rpp_host::Buffers mem;                       // the batch's device arrays; page-locked staging of the inputs / the proofs
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};      // phase boundaries of a batch
   double last_ms[4] = {0};                     // device milliseconds of the last batch: begin + head | rounds | copy out | whole
   double commit_ms[2] = {0};                   // the last bpmi_ipa_batch_prover_commit_batch: its kernels on the device | the whole call on the host's clock
@@ -31,8 +30,7 @@ void bpmi_ipa_batch_prover_destroy(bpmi_ipa_batch_prover *pv) {
   if (pv->bases) (void)hipFree(pv->bases);
   if (pv->cbases) (void)hipFree(pv->cbases);
   if (pv->hscale) (void)hipFree(pv->hscale);
-  if (pv->buf) (void)hipFree(pv->buf);
-  if (pv->pin) (void)hipHostFree(pv->pin);
+  pv->mem.release();
   for (auto e : pv->ev) if (e) (void)hipEventDestroy(e);
   delete pv;
 }
@@ -43,8 +41,7 @@ static int ipa_batch_prover_create_impl(bpmi_ctx *ctx, uint32_t n, const uint8_t
   *out = nullptr;
   const IppPlan plan = ipp_plan(n, ctx->opt_prover_tw);          // (option "prover_table_bits" is read HERE)
   if (plan.err) return fail(ctx, plan.err, plan.msg);
-  if (h_scale) for (u32 j = 0; j < n; j++)
-    if (!rp_scalar_reduced(h_scale + 32 * (size_t)j)) return fail(ctx, BPMI_E_ARG, "bpmi_ipa_batch_prover_create: h_scale[" + std::to_string(j) + "] is not below the group order");
+  if (const std::string bad = rpp_host::unreduced({{"h_scale", h_scale, n}}); !bad.empty()) return fail(ctx, BPMI_E_ARG, "bpmi_ipa_batch_prover_create: " + bad);
   HIPCHK(ctx, hipSetDevice(ctx->device));
   {
     const PointCheck pc(ctx, "bpmi_ipa_batch_prover_create", ctx->stream, ctx->opt_validate >= 1);
@@ -88,17 +85,11 @@ static int ipa_batch_prover_create_impl(bpmi_ctx *ctx, uint32_t n, const uint8_t
   partial = nullptr;
   return BPMI_OK;
 }
-// (the C ABI never throws: a failed host allocation inside is BPMI_E_NOMEM)
 int bpmi_ipa_batch_prover_create(bpmi_ctx *ctx, uint32_t n, const uint8_t *g, const uint8_t *h, const uint8_t u[64], const uint8_t *h_scale,
                                  bpmi_ipa_batch_prover **out) {
   bpmi_ipa_batch_prover *partial = nullptr;
-  try {
-    return ipa_batch_prover_create_impl(ctx, n, g, h, u, h_scale, out, partial);
-  } catch (const std::bad_alloc &) {
-    if (partial) bpmi_ipa_batch_prover_destroy(partial);
-    if (out) *out = nullptr;
-    return ctx ? fail(ctx, BPMI_E_NOMEM, "bpmi_ipa_batch_prover_create: out of host memory") : BPMI_E_NOMEM;
-  }
+  return rpp_host::guarded(ctx, "bpmi_ipa_batch_prover_create", [&] { return ipa_batch_prover_create_impl(ctx, n, g, h, u, h_scale, out, partial); },
+                           [&] { if (partial) bpmi_ipa_batch_prover_destroy(partial); if (out) *out = nullptr; });
 }
 
 uint64_t bpmi_ipa_prove_batch_transcript_bytes(const bpmi_ipa_batch_prover *pv, int protocol, uint64_t seed_len) {
@@ -125,13 +116,9 @@ static int ipa_prove_batch_impl(bpmi_ipa_batch_prover *pv, int protocol, uint64_
   if (const char *bad = ipp_seeds_error(n_proofs, seed_off, seeds != nullptr, &max_seed)) return fail(ctx, BPMI_E_ARG, std::string("bpmi_ipa_prove_batch: ") + bad);
   const u32 P = (u32)n_proofs, n = pv->n, k = pv->k;
   if (const char *bad = ipp_cap_error(k, protocol, n_proofs, max_seed, cap)) return fail(ctx, BPMI_E_ARG, std::string("bpmi_ipa_prove_batch: ") + bad);
-  // the reference's provers take ModP values: reduced by construction (src/utils/utils.py:24-27); raw bytes are checked here
-  for (uint64_t i = 0; i < n_proofs * n; i++) {
-    if (!rp_scalar_reduced(a + 32 * i)) return fail(ctx, BPMI_E_ARG, "bpmi_ipa_prove_batch: a[" + std::to_string(i) + "] is not below the group order");
-    if (!rp_scalar_reduced(b + 32 * i)) return fail(ctx, BPMI_E_ARG, "bpmi_ipa_prove_batch: b[" + std::to_string(i) + "] is not below the group order");
-  }
-  if (c) for (uint64_t i = 0; i < n_proofs; i++)
-    if (!rp_scalar_reduced(c + 32 * i)) return fail(ctx, BPMI_E_ARG, "bpmi_ipa_prove_batch: c[" + std::to_string(i) + "] is not below the group order");
+  for (int pass = 0; pass < 2; pass++)                   // a and b side by side, then c
+    if (const std::string bad = pass ? rpp_host::unreduced({{"c", c, n_proofs}}) : rpp_host::unreduced({{"a", a, n_proofs * n}, {"b", b, n_proofs * n}}); !bad.empty())
+      return fail(ctx, BPMI_E_ARG, "bpmi_ipa_prove_batch: " + bad);
   HIPCHK(ctx, hipSetDevice(ctx->device));
   // the transcript's start: Protocol 1 base64(seed) "&" (transcript.py:13-14), Protocol 2 "&" || prefix (inner_product_prover.py:58-63)
   const u32 dig0_stride = (u32)(((protocol == 1 ? ((max_seed + 2) / 3) * 4 + 1 : 1 + max_seed) + 15) & ~15ull);
@@ -150,24 +137,14 @@ static int ipa_prove_batch_impl(bpmi_ipa_batch_prover *pv, int protocol, uint64_
   const size_t o_ab = take(64ull * P), o_xs = take(32ull * P * k), o_lr = take(128ull * P * k), o_head = take(128ull * P);
   const size_t o_trlen = take(4ull * P), o_tr = take((size_t)P * tr_stride);
   const size_t out_bytes = o - o_out;
-  if (o > pv->buf_bytes) {
-    if (pv->buf) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(pv->buf)); pv->buf = nullptr; pv->buf_bytes = 0; }
-    HIPCHK(ctx, hipMalloc(&pv->buf, o + o / 8));
-    pv->buf_bytes = o + o / 8;
-  }
-  const size_t pin_need = std::max(in_bytes, out_bytes);
-  if (pin_need > pv->pin_bytes) {
-    if (pv->pin) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipHostFree(pv->pin)); pv->pin = nullptr; pv->pin_bytes = 0; }
-    HIPCHK(ctx, hipHostMalloc(&pv->pin, pin_need + pin_need / 8, hipHostMallocDefault));
-    pv->pin_bytes = pin_need + pin_need / 8;
-  }
-  char *d = (char *)pv->buf, *hp = (char *)pv->pin;
+  if (int rc = pv->mem.grow(ctx, o, std::max(in_bytes, out_bytes))) return rc;
+  char *d = (char *)pv->mem.buf, *hp = (char *)pv->mem.pin;
   // ---- inputs into the staging buffer
   for (u32 p = 0; p < P; p++) {
-    char *dg = hp + o_dig0 + (size_t)p * dig0_stride;
+    uint8_t *dg = (uint8_t *)hp + o_dig0 + (size_t)p * dig0_stride;
     const uint64_t sl = seed_off[p + 1] - seed_off[p];
     size_t tl = 0;
-    if (protocol == 1) { tl = rpp_host::b64_into(dg, sl ? seeds + seed_off[p] : (const uint8_t *)"", sl); dg[tl++] = '&'; }
+    if (protocol == 1) { tl = rp::b64_encode(dg, sl ? seeds + seed_off[p] : (const uint8_t *)"", sl); dg[tl++] = '&'; }
     else { dg[tl++] = '&'; if (sl) memcpy(dg + tl, seeds + seed_off[p], sl); tl += sl; }
     ((u32 *)(hp + o_dlen))[p] = (u32)tl;
   }
@@ -201,12 +178,7 @@ static int ipa_prove_batch_impl(bpmi_ipa_batch_prover *pv, int protocol, uint64_
     else hipLaunchKernelGGL(ipp::k_ip_round_wide<1024>, grid, dim3(1024), 0, st, B, round, first);
   };
   auto msm = [&](u32 njobs, u32 ntypes, u32 T, u32 base_off, const u32 *scalars, u32 stride, int gl) {
-    rpp::MsmJobs J;
-    J.njobs = njobs; J.ntypes = ntypes; J.T = T; J.bases = pv->bases + base_off; J.scalars = scalars; J.stride = stride; J.out = B.jout;
-    const uint64_t threads = (uint64_t)njobs << gl;
-    if (gl == 6) hipLaunchKernelGGL(rpp::k_pv_msm<6>, blocks(threads, 256), dim3(256), 0, st, J, tab);
-    else if (gl == 4) hipLaunchKernelGGL(rpp::k_pv_msm<4>, blocks(threads, 256), dim3(256), 0, st, J, tab);
-    else hipLaunchKernelGGL(rpp::k_pv_msm<1>, blocks(threads, 256), dim3(256), 0, st, J, tab);
+    rpp_host::launch_msm(st, rpp::MsmJobs{njobs, ntypes, T, pv->bases + base_off, scalars, stride, B.jout}, tab, gl);
   };
   (void)hipEventRecord(ev[0], st);
   hipLaunchKernelGGL(ipp::k_ip_begin, blocks(P, 64), dim3(64), 0, st, B);
@@ -251,11 +223,8 @@ static int ipa_prove_batch_impl(bpmi_ipa_batch_prover *pv, int protocol, uint64_
 int bpmi_ipa_prove_batch(bpmi_ipa_batch_prover *pv, int protocol, uint64_t n_proofs, const uint8_t *a, const uint8_t *b, const uint8_t *c, const uint8_t *P,
                          const uint8_t *seeds, const uint64_t *seed_off, uint8_t *ab, uint8_t *xs, uint8_t *LR, uint8_t *head, uint8_t *transcripts,
                          uint64_t cap, uint64_t *tr_off) {
-  try {
-    return ipa_prove_batch_impl(pv, protocol, n_proofs, a, b, c, P, seeds, seed_off, ab, xs, LR, head, transcripts, cap, tr_off);
-  } catch (const std::bad_alloc &) {
-    return pv && pv->ctx ? fail(pv->ctx, BPMI_E_NOMEM, "bpmi_ipa_prove_batch: out of host memory") : BPMI_E_NOMEM;
-  }
+  return rpp_host::guarded(pv ? pv->ctx : nullptr, "bpmi_ipa_prove_batch",
+                           [&] { return ipa_prove_batch_impl(pv, protocol, n_proofs, a, b, c, P, seeds, seed_off, ab, xs, LR, head, transcripts, cap, tr_off); });
 }
 
 int bpmi_ipa_batch_prover_last_ms(const bpmi_ipa_batch_prover *pv, double ms[4]) {
@@ -282,12 +251,9 @@ static int ipa_batch_prover_commit_batch_impl(bpmi_ipa_batch_prover *pv, uint64_
   if (const char *over = ipp_batch_error(pv->max_proofs, count)) return fail(ctx, BPMI_E_ARG, std::string(fn) + over);
   const auto wall0 = std::chrono::steady_clock::now();
   const u32 C = (u32)count, n = pv->n;
-  for (uint64_t i = 0; i < count * n; i++) {
-    if (a && !rp_scalar_reduced(a + 32 * i)) return fail(ctx, BPMI_E_ARG, std::string(fn) + "a[" + std::to_string(i) + "] is not below the group order");
-    if (b && !rp_scalar_reduced(b + 32 * i)) return fail(ctx, BPMI_E_ARG, std::string(fn) + "b[" + std::to_string(i) + "] is not below the group order");
-  }
-  if (t) for (uint64_t i = 0; i < count; i++)
-    if (!rp_scalar_reduced(t + 32 * i)) return fail(ctx, BPMI_E_ARG, std::string(fn) + "t[" + std::to_string(i) + "] is not below the group order");
+  for (int pass = 0; pass < 2; pass++)                   // a and b side by side, then t
+    if (const std::string bad = pass ? rpp_host::unreduced({{"t", t, count}}) : rpp_host::unreduced({{"a", a, count * n}, {"b", b, count * n}}); !bad.empty())
+      return fail(ctx, BPMI_E_ARG, fn + bad);
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const u32 T = (a ? n : 0u) + (b ? n : 0u) + (u_mode ? 1u : 0u);
   using rpp_host::up256;
@@ -296,18 +262,8 @@ static int ipa_batch_prover_commit_batch_impl(bpmi_ipa_batch_prover *pv, uint64_
   const size_t o_ain = take(a ? 32ull * C * n : 0), o_bin = take(b ? 32ull * C * n : 0), o_tin = take(t ? 32ull * C : 0);
   const size_t in_bytes = o;                                   // everything above is uploaded in one copy
   const size_t o_jsc = take(32ull * C * T), o_jout = take(144ull * C), o_pts = take(64ull * C);
-  if (o > pv->buf_bytes) {
-    if (pv->buf) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(pv->buf)); pv->buf = nullptr; pv->buf_bytes = 0; }
-    HIPCHK(ctx, hipMalloc(&pv->buf, o + o / 8));
-    pv->buf_bytes = o + o / 8;
-  }
-  const size_t pin_need = std::max(in_bytes, (size_t)(64ull * C));
-  if (pin_need > pv->pin_bytes) {
-    if (pv->pin) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipHostFree(pv->pin)); pv->pin = nullptr; pv->pin_bytes = 0; }
-    HIPCHK(ctx, hipHostMalloc(&pv->pin, pin_need + pin_need / 8, hipHostMallocDefault));
-    pv->pin_bytes = pin_need + pin_need / 8;
-  }
-  char *d = (char *)pv->buf, *hp = (char *)pv->pin;
+  if (int rc = pv->mem.grow(ctx, o, std::max(in_bytes, (size_t)(64ull * C)))) return rc;
+  char *d = (char *)pv->mem.buf, *hp = (char *)pv->mem.pin;
   if (a) memcpy(hp + o_ain, a, 32ull * C * n);
   if (b) memcpy(hp + o_bin, b, 32ull * C * n);
   if (t) memcpy(hp + o_tin, t, 32ull * C);
@@ -323,13 +279,8 @@ static int ipa_batch_prover_commit_batch_impl(bpmi_ipa_batch_prover *pv, uint64_
   if (NT == 256u) hipLaunchKernelGGL(ipp::k_ip_commit_scalars<256>, grid, dim3(256), 0, st, K);
   else if (NT == 512u) hipLaunchKernelGGL(ipp::k_ip_commit_scalars<512>, grid, dim3(512), 0, st, K);
   else hipLaunchKernelGGL(ipp::k_ip_commit_scalars<1024>, grid, dim3(1024), 0, st, K);
-  rpp::MsmJobs J;
-  J.njobs = C; J.ntypes = 1; J.T = T; J.bases = pv->cbases + ipp_commit_bases_offset(n, a != nullptr, b != nullptr); J.scalars = K.jsc; J.stride = T; J.out = (u32 *)(d + o_jout);
-  const rpp::Tab tab = rpp::Tab{pv->table, pv->tw, pv->wt, pv->bt};
-  const int gl = ipp_job_lanes_log2(n, count, ctx->opt_prover_job_lanes);
-  const dim3 mgrid((u32)((((uint64_t)C << gl) + 255) / 256));
-  if (gl == 6) hipLaunchKernelGGL(rpp::k_pv_msm<6>, mgrid, dim3(256), 0, st, J, tab);
-  else hipLaunchKernelGGL(rpp::k_pv_msm<4>, mgrid, dim3(256), 0, st, J, tab);
+  const rpp::MsmJobs J = {C, 1, T, pv->cbases + ipp_commit_bases_offset(n, a != nullptr, b != nullptr), K.jsc, T, (u32 *)(d + o_jout)};
+  rpp_host::launch_msm(st, J, rpp::Tab{pv->table, pv->tw, pv->wt, pv->bt}, ipp_job_lanes_log2(n, count, ctx->opt_prover_job_lanes));
   hipLaunchKernelGGL(rpp::k_pv_affine, dim3((C + 255u) / 256u), dim3(256), 0, st, (const u32 *)J.out, C, 1u, (u32 *)(d + o_pts), 1u, 0u, 0u);
   (void)hipEventRecord(pv->ev[1], st);
   hipError_t e = hipGetLastError();
@@ -342,11 +293,7 @@ static int ipa_batch_prover_commit_batch_impl(bpmi_ipa_batch_prover *pv, uint64_
   return BPMI_OK;
 }
 int bpmi_ipa_batch_prover_commit_batch(bpmi_ipa_batch_prover *pv, uint64_t count, const uint8_t *a, const uint8_t *b, int u_mode, const uint8_t *t, uint8_t *out) {
-  try {
-    return ipa_batch_prover_commit_batch_impl(pv, count, a, b, u_mode, t, out);
-  } catch (const std::bad_alloc &) {
-    return pv && pv->ctx ? fail(pv->ctx, BPMI_E_NOMEM, "bpmi_ipa_batch_prover_commit_batch: out of host memory") : BPMI_E_NOMEM;
-  }
+  return rpp_host::guarded(pv ? pv->ctx : nullptr, "bpmi_ipa_batch_prover_commit_batch", [&] { return ipa_batch_prover_commit_batch_impl(pv, count, a, b, u_mode, t, out); });
 }
 
 int bpmi_ipa_batch_prover_commit_last_ms(const bpmi_ipa_batch_prover *pv, double ms[2]) {

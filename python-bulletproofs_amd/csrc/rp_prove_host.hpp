@@ -13,23 +13,19 @@ struct bpmi_rp_prover {
   u32 nb = 0, m = 1;                           // bits per value, values per proof (m > 1: aggregated proofs)
   u32 *table = nullptr;                        // [(3 + 2n)][wt][bt] affine points
   u32 tw = 16, wt = 16, bt = 32768;            // table windows: tw bits, wt = ceil(256 / tw) per scalar, bt = 2^(tw-1) entries each
-  unsigned short *bases = nullptr;             // device: the base lists of every job kind (offsets below, in entries)
-  u32 off_S = 0, off_T = 0, off_P = 0, off_round = 0;
+  unsigned short *bases = nullptr;             // device: the base lists of every job kind (rpp_class_bases(n, n); rpp_off_*: where each starts)
   unsigned short *mixed_bases = nullptr;       // device: the base lists of every class of this capacity (bpmi_rp_prove_batch_mixed: made by its first call)
   rpp::sc x_ip;                                // mod_hash(b"&", q): the Protocol-1 challenge of an empty seed (the same for every proof)
   std::string ip_prefix;                       // "&&" str(x_ip) "&"
   unsigned char *d_ip_prefix = nullptr;
   u32 u_new[16];                               // x_ip u, affine words
-  void *buf = nullptr; size_t buf_bytes = 0;   // the batch's device arrays (grown on demand)
-  void *pin = nullptr; size_t pin_bytes = 0;   // page-locked staging of the inputs / the proofs
+  rpp_host::Buffers mem;                       // the batch's device arrays; page-locked staging of the inputs / the proofs
   hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // phase boundaries of a batch, created once with the prover
   hipEvent_t ev_chain[2] = {nullptr, nullptr};                                            // two halves of a batch: the last multi-scalar multiplication of each
   double last_ms[8] = {0};                     // device milliseconds of the last batch: blind+A/S | y,z+T | x+final+P_new | rounds | emit+copy | total
 };
 
 namespace rpp_host {
-
-static inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // decimal text of a 256-bit little-endian value
 static std::string decimal_of(const uint8_t le[32]) {
@@ -38,18 +34,6 @@ static std::string decimal_of(const uint8_t le[32]) {
   std::vector<uint8_t> dg;
   rpt::append_decimal(dg, v);
   return std::string((const char *)dg.data(), dg.size() - 1);
-}
-// base64 of a seed, written where it is needed (a batch encodes one seed per proof: no string per proof); returns the length
-static size_t b64_into(char *o, const uint8_t *p, size_t n) {
-  static const char T[] = "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789+/";
-  char *q = o;
-  for (size_t i = 0; i < n; i += 3) {
-    const uint32_t a = p[i], b = i + 1 < n ? p[i + 1] : 0, c = i + 2 < n ? p[i + 2] : 0;
-    const uint32_t v = (a << 16) | (b << 8) | c;
-    *q++ = T[v >> 18]; *q++ = T[(v >> 12) & 63];
-    *q++ = i + 1 < n ? T[(v >> 6) & 63] : '='; *q++ = i + 2 < n ? T[v & 63] : '=';
-  }
-  return (size_t)(q - o);
 }
 
 // The fixed-base tables of nb bases (basepts: nb x 64 bytes on the host), shared by the batched provers: the window bases 2^(tw k) base_b
@@ -87,6 +71,75 @@ static int build_tables(bpmi_ctx *ctx, const char *fn, const std::vector<uint8_t
   return rc;
 }
 
+// ---- what bpmi_rp_prove_batch and bpmi_rp_prove_batch_mixed (rp_prove_mixed_host.hpp) share: a call of the latter is the former's host
+// work once per class
+
+// The rpp::Batch of P proofs of shape g whose arrays sit at `at` in the device buffer d.  hs0: the base of hs_0 (3 + the generators the
+// tables were built over); p0: the call-wide index of proof 0
+static rpp::Batch make_batch(const bpmi_rp_prover *pv, char *d, const RppRegions &at, const RppGeom &g, u32 P, const RppStrides &stride, u32 hs0, u32 p0) {
+  rpp::Batch B;
+  memset(&B, 0, sizeof(B));
+  B.P = P; B.n = g.n; B.k = g.k; B.nb = pv->nb; B.m = g.m; B.hs0 = hs0; B.p0 = p0; B.table = rpp::Tab{pv->table, pv->tw, pv->wt, pv->bt};
+  B.dig0 = (const unsigned char *)(d + at.o_dig0); B.dig0_stride = stride.dig0_stride; B.dig0_len = (const u32 *)(d + at.o_dlen);
+  B.values = (const u32 *)(d + at.o_val); B.gammas = (const u32 *)(d + at.o_gam);
+  B.ip_prefix = pv->d_ip_prefix; B.ip_prefix_len = (u32)pv->ip_prefix.size(); B.x_ip = pv->x_ip;
+  memcpy(B.u_new, pv->u_new, 64);
+  B.tr = (unsigned char *)(d + at.o_tr); B.tr_stride = stride.tr_stride; B.tr_len = (u32 *)(d + at.o_trlen);
+  B.slr = (u32 *)(d + at.o_slr); B.alpha = (u32 *)(d + at.o_alpha); B.chal = (u32 *)(d + at.o_chal); B.tau = (u32 *)(d + at.o_tau); B.tsc = (u32 *)(d + at.o_tsc);
+  B.res = (u32 *)(d + at.o_res); B.xs = (u32 *)(d + at.o_xs); B.xr = (u32 *)(d + at.o_xr);
+  B.a = (u32 *)(d + at.o_a); B.b = (u32 *)(d + at.o_b); B.cg = (u32 *)(d + at.o_cg); B.hf = (u32 *)(d + at.o_hf);
+  B.jsc = (u32 *)(d + at.o_jsc); B.jout = (u32 *)(d + at.o_jout); B.pts = (u32 *)(d + at.o_pts);
+  return B;
+}
+
+// The inputs of P proofs of m values into the staging buffer hp (zeroed): base64(seed) || '&', which starts every range-proof transcript
+// (transcript.py:13-14), with its length; the values and blinding factors; the seeds' bytes at `seeds_at`; and the proofs' rows of the seed
+// and output offsets, soff / ooff (row P too: the next class's first, or the call's end).  seed0, out0: where the first seed and the first
+// proof sit in the call's seed and output bytes; fixed_bytes: a proof without its seed
+static void stage_inputs(char *hp, const RppRegions &at, const RppStrides &stride, u32 m, u32 P, const uint8_t *values, const uint8_t *gammas, const uint8_t *seeds,
+                         const uint64_t *seed_off, char *seeds_at, uint64_t *soff, uint64_t *ooff, uint64_t seed0, uint64_t out0, uint64_t fixed_bytes) {
+  for (u32 p = 0; p < P; p++) {
+    uint8_t *dg = (uint8_t *)hp + at.o_dig0 + (size_t)p * stride.dig0_stride;          // (stride.dig0_stride >= 4 ceil(len / 3) + 1)
+    const uint64_t sl = seed_off[p + 1] - seed_off[p];
+    size_t tl = rp::b64_encode(dg, seeds + seed_off[p], sl);
+    dg[tl++] = '&';
+    ((u32 *)(hp + at.o_dlen))[p] = (u32)tl;
+    soff[p] = seed0 + (seed_off[p] - seed_off[0]);
+    ooff[p] = out0;
+    out0 += fixed_bytes + sl;
+  }
+  soff[P] = seed0 + (seed_off[P] - seed_off[0]);
+  ooff[P] = out0;
+  memcpy(hp + at.o_val, values, 32ull * P * m);
+  memcpy(hp + at.o_gam, gammas, 32ull * P * m);
+  if (seed_off[P] > seed_off[0]) memcpy(seeds_at, seeds + seed_off[0], seed_off[P] - seed_off[0]);
+}
+
+// The end of a call whose kernels are queued on the prover's stream: the proofs (total_out bytes at d_out) go straight into the caller's
+// buffer when it is page-locked (bpmi_host_alloc: what BatchRangeProver hands in), else through the prover's staging buffer and one host
+// copy (18 MB for 2^14 64-bit proofs: 2-3 ms of a 27 ms batch); then the phases of bpmi_rp_prover_last_ms.  fn: "entry point: "
+static int finish_call(bpmi_rp_prover *pv, const char *fn, const char *d_out, size_t total_out, uint8_t *out) {
+  bpmi_ctx *ctx = pv->ctx;
+  hipStream_t st = ctx->stream;
+  hipEvent_t *ev = pv->ev;
+  (void)hipEventRecord(ev[5], st);
+  hipError_t e = hipGetLastError();
+  bool direct = false;
+  {
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, out) == hipSuccess && attr.type == hipMemoryTypeHost) direct = true;
+    else (void)hipGetLastError();                              // an ordinary host pointer is "invalid value" to the query
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(direct ? (void *)out : pv->mem.pin, d_out, total_out, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipEventRecord(ev[6], st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return fail(ctx, BPMI_E_HIP, std::string(fn) + hipGetErrorString(e));
+  if (!direct) memcpy(out, pv->mem.pin, total_out);
+  for (int i = 0; i < 6; i++) { float ms = 0; (void)hipEventElapsedTime(&ms, ev[i], ev[i + 1]); pv->last_ms[i] = ms; }
+  { float ms = 0; (void)hipEventElapsedTime(&ms, ev[0], ev[6]); pv->last_ms[6] = ms; }
+  return BPMI_OK;
+}
+
 }  // namespace rpp_host
 
 extern "C" {
@@ -98,8 +151,7 @@ void bpmi_rp_prover_destroy(bpmi_rp_prover *pv) {
   if (pv->bases) (void)hipFree(pv->bases);
   if (pv->mixed_bases) (void)hipFree(pv->mixed_bases);
   if (pv->d_ip_prefix) (void)hipFree(pv->d_ip_prefix);
-  if (pv->buf) (void)hipFree(pv->buf);
-  if (pv->pin) (void)hipHostFree(pv->pin);
+  pv->mem.release();
   for (auto e : pv->ev) if (e) (void)hipEventDestroy(e);
   for (auto e : pv->ev_chain) if (e) (void)hipEventDestroy(e);
   delete pv;
@@ -107,17 +159,11 @@ void bpmi_rp_prover_destroy(bpmi_rp_prover *pv) {
 
 static int rp_prover_create_impl(bpmi_ctx *ctx, uint32_t vbits, uint32_t m, const uint8_t g[64], const uint8_t h[64], const uint8_t u[64], const uint8_t *gs, const uint8_t *hs,
                                  bpmi_rp_prover **out, bpmi_rp_prover *&partial);
-// (the C ABI never throws: a failed host allocation inside -- the 64 (3 + 2n)-byte point list, the base lists, a std::string -- is BPMI_E_NOMEM)
 int bpmi_rp_prover_create_aggregated(bpmi_ctx *ctx, uint32_t nbits, uint32_t m, const uint8_t g[64], const uint8_t h[64], const uint8_t u[64], const uint8_t *gs,
                                      const uint8_t *hs, bpmi_rp_prover **out) {
   bpmi_rp_prover *partial = nullptr;
-  try {
-    return rp_prover_create_impl(ctx, nbits, m, g, h, u, gs, hs, out, partial);
-  } catch (const std::bad_alloc &) {
-    if (partial) bpmi_rp_prover_destroy(partial);
-    if (out) *out = nullptr;
-    return ctx ? fail(ctx, BPMI_E_NOMEM, "bpmi_rp_prover_create: out of host memory") : BPMI_E_NOMEM;
-  }
+  return rpp_host::guarded(ctx, "bpmi_rp_prover_create", [&] { return rp_prover_create_impl(ctx, nbits, m, g, h, u, gs, hs, out, partial); },
+                           [&] { if (partial) bpmi_rp_prover_destroy(partial); if (out) *out = nullptr; });
 }
 int bpmi_rp_prover_create(bpmi_ctx *ctx, uint32_t nbits, const uint8_t g[64], const uint8_t h[64], const uint8_t u[64], const uint8_t *gs, const uint8_t *hs,
                           bpmi_rp_prover **out) {
@@ -191,7 +237,6 @@ static int rp_prover_create_impl(bpmi_ctx *ctx, uint32_t vbits, uint32_t m, cons
   if (rc) return bail(rc);
   // the base lists of every job kind (rpp_plan)
   const std::vector<unsigned short> &bl = plan.bases;
-  pv->off_S = plan.off_S; pv->off_T = plan.off_T; pv->off_P = plan.off_P; pv->off_round = plan.off_round;
   e = hipMalloc(&pv->bases, 2 * bl.size());
   if (e == hipSuccess) e = hipMemcpy(pv->bases, bl.data(), 2 * bl.size(), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMalloc(&pv->d_ip_prefix, pv->ip_prefix.size() + 16);
@@ -204,27 +249,9 @@ static int rp_prover_create_impl(bpmi_ctx *ctx, uint32_t vbits, uint32_t m, cons
 
 uint64_t bpmi_rp_prove_batch_proof_bytes(const bpmi_rp_prover *pv, uint64_t seed_len) {
   if (!pv) return 0;
-  const uint64_t k = pv->k;
-  return 6 + 32 * (5 + k) + 33 * (6 + 2 * k) + 128 + 2 + seed_len + 2 + (pv->ctx->opt_prover_wire == 3 ? 32 * (6 + 2 * k) : 0);
+  return rpp_fixed_bytes(pv->k, pv->ctx->opt_prover_wire) + seed_len;
 }
 
-static int rp_prove_batch_impl(bpmi_rp_prover *pv, uint64_t n_proofs, const uint8_t *values, const uint8_t *gammas, const uint8_t *seeds, const uint64_t *seed_off,
-                               uint8_t *out, uint64_t cap, uint64_t *out_off);
-int bpmi_rp_prove_batch(bpmi_rp_prover *pv, uint64_t n_proofs, const uint8_t *values, const uint8_t *gammas, const uint8_t *seeds, const uint64_t *seed_off,
-                        uint8_t *out, uint64_t cap, uint64_t *out_off) {
-  try {
-    return rp_prove_batch_impl(pv, n_proofs, values, gammas, seeds, seed_off, out, cap, out_off);
-  } catch (const std::bad_alloc &) {
-    return pv && pv->ctx ? fail(pv->ctx, BPMI_E_NOMEM, "bpmi_rp_prove_batch: out of host memory") : BPMI_E_NOMEM;
-  }
-}
-// a 32-byte little-endian value below the group order?  (the kernels' mod-q arithmetic takes reduced operands: taux = ... + z^2 gamma)
-static bool rp_scalar_reduced(const uint8_t le[32]) {
-  static const uint8_t QLE[32] = {0x41, 0x41, 0x36, 0xD0, 0x8C, 0x5E, 0xD2, 0xBF, 0x3B, 0xA0, 0x48, 0xAF, 0xE6, 0xDC, 0xAE, 0xBA,
-                                  0xFE, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF, 0xFF};
-  for (int i = 31; i >= 0; i--) if (le[i] != QLE[i]) return le[i] < QLE[i];
-  return false;
-}
 static int rp_prove_batch_impl(bpmi_rp_prover *pv, uint64_t n_proofs, const uint8_t *values, const uint8_t *gammas, const uint8_t *seeds, const uint64_t *seed_off,
                                uint8_t *out, uint64_t cap, uint64_t *out_off) {
   if (!pv) return BPMI_E_ARG;
@@ -234,13 +261,11 @@ static int rp_prove_batch_impl(bpmi_rp_prover *pv, uint64_t n_proofs, const uint
   // the per-call caps come first: nothing of a batch beyond them is read or allocated
   if (const char *over = rpp_batch_error(pv->max_proofs, n_proofs)) return fail(ctx, BPMI_E_ARG, over);
   if (!seeds && seed_off[n_proofs] != seed_off[0]) return fail(ctx, BPMI_E_ARG, "null argument");
-  // the reference's prover takes ModP values: reduced by construction (/root/reference/src/utils/utils.py:24-27); raw bytes are checked here
-  for (uint64_t p = 0; p < n_proofs * pv->m; p++) {
-    if (!rp_scalar_reduced(values + 32 * p)) return fail(ctx, BPMI_E_ARG, "bpmi_rp_prove_batch: values[" + std::to_string(p) + "] is not below the group order");
-    if (!rp_scalar_reduced(gammas + 32 * p)) return fail(ctx, BPMI_E_ARG, "bpmi_rp_prove_batch: gammas[" + std::to_string(p) + "] is not below the group order");
-  }
+  if (const std::string bad = rpp_host::unreduced({{"values", values, n_proofs * pv->m}, {"gammas", gammas, n_proofs * pv->m}}); !bad.empty())
+    return fail(ctx, BPMI_E_ARG, "bpmi_rp_prove_batch: " + bad);
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  const u32 P = (u32)n_proofs, n = pv->n, k = pv->k, npt = 6 + 2 * k;
+  const RppGeom g = rpp_geom(pv->nb, pv->m);
+  const u32 P = (u32)n_proofs, n = g.n, k = g.k, npt = g.npt;
   const int wire_fmt = ctx->opt_prover_wire;                  // 2, or 3: with the points' y coordinates (bpmi_rp_prove_batch_proof_bytes counts them)
   // the proofs' seeds: base64(seed) || '&' starts every range-proof transcript (transcript.py:13-14)
   uint64_t max_seed = 0, total_out = 0;
@@ -254,62 +279,16 @@ static int rp_prove_batch_impl(bpmi_rp_prover *pv, uint64_t n_proofs, const uint
   }
   out_off[P] = total_out;
   if (total_out > cap) return fail(ctx, BPMI_E_ARG, "the output buffer is too small (bpmi_rp_prove_batch_proof_bytes per proof)");
-  const u32 dig0_stride = (u32)((((max_seed + 2) / 3) * 4 + 1 + 15) & ~15ull);
-  const u32 tr_stride = (u32)((std::max<uint64_t>(dig0_stride + 4 * 45 + 3 * 80, pv->ip_prefix.size() + (uint64_t)k * (90 + 80)) + 64 + 15) & ~15ull);
-  // ---- device layout
-  using rpp_host::up256;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += up256(bytes); return at; };
-  const size_t o_dig0 = take((size_t)P * dig0_stride), o_dlen = take(4ull * P), o_val = take(32ull * P * pv->m), o_gam = take(32ull * P * pv->m);
-  const size_t o_seeds = take(seed_off[P] - seed_off[0] + 16), o_soff = take(8ull * (P + 1)), o_ooff = take(8ull * (P + 1));
-  const size_t in_bytes = o;                                   // everything above is uploaded in one copy
-  const size_t o_tr = take((size_t)P * tr_stride), o_trlen = take(4ull * P);
-  const size_t o_slr = take(32ull * P * (2 * n + 1)), o_alpha = take(32ull * P), o_chal = take(128ull * P), o_tau = take(64ull * P), o_tsc = take(128ull * P);
-  const size_t o_res = take(160ull * P), o_xs = take(32ull * P * k), o_xr = take(64ull * P);
-  const size_t o_a = take(32ull * P * n), o_b = take(32ull * P * n), o_cg = take(32ull * P * n), o_hf = take(32ull * P * n);
-  const size_t o_jsc = take(32ull * P * (2 * n + 2)), o_jout = take(144ull * 2 * P), o_pts = take(64ull * P * npt);
-  const size_t o_out = take(total_out + 16);
-  if (o > pv->buf_bytes) {
-    if (pv->buf) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(pv->buf)); pv->buf = nullptr; pv->buf_bytes = 0; }
-    HIPCHK(ctx, hipMalloc(&pv->buf, o + o / 8));
-    pv->buf_bytes = o + o / 8;
-  }
-  const size_t pin_need = std::max(in_bytes, (size_t)total_out);      // (the output half is only used when `out` is pageable)
-  if (pin_need > pv->pin_bytes) {
-    if (pv->pin) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipHostFree(pv->pin)); pv->pin = nullptr; pv->pin_bytes = 0; }
-    HIPCHK(ctx, hipHostMalloc(&pv->pin, pin_need + pin_need / 8, hipHostMallocDefault));
-    pv->pin_bytes = pin_need + pin_need / 8;
-  }
-  char *d = (char *)pv->buf, *hp = (char *)pv->pin;
-  // ---- inputs into the staging buffer
-  memset(hp, 0, in_bytes);
-  for (u32 p = 0; p < P; p++) {
-    char *dg = hp + o_dig0 + (size_t)p * dig0_stride;                 // (dig0_stride >= 4 ceil(len / 3) + 1)
-    size_t tl = rpp_host::b64_into(dg, seeds + seed_off[p], seed_off[p + 1] - seed_off[p]);
-    dg[tl++] = '&';
-    ((u32 *)(hp + o_dlen))[p] = (u32)tl;
-    ((uint64_t *)(hp + o_soff))[p] = seed_off[p] - seed_off[0];
-    ((uint64_t *)(hp + o_ooff))[p] = out_off[p];
-  }
-  ((uint64_t *)(hp + o_soff))[P] = seed_off[P] - seed_off[0];
-  ((uint64_t *)(hp + o_ooff))[P] = out_off[P];
-  memcpy(hp + o_val, values, 32ull * P * pv->m);
-  memcpy(hp + o_gam, gammas, 32ull * P * pv->m);
-  if (seed_off[P] > seed_off[0]) memcpy(hp + o_seeds, seeds + seed_off[0], seed_off[P] - seed_off[0]);
+  const RppLayout L = rpp_layout(g, P, seed_off[P] - seed_off[0], max_seed, total_out, pv->ip_prefix.size());
+  if (int rc = pv->mem.grow(ctx, L.need, std::max(L.in_bytes, (size_t)total_out))) return rc;        // (the output half is only used when `out` is pageable)
+  char *d = (char *)pv->mem.buf, *hp = (char *)pv->mem.pin;
+  memset(hp, 0, L.in_bytes);
+  rpp_host::stage_inputs(hp, L, L, g.m, P, values, gammas, seeds, seed_off, hp + L.o_seeds, (uint64_t *)(hp + L.o_soff), (uint64_t *)(hp + L.o_ooff), 0, 0,
+                         rpp_fixed_bytes(k, wire_fmt));
   hipStream_t st = ctx->stream;
-  HIPCHK(ctx, hipMemcpyAsync(d, hp, in_bytes, hipMemcpyHostToDevice, st));
-  rpp::Batch B;
-  memset(&B, 0, sizeof(B));
-  B.P = P; B.n = n; B.k = k; B.nb = pv->nb; B.m = pv->m; B.hs0 = 3 + n; B.table = rpp::Tab{pv->table, pv->tw, pv->wt, pv->bt};
-  B.dig0 = (const unsigned char *)(d + o_dig0); B.dig0_stride = dig0_stride; B.dig0_len = (const u32 *)(d + o_dlen);
-  B.values = (const u32 *)(d + o_val); B.gammas = (const u32 *)(d + o_gam);
-  B.ip_prefix = pv->d_ip_prefix; B.ip_prefix_len = (u32)pv->ip_prefix.size(); B.x_ip = pv->x_ip;
-  memcpy(B.u_new, pv->u_new, 64);
-  B.tr = (unsigned char *)(d + o_tr); B.tr_stride = tr_stride; B.tr_len = (u32 *)(d + o_trlen);
-  B.slr = (u32 *)(d + o_slr); B.alpha = (u32 *)(d + o_alpha); B.chal = (u32 *)(d + o_chal); B.tau = (u32 *)(d + o_tau); B.tsc = (u32 *)(d + o_tsc);
-  B.res = (u32 *)(d + o_res); B.xs = (u32 *)(d + o_xs); B.xr = (u32 *)(d + o_xr);
-  B.a = (u32 *)(d + o_a); B.b = (u32 *)(d + o_b); B.cg = (u32 *)(d + o_cg); B.hf = (u32 *)(d + o_hf);
-  B.jsc = (u32 *)(d + o_jsc); B.jout = (u32 *)(d + o_jout); B.pts = (u32 *)(d + o_pts);
+  HIPCHK(ctx, hipMemcpyAsync(d, hp, L.in_bytes, hipMemcpyHostToDevice, st));
+  const rpp::Batch B = rpp_host::make_batch(pv, d, L, g, P, L, 3 + n, 0);
+  const u32 dig0_stride = L.dig0_stride, tr_stride = L.tr_stride;
   hipEvent_t *ev = pv->ev;
   auto blocks = [](uint64_t threads, u32 per) { return dim3((u32)((threads + per - 1) / per)); };
   // Round 6 experiment (option "prover_split", off): a large batch as TWO halves on the ctx's two lanes.  Between two multi-scalar
@@ -352,13 +331,8 @@ static int rp_prove_batch_impl(bpmi_rp_prover *pv, uint64_t n_proofs, const uint
     hipStream_t hs = h.st;
     const u32 Pc = H.P;
     auto msm = [&](u32 njobs, u32 ntypes, u32 T, u32 base_off, const u32 *scalars, u32 stride, int gl) {
-      rpp::MsmJobs J;
-      J.njobs = njobs; J.ntypes = ntypes; J.T = T; J.bases = pv->bases + base_off; J.scalars = scalars; J.stride = stride; J.out = H.jout;
-      const uint64_t threads = (uint64_t)njobs << gl;
       if (other) (void)hipStreamWaitEvent(hs, other, 0);
-      if (gl == 6) hipLaunchKernelGGL(rpp::k_pv_msm<6>, blocks(threads, 256), dim3(256), 0, hs, J, H.table);
-      else if (gl == 4) hipLaunchKernelGGL(rpp::k_pv_msm<4>, blocks(threads, 256), dim3(256), 0, hs, J, H.table);
-      else hipLaunchKernelGGL(rpp::k_pv_msm<1>, blocks(threads, 256), dim3(256), 0, hs, J, H.table);
+      rpp_host::launch_msm(hs, rpp::MsmJobs{njobs, ntypes, T, pv->bases + base_off, scalars, stride, H.jout}, H.table, gl);
       if (mine) (void)hipEventRecord(mine, hs);
     };
     auto affine = [&](u32 count, u32 per, u32 slot0, u32 stp) {
@@ -369,32 +343,32 @@ static int rp_prove_batch_impl(bpmi_rp_prover *pv, uint64_t n_proofs, const uint
       hipLaunchKernelGGL(rpp::k_pv_blind, blocks((uint64_t)Pc * (2 * n + 2), 256), dim3(256), 0, hs, H);
       hipLaunchKernelGGL(rpp::k_pv_commit_A, blocks((uint64_t)Pc * 16, 256), dim3(256), 0, hs, H, H.jout);
       affine(Pc, 1, PV_PT_A, 0);
-      msm(Pc, 1, 2 * n + 1, pv->off_S, H.slr, 2 * n + 1, rpp_job_lanes_log2(n, Pc, job_lanes));
+      msm(Pc, 1, 2 * n + 1, rpp_off_S(n), H.slr, 2 * n + 1, rpp_job_lanes_log2(n, Pc, job_lanes));
       affine(Pc, 1, PV_PT_S, 0);
       if (h.rec) (void)hipEventRecord(ev[1], hs);
     } else if (sidx == 1) {                              // y, z, tau1, tau2; t1, t2; T1, T2 (:60-67)
       hipLaunchKernelGGL(rpp::k_pv_chal_yz, blocks(Pc, 64), dim3(64), 0, hs, H);
       PV_WIDE(k_pv_poly, H);
-      msm(2 * Pc, 1, 2, pv->off_T, H.tsc, 2, 1);
+      msm(2 * Pc, 1, 2, rpp_off_T(n), H.tsc, 2, 1);
       affine(2 * Pc, 2, PV_PT_T1, 1);
       if (h.rec) (void)hipEventRecord(ev[2], hs);
     } else if (sidx == 2) {                              // x; l, r, t_hat, taux, mu; P_new (:68-90; inner_product_prover.py:33-37)
       hipLaunchKernelGGL(rpp::k_pv_final_chal, blocks(Pc, 64), dim3(64), 0, hs, H);
       PV_WIDE(k_pv_final_wide, H);
-      msm(Pc, 1, 2 * n + 1, pv->off_P, H.jsc, 2 * n + 1, rpp_job_lanes_log2(n, Pc, job_lanes));
+      msm(Pc, 1, 2 * n + 1, rpp_off_P(n), H.jsc, 2 * n + 1, rpp_job_lanes_log2(n, Pc, job_lanes));
       affine(Pc, 1, PV_PT_PNEW, 0);
       if (h.rec) (void)hipEventRecord(ev[3], hs);
       PV_WIDE(k_pv_round_wide, H, 0u, 1u);
     } else if (sidx < 3 + k) {                           // a round of Protocol 2 (inner_product_prover.py:94-110)
       const u32 r = sidx - 3;
-      msm(2 * Pc, 2, n + 1, pv->off_round + r * 2 * (n + 1), H.jsc, n + 1, rpp_job_lanes_log2(n, 2 * (uint64_t)Pc, job_lanes));
+      msm(2 * Pc, 2, n + 1, rpp_off_round(n, r), H.jsc, n + 1, rpp_job_lanes_log2(n, 2 * (uint64_t)Pc, job_lanes));
       affine(2 * Pc, 2, 6 + r, k);
       hipLaunchKernelGGL(rpp::k_pv_round_chal, blocks(Pc, 64), dim3(64), 0, hs, H, r);
       PV_WIDE(k_pv_round_wide, H, r, 0u);
     } else {
       if (h.rec) (void)hipEventRecord(ev[4], hs);
-      hipLaunchKernelGGL(rpp::k_pv_emit, blocks(Pc, 64), dim3(64), 0, hs, H, (const unsigned char *)(d + o_seeds), (const uint64_t *)(d + o_soff) + h.p0,
-                         (unsigned char *)(d + o_out), (const uint64_t *)(d + o_ooff) + h.p0, (u32)wire_fmt);
+      hipLaunchKernelGGL(rpp::k_pv_emit, blocks(Pc, 64), dim3(64), 0, hs, H, (const unsigned char *)(d + L.o_seeds), (const uint64_t *)(d + L.o_soff) + h.p0,
+                         (unsigned char *)(d + L.o_out), (const uint64_t *)(d + L.o_ooff) + h.p0, (u32)wire_fmt);
     }
   };
 #undef PV_WIDE
@@ -416,24 +390,11 @@ static int rp_prove_batch_impl(bpmi_rp_prover *pv, uint64_t n_proofs, const uint
     Half ha = make_half(0, P, st, true);
     for (u32 sidx = 0; sidx < nsteps; sidx++) step(ha, sidx, nullptr, nullptr);
   }
-  (void)hipEventRecord(ev[5], st);
-  hipError_t e = hipGetLastError();
-  // the proofs go straight into the caller's buffer when it is page-locked (bpmi_host_alloc: what BatchRangeProver hands in), else
-  // through the prover's staging buffer and one host copy (18 MB for 2^14 64-bit proofs: 2-3 ms of a 27 ms batch)
-  bool direct = false;
-  {
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, out) == hipSuccess && attr.type == hipMemoryTypeHost) direct = true;
-    else (void)hipGetLastError();                              // an ordinary host pointer is "invalid value" to the query
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(direct ? (void *)out : (void *)hp, d + o_out, total_out, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipEventRecord(ev[6], st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return fail(ctx, BPMI_E_HIP, std::string("bpmi_rp_prove_batch: ") + hipGetErrorString(e));
-  if (!direct) memcpy(out, hp, total_out);
-  for (int i = 0; i < 6; i++) { float ms = 0; (void)hipEventElapsedTime(&ms, ev[i], ev[i + 1]); pv->last_ms[i] = ms; }
-  { float ms = 0; (void)hipEventElapsedTime(&ms, ev[0], ev[6]); pv->last_ms[6] = ms; }
-  return BPMI_OK;
+  return rpp_host::finish_call(pv, "bpmi_rp_prove_batch: ", d + L.o_out, total_out, out);
+}
+int bpmi_rp_prove_batch(bpmi_rp_prover *pv, uint64_t n_proofs, const uint8_t *values, const uint8_t *gammas, const uint8_t *seeds, const uint64_t *seed_off,
+                        uint8_t *out, uint64_t cap, uint64_t *out_off) {
+  return rpp_host::guarded(pv ? pv->ctx : nullptr, "bpmi_rp_prove_batch", [&] { return rp_prove_batch_impl(pv, n_proofs, values, gammas, seeds, seed_off, out, cap, out_off); });
 }
 
 // out[i] = values[i] g + gammas[i] h from the prover's tables: the pairs laid out as the scalars of count two-term jobs over the base
@@ -444,35 +405,21 @@ static int rp_prover_commit_batch_impl(bpmi_rp_prover *pv, uint64_t count, const
   if (count == 0) return BPMI_OK;
   if (!values || !gammas || !out) return fail(ctx, BPMI_E_ARG, "null argument");
   if (count > PROVER_COMMIT_MAX) return fail(ctx, BPMI_E_ARG, "at most 2^24 commitments per call");
-  for (uint64_t i = 0; i < count; i++) {
-    if (!rp_scalar_reduced(values + 32 * i)) return fail(ctx, BPMI_E_ARG, "bpmi_rp_prover_commit_batch: values[" + std::to_string(i) + "] is not below the group order");
-    if (!rp_scalar_reduced(gammas + 32 * i)) return fail(ctx, BPMI_E_ARG, "bpmi_rp_prover_commit_batch: gammas[" + std::to_string(i) + "] is not below the group order");
-  }
+  if (const std::string bad = rpp_host::unreduced({{"values", values, count}, {"gammas", gammas, count}}); !bad.empty())
+    return fail(ctx, BPMI_E_ARG, "bpmi_rp_prover_commit_batch: " + bad);
   HIPCHK(ctx, hipSetDevice(ctx->device));
   using rpp_host::up256;
   const u32 C = (u32)count;
   const size_t o_val = 0, o_gam = up256(32ull * C), in_bytes = o_gam + up256(32ull * C);
   const size_t o_jsc = in_bytes, o_jout = o_jsc + up256(64ull * C), o_pts = o_jout + up256(144ull * C), need = o_pts + up256(64ull * C);
-  if (need > pv->buf_bytes) {
-    if (pv->buf) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(pv->buf)); pv->buf = nullptr; pv->buf_bytes = 0; }
-    HIPCHK(ctx, hipMalloc(&pv->buf, need + need / 8));
-    pv->buf_bytes = need + need / 8;
-  }
-  const size_t pin_need = std::max(in_bytes, (size_t)(64ull * C));
-  if (pin_need > pv->pin_bytes) {
-    if (pv->pin) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipHostFree(pv->pin)); pv->pin = nullptr; pv->pin_bytes = 0; }
-    HIPCHK(ctx, hipHostMalloc(&pv->pin, pin_need + pin_need / 8, hipHostMallocDefault));
-    pv->pin_bytes = pin_need + pin_need / 8;
-  }
-  char *d = (char *)pv->buf, *hp = (char *)pv->pin;
+  if (int rc = pv->mem.grow(ctx, need, std::max(in_bytes, (size_t)(64ull * C)))) return rc;
+  char *d = (char *)pv->mem.buf, *hp = (char *)pv->mem.pin;
   hipStream_t st = ctx->stream;
   memcpy(hp + o_val, values, 32ull * C);
   memcpy(hp + o_gam, gammas, 32ull * C);
   HIPCHK(ctx, hipMemcpyAsync(d, hp, in_bytes, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(rpp::k_pv_commit_pairs, dim3((2u * C + 255u) / 256u), dim3(256), 0, st, (const u32 *)(d + o_val), (const u32 *)(d + o_gam), C, (u32 *)(d + o_jsc));
-  rpp::MsmJobs J;
-  J.njobs = C; J.ntypes = 1; J.T = 2; J.bases = pv->bases + pv->off_T; J.scalars = (const u32 *)(d + o_jsc); J.stride = 2; J.out = (u32 *)(d + o_jout);
-  hipLaunchKernelGGL(rpp::k_pv_msm<1>, dim3((u32)((2ull * C + 255) / 256)), dim3(256), 0, st, J, rpp::Tab{pv->table, pv->tw, pv->wt, pv->bt});
+  rpp_host::launch_msm(st, rpp::MsmJobs{C, 1, 2, pv->bases + rpp_off_T(pv->n), (const u32 *)(d + o_jsc), 2, (u32 *)(d + o_jout)}, rpp::Tab{pv->table, pv->tw, pv->wt, pv->bt}, 1);
   hipLaunchKernelGGL(rpp::k_pv_affine, dim3((C + 255u) / 256u), dim3(256), 0, st, (const u32 *)(d + o_jout), C, 1u, (u32 *)(d + o_pts), 1u, 0u, 0u);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(hp, d + o_pts, 64ull * C, hipMemcpyDeviceToHost, st);
@@ -482,11 +429,7 @@ static int rp_prover_commit_batch_impl(bpmi_rp_prover *pv, uint64_t count, const
   return BPMI_OK;
 }
 int bpmi_rp_prover_commit_batch(bpmi_rp_prover *pv, uint64_t count, const uint8_t *values, const uint8_t *gammas, uint8_t *out) {
-  try {
-    return rp_prover_commit_batch_impl(pv, count, values, gammas, out);
-  } catch (const std::bad_alloc &) {
-    return pv && pv->ctx ? fail(pv->ctx, BPMI_E_NOMEM, "bpmi_rp_prover_commit_batch: out of host memory") : BPMI_E_NOMEM;
-  }
+  return rpp_host::guarded(pv ? pv->ctx : nullptr, "bpmi_rp_prover_commit_batch", [&] { return rp_prover_commit_batch_impl(pv, count, values, gammas, out); });
 }
 
 int bpmi_rp_prover_last_ms(const bpmi_rp_prover *pv, double ms[7]) {

@@ -10,9 +10,7 @@ extern "C" {
 
 uint64_t bpmi_rp_prove_batch_proof_bytes_class(const bpmi_rp_prover *pv, uint32_t m, uint64_t seed_len) {
   if (!pv || m < 1 || (m & (m - 1)) || m > pv->m || (uint64_t)pv->nb * m < 2) return 0;
-  u32 k = 0;
-  while ((1u << k) < pv->nb * m) k++;
-  return rppm_fixed_bytes(k, pv->ctx->opt_prover_wire) + seed_len;
+  return rpp_fixed_bytes(rpp_geom(pv->nb, m).k, pv->ctx->opt_prover_wire) + seed_len;
 }
 
 static int rp_prove_batch_mixed_impl(bpmi_rp_prover *pv, uint32_t n_classes, const bpmi_rp_prove_class *classes, uint8_t *out, uint64_t cap, uint64_t *out_off) {
@@ -45,13 +43,10 @@ static int rp_prove_batch_mixed_impl(bpmi_rp_prover *pv, uint32_t n_classes, con
   const RppmPlan plan = rpp_mixed_plan(pv->nb, pv->m, pv->tw, n_classes, in.data(), wire_fmt, ctx->opt_prover_job_lanes, pv->ip_prefix.size());
   if (plan.err) return fail(ctx, plan.err, fn + plan.msg);
   if (plan.total_out > cap) return fail(ctx, BPMI_E_ARG, std::string(fn) + "the output buffer is too small (bpmi_rp_prove_batch_proof_bytes_class per proof)");
-  // the reference's prover takes ModP values: reduced by construction (/root/reference/src/utils/utils.py:24-27); raw bytes are checked here
   for (u32 c = 0; c < n_classes; c++) {
     const bpmi_rp_prove_class &k = classes[c];
-    for (uint64_t p = 0; p < k.n_proofs * k.m; p++) {
-      if (!rp_scalar_reduced(k.values + 32 * p)) return fail(ctx, BPMI_E_ARG, std::string(fn) + "class " + std::to_string(c) + ": values[" + std::to_string(p) + "] is not below the group order");
-      if (!rp_scalar_reduced(k.gammas + 32 * p)) return fail(ctx, BPMI_E_ARG, std::string(fn) + "class " + std::to_string(c) + ": gammas[" + std::to_string(p) + "] is not below the group order");
-    }
+    if (const std::string bad = rpp_host::unreduced({{"values", k.values, k.n_proofs * k.m}, {"gammas", k.gammas, k.n_proofs * k.m}}); !bad.empty())
+      return fail(ctx, BPMI_E_ARG, std::string(fn) + "class " + std::to_string(c) + ": " + bad);
   }
   HIPCHK(ctx, hipSetDevice(ctx->device));
   // the base lists of every class of this capacity, once per prover
@@ -68,19 +63,9 @@ static int rp_prove_batch_mixed_impl(bpmi_rp_prover *pv, uint32_t n_classes, con
     if (e != hipSuccess) { (void)hipFree(dev); return fail(ctx, BPMI_E_HIP, std::string(fn) + hipGetErrorString(e)); }
     pv->mixed_bases = dev;
   }
-  if (plan.need > pv->buf_bytes) {
-    if (pv->buf) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipFree(pv->buf)); pv->buf = nullptr; pv->buf_bytes = 0; }
-    HIPCHK(ctx, hipMalloc(&pv->buf, plan.need + plan.need / 8));
-    pv->buf_bytes = plan.need + plan.need / 8;
-  }
   const size_t total_out = (size_t)plan.total_out, in_bytes = plan.in_bytes;
-  const size_t pin_need = std::max(in_bytes, total_out);        // (the output half is only used when `out` is pageable)
-  if (pin_need > pv->pin_bytes) {
-    if (pv->pin) { HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); HIPCHK(ctx, hipHostFree(pv->pin)); pv->pin = nullptr; pv->pin_bytes = 0; }
-    HIPCHK(ctx, hipHostMalloc(&pv->pin, pin_need + pin_need / 8, hipHostMallocDefault));
-    pv->pin_bytes = pin_need + pin_need / 8;
-  }
-  char *d = (char *)pv->buf, *hp = (char *)pv->pin;
+  if (int rc = pv->mem.grow(ctx, plan.need, std::max(in_bytes, total_out))) return rc;        // (the output half is only used when `out` is pageable)
+  char *d = (char *)pv->mem.buf, *hp = (char *)pv->mem.pin;
   // ---- every class's inputs and the call's device tables into the staging buffer
   memset(hp, 0, in_bytes);
   uint64_t *soff = (uint64_t *)(hp + plan.o_soff), *ooff = (uint64_t *)(hp + plan.o_ooff);
@@ -88,33 +73,9 @@ static int rp_prove_batch_mixed_impl(bpmi_rp_prover *pv, uint32_t n_classes, con
   for (u32 c = 0; c < n_classes; c++) {
     const bpmi_rp_prove_class &k = classes[c];
     const RppmClass &q = plan.cls[c];
-    const u32 P = (u32)q.count;
-    uint64_t at = q.out_at;
-    for (u32 p = 0; p < P; p++) {
-      char *dg = hp + q.o_dig0 + (size_t)p * q.dig0_stride;            // (dig0_stride >= 4 ceil(len / 3) + 1)
-      const uint64_t sl = k.seed_off[p + 1] - k.seed_off[p];
-      size_t tl = rpp_host::b64_into(dg, k.seeds + k.seed_off[p], sl);
-      dg[tl++] = '&';
-      ((u32 *)(hp + q.o_dlen))[p] = (u32)tl;
-      soff[q.first + p] = q.seed_at + (k.seed_off[p] - k.seed_off[0]);
-      ooff[q.first + p] = at;
-      at += q.fixed_bytes + sl;
-    }
-    memcpy(hp + q.o_val, k.values, 32ull * P * q.m);
-    memcpy(hp + q.o_gam, k.gammas, 32ull * P * q.m);
-    if (in[c].seed_total) memcpy(hp + plan.o_seeds + q.seed_at, k.seeds + k.seed_off[0], in[c].seed_total);
-    rpp::Batch B;
-    memset(&B, 0, sizeof(B));
-    B.P = P; B.n = q.n; B.k = q.k; B.nb = pv->nb; B.m = q.m; B.hs0 = 3 + pv->n; B.p0 = (u32)q.first; B.table = tab;
-    B.dig0 = (const unsigned char *)(d + q.o_dig0); B.dig0_stride = q.dig0_stride; B.dig0_len = (const u32 *)(d + q.o_dlen);
-    B.values = (const u32 *)(d + q.o_val); B.gammas = (const u32 *)(d + q.o_gam);
-    B.ip_prefix = pv->d_ip_prefix; B.ip_prefix_len = (u32)pv->ip_prefix.size(); B.x_ip = pv->x_ip;
-    memcpy(B.u_new, pv->u_new, 64);
-    B.tr = (unsigned char *)(d + q.o_tr); B.tr_stride = q.tr_stride; B.tr_len = (u32 *)(d + q.o_trlen);
-    B.slr = (u32 *)(d + q.o_slr); B.alpha = (u32 *)(d + q.o_alpha); B.chal = (u32 *)(d + q.o_chal); B.tau = (u32 *)(d + q.o_tau); B.tsc = (u32 *)(d + q.o_tsc);
-    B.res = (u32 *)(d + q.o_res); B.xs = (u32 *)(d + q.o_xs); B.xr = (u32 *)(d + q.o_xr);
-    B.a = (u32 *)(d + q.o_a); B.b = (u32 *)(d + q.o_b); B.cg = (u32 *)(d + q.o_cg); B.hf = (u32 *)(d + q.o_hf);
-    B.jsc = (u32 *)(d + q.o_jsc); B.jout = (u32 *)(d + q.o_jout); B.pts = (u32 *)(d + q.o_pts);
+    rpp_host::stage_inputs(hp, q, q, q.m, (u32)q.count, k.values, k.gammas, k.seeds, k.seed_off, hp + plan.o_seeds + q.seed_at, soff + q.first, ooff + q.first, q.seed_at,
+                           q.out_at, q.fixed_bytes);
+    const rpp::Batch B = rpp_host::make_batch(pv, d, q, q, (u32)q.count, q, 3 + pv->n, (u32)q.first);
     memcpy(hp + plan.o_batch + (size_t)RPPM_BATCH_SLOT * c, &B, sizeof(B));
     for (u32 s = 0; s + 1 < plan.nsteps; s++) {
       const RppmJobs &j = plan.jobs[(size_t)s * n_classes + c];
@@ -126,8 +87,6 @@ static int rp_prove_batch_mixed_impl(bpmi_rp_prover *pv, uint32_t n_classes, con
       memcpy(hp + plan.o_jobs + (size_t)RPPM_JOBS_SLOT * ((size_t)s * n_classes + c), &J, sizeof(J));
     }
   }
-  soff[plan.n_proofs] = plan.seed_bytes;
-  ooff[plan.n_proofs] = plan.total_out;
   if (!plan.units.empty()) memcpy(hp + plan.o_units, plan.units.data(), sizeof(RppmUnit) * plan.units.size());
   hipStream_t st = ctx->stream;
   HIPCHK(ctx, hipMemcpyAsync(d, hp, in_bytes, hipMemcpyHostToDevice, st));
@@ -173,33 +132,15 @@ static int rp_prove_batch_mixed_impl(bpmi_rp_prover *pv, uint32_t n_classes, con
     }
 #undef PVM_WIDE
   }
-  (void)hipEventRecord(ev[5], st);
-  hipError_t e = hipGetLastError();
-  bool direct = false;                                           // (as bpmi_rp_prove_batch: straight into a page-locked `out`)
-  {
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, out) == hipSuccess && attr.type == hipMemoryTypeHost) direct = true;
-    else (void)hipGetLastError();
-  }
   // the output offsets leave the staging buffer before the proofs may land in it
-  std::vector<uint64_t> offs(ooff, ooff + plan.n_proofs + 1);
-  if (e == hipSuccess) e = hipMemcpyAsync(direct ? (void *)out : (void *)hp, d + plan.o_out, total_out, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipEventRecord(ev[6], st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return fail(ctx, BPMI_E_HIP, std::string(fn) + hipGetErrorString(e));
-  if (!direct) memcpy(out, hp, total_out);
+  const std::vector<uint64_t> offs(ooff, ooff + plan.n_proofs + 1);
+  if (int rc = rpp_host::finish_call(pv, fn, d + plan.o_out, total_out, out)) return rc;
   memcpy(out_off, offs.data(), 8 * offs.size());
-  for (int i = 0; i < 6; i++) { float ms = 0; (void)hipEventElapsedTime(&ms, ev[i], ev[i + 1]); pv->last_ms[i] = ms; }
-  { float ms = 0; (void)hipEventElapsedTime(&ms, ev[0], ev[6]); pv->last_ms[6] = ms; }
   return BPMI_OK;
 }
 
 int bpmi_rp_prove_batch_mixed(bpmi_rp_prover *pv, uint32_t n_classes, const bpmi_rp_prove_class *classes, uint8_t *out, uint64_t cap, uint64_t *out_off) {
-  try {
-    return rp_prove_batch_mixed_impl(pv, n_classes, classes, out, cap, out_off);
-  } catch (const std::bad_alloc &) {
-    return pv && pv->ctx ? fail(pv->ctx, BPMI_E_NOMEM, "bpmi_rp_prove_batch_mixed: out of host memory") : BPMI_E_NOMEM;
-  }
+  return rpp_host::guarded(pv ? pv->ctx : nullptr, "bpmi_rp_prove_batch_mixed", [&] { return rp_prove_batch_mixed_impl(pv, n_classes, classes, out, cap, out_off); });
 }
 
 }  // extern "C"

@@ -13,35 +13,6 @@
 
 #define RPPM_MAX_CLASSES 64u
 
-// The base lists of a class of n_c elements under a capacity of N (n_c <= N): rpp_plan's lists with gs_i at base 3 + i and hs_i at
-// base 3 + N + i.  rpp_class_bases(n, n) is rpp_plan(..).bases entry for entry; the offsets are rpp_plan's, functions of n_c alone:
-// S at 0, T at 2n + 1, P_new at 2n + 3, round r at 4n + 4 + r 2 (n + 1).
-static inline std::vector<unsigned short> rpp_class_bases(u32 n, u32 N) {
-  u32 k = 0;
-  while ((1u << k) < n) k++;
-  std::vector<unsigned short> bl;
-  bl.reserve((size_t)(2 * (2 * n + 1) + 2) + (size_t)k * 2 * (n + 1));
-  for (int pass = 0; pass < 2; pass++) {                   // S: .., h;  T: g, h;  P_new: .., u
-    for (u32 i = 0; i < n; i++) bl.push_back((unsigned short)(3 + i));
-    for (u32 i = 0; i < n; i++) bl.push_back((unsigned short)(3 + N + i));
-    bl.push_back(pass == 0 ? 1 : 2);
-    if (pass == 0) { bl.push_back(0); bl.push_back(1); }
-  }
-  for (u32 r = 0; r < k; r++) {
-    const u32 len = n >> r, half = len >> 1;
-    for (int side = 0; side < 2; side++) {                 // 0: L, 1: R
-      for (u32 j = 0; j < n; j++) if (((j & (len - 1)) >= half) == (side == 0)) bl.push_back((unsigned short)(3 + j));
-      for (u32 j = 0; j < n; j++) if (((j & (len - 1)) < half) == (side == 0)) bl.push_back((unsigned short)(3 + N + j));
-      bl.push_back(2);
-    }
-  }
-  return bl;
-}
-static inline size_t rpp_class_bases_len(u32 n) {
-  u32 k = 0;
-  while ((1u << k) < n) k++;
-  return (size_t)(4 * n + 4) + (size_t)k * 2 * (n + 1);
-}
 // The lists of EVERY class of a capacity in one array, cached on the prover: class m = 2^e (nbits m >= 2) at entry
 // rpp_capacity_bases_off(nbits, M, m); the whole array has rpp_capacity_bases_off(nbits, M, 2 M) entries (at most 53 000)
 static inline size_t rpp_capacity_bases_off(u32 nbits, u32 M, u32 m) {
@@ -72,14 +43,9 @@ struct RppmLaunch {
 // a class's jobs of a step's multi-scalar multiplication (rpp::MsmJobs without the pointers)
 struct RppmJobs { u32 njobs = 0, ntypes = 0, T = 0, stride = 0, base_off = 0, from_slr = 0, from_tsc = 0; };
 
-struct RppmClass {
-  u32 m = 0, n = 0, k = 0, NT = 0, per_block = 0, npt = 0;
+struct RppmClass : RppGeom, RppStrides, RppRegions {   // RppRegions: its arrays in the prover's device buffer
   uint64_t count = 0, first = 0;                 // proofs; the call-wide index of proof 0 (class-major in the caller's order)
-  u32 dig0_stride = 0, tr_stride = 0;
   size_t bases_off = 0;                          // its lists in the capacity's array (entries)
-  // regions, in bytes from the start of the prover's device buffer.  Inputs (uploaded): dig0, dlen, val, gam.  Scratch: the rest.
-  size_t o_dig0 = 0, o_dlen = 0, o_val = 0, o_gam = 0;
-  size_t o_tr = 0, o_trlen = 0, o_slr = 0, o_alpha = 0, o_chal = 0, o_tau = 0, o_tsc = 0, o_res = 0, o_xs = 0, o_xr = 0, o_a = 0, o_b = 0, o_cg = 0, o_hf = 0, o_jsc = 0, o_jout = 0, o_pts = 0;
   size_t seed_at = 0;                            // its seeds inside the call's seed bytes
   uint64_t out_at = 0, out_bytes = 0;            // its slice of the output
   uint64_t fixed_bytes = 0;                      // a proof without its seed
@@ -101,7 +67,6 @@ struct RppmPlan {
 #define RPPM_JOBS_SLOT 48u                       // bytes of an rpp::MsmJobs
 
 static inline RppmPlan rppm_error(const std::string &msg) { RppmPlan p; p.err = BPMI_E_ARG; p.msg = msg; return p; }
-static inline uint64_t rppm_fixed_bytes(u32 k, int wire_fmt) { return 6 + 32 * (5 + (uint64_t)k) + 33 * (6 + 2 * (uint64_t)k) + 128 + 2 + 2 + (wire_fmt == 3 ? 32 * (6 + 2 * (uint64_t)k) : 0); }
 
 // tw: the window bits of the prover's tables (recorded: one width for every class); wire_fmt: option "prover_wire_format"; job_lanes:
 // option "prover_job_lanes"; ip_prefix_len: bytes of "&&" str(x_ip) "&", which start every Protocol-2 transcript (the prover's own; 81: the
@@ -142,30 +107,24 @@ static inline RppmPlan rpp_mixed_plan(uint32_t nbits, uint32_t M, u32 tw, uint32
   p.nb = nbits; p.M = M; p.N = nbits * M; p.tw = tw;
   p.cls.resize(n_classes);
   p.n_proofs = proofs;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
+  RppTake take;
   // ---- classes: geometry, inputs
   for (u32 c = 0; c < n_classes; c++) {
     const RppmClassIn &k = classes[c];
     RppmClass &q = p.cls[c];
-    q.m = k.m; q.n = nbits * k.m;                                // rpp_plan's rules (without its base lists: a call plans up to 64 classes)
-    while ((1u << q.k) < q.n) q.k++;
-    q.NT = q.n <= 256u ? 256u : q.n; q.per_block = q.NT / q.n; q.npt = 6 + 2 * q.k;
+    static_cast<RppGeom &>(q) = rpp_geom(nbits, k.m);
     q.count = k.count;
     q.first = c ? p.cls[c - 1].first + p.cls[c - 1].count : 0;
-    q.dig0_stride = (u32)((((k.seed_max + 2) / 3) * 4 + 1 + 15) & ~15ull);
-    const uint64_t tr_a = (uint64_t)q.dig0_stride + 4 * 45 + 3 * 80, tr_b = ip_prefix_len + (uint64_t)q.k * (90 + 80);
-    q.tr_stride = (u32)(((tr_a > tr_b ? tr_a : tr_b) + 64 + 15) & ~15ull);
+    static_cast<RppStrides &>(q) = rpp_strides(k.seed_max, q.k, ip_prefix_len);
     q.bases_off = rpp_capacity_bases_off(nbits, M, k.m);
     q.seed_at = p.seed_bytes;
     p.seed_bytes += k.seed_total;
-    q.fixed_bytes = rppm_fixed_bytes(q.k, wire_fmt);
+    q.fixed_bytes = rpp_fixed_bytes(q.k, wire_fmt);
     q.out_at = p.total_out;
     q.out_bytes = q.count * q.fixed_bytes + k.seed_total;
     p.total_out += q.out_bytes;
     if (q.k > p.k_max) p.k_max = q.k;
-    const size_t P = (size_t)q.count;
-    q.o_dig0 = take(P * q.dig0_stride); q.o_dlen = take(4 * P); q.o_val = take(32 * P * q.m); q.o_gam = take(32 * P * q.m);
+    rpp_take_inputs(q, take, q, (size_t)q.count, q);
   }
   p.nsteps = n_classes ? 4 + p.k_max : 0;
   // ---- steps: the launches and their units
@@ -218,17 +177,17 @@ static inline RppmPlan rpp_mixed_plan(uint32_t nbits, uint32_t M, u32 tw, uint32
     simple(RPPM_BLIND, 0, 256, [&](u32 c) { return ceil_div(p.cls[c].count * (2 * p.cls[c].n + 2), 256); });
     simple(RPPM_COMMIT_A, 0, 256, [&](u32 c) { return ceil_div(p.cls[c].count * 16, 256); });
     affine(0, 1, 2 /* PV_PT_A */, 0, 0, all);
-    msm(0, [&](u32 c, RppmJobs &j) { const RppmClass &q = p.cls[c]; j.njobs = (u32)q.count; j.ntypes = 1; j.T = 2 * q.n + 1; j.stride = 2 * q.n + 1; j.base_off = 0; j.from_slr = 1; }, 0);
+    msm(0, [&](u32 c, RppmJobs &j) { const RppmClass &q = p.cls[c]; j.njobs = (u32)q.count; j.ntypes = 1; j.T = 2 * q.n + 1; j.stride = 2 * q.n + 1; j.base_off = rpp_off_S(q.n); j.from_slr = 1; }, 0);
     affine(0, 1, 3 /* PV_PT_S */, 0, 0, all);
     // step 1: y, z, T1, T2
     simple(RPPM_CHAL_YZ, 1, 64, chain);
     wide(RPPM_POLY, 1, all);
-    msm(1, [&](u32 c, RppmJobs &j) { const RppmClass &q = p.cls[c]; j.njobs = 2 * (u32)q.count; j.ntypes = 1; j.T = 2; j.stride = 2; j.base_off = 2 * q.n + 1; j.from_tsc = 1; }, 1);
+    msm(1, [&](u32 c, RppmJobs &j) { const RppmClass &q = p.cls[c]; j.njobs = 2 * (u32)q.count; j.ntypes = 1; j.T = 2; j.stride = 2; j.base_off = rpp_off_T(q.n); j.from_tsc = 1; }, 1);
     affine(1, 2, 0 /* PV_PT_T1 */, 1, 0, all);
     // step 2: x, the vectors, P_new, the scalars of round 0
     simple(RPPM_FINAL_CHAL, 2, 64, chain);
     wide(RPPM_FINAL_WIDE, 2, all);
-    msm(2, [&](u32 c, RppmJobs &j) { const RppmClass &q = p.cls[c]; j.njobs = (u32)q.count; j.ntypes = 1; j.T = 2 * q.n + 1; j.stride = 2 * q.n + 1; j.base_off = 2 * q.n + 3; }, 0);
+    msm(2, [&](u32 c, RppmJobs &j) { const RppmClass &q = p.cls[c]; j.njobs = (u32)q.count; j.ntypes = 1; j.T = 2 * q.n + 1; j.stride = 2 * q.n + 1; j.base_off = rpp_off_P(q.n); }, 0);
     affine(2, 1, 5 /* PV_PT_PNEW */, 0, 0, all);
     wide(RPPM_ROUND_WIDE, 2, all, 0, 1);
     // steps 3 .. 2 + k_max: round r for the classes with k_c > r
@@ -237,7 +196,7 @@ static inline RppmPlan rpp_mixed_plan(uint32_t nbits, uint32_t M, u32 tw, uint32
       msm(3 + r, [&](u32 c, RppmJobs &j) {
         const RppmClass &q = p.cls[c];
         if (q.k <= r) return;
-        j.njobs = 2 * (u32)q.count; j.ntypes = 2; j.T = q.n + 1; j.stride = q.n + 1; j.base_off = 4 * q.n + 4 + r * 2 * (q.n + 1);
+        j.njobs = 2 * (u32)q.count; j.ntypes = 2; j.T = q.n + 1; j.stride = q.n + 1; j.base_off = rpp_off_round(q.n, r);
       }, 0);
       affine(3 + r, 2, 6 + r, 0, 1, in_round);
       simple(RPPM_ROUND_CHAL, 3 + r, 64, [&](u32 c) { return in_round(c) ? chain(c) : 0u; }, r, 0);
@@ -253,17 +212,9 @@ static inline RppmPlan rpp_mixed_plan(uint32_t nbits, uint32_t M, u32 tw, uint32
   p.o_batch = take((size_t)RPPM_BATCH_SLOT * n_classes);
   p.o_jobs = take((size_t)RPPM_JOBS_SLOT * p.jobs.size());
   p.o_units = take(sizeof(RppmUnit) * p.units.size());
-  p.in_bytes = o;
-  for (u32 c = 0; c < n_classes; c++) {
-    RppmClass &q = p.cls[c];
-    const size_t P = (size_t)q.count, n = q.n, k = q.k;
-    q.o_tr = take(P * q.tr_stride); q.o_trlen = take(4 * P);
-    q.o_slr = take(32 * P * (2 * n + 1)); q.o_alpha = take(32 * P); q.o_chal = take(128 * P); q.o_tau = take(64 * P); q.o_tsc = take(128 * P);
-    q.o_res = take(160 * P); q.o_xs = take(32 * P * k); q.o_xr = take(64 * P);
-    q.o_a = take(32 * P * n); q.o_b = take(32 * P * n); q.o_cg = take(32 * P * n); q.o_hf = take(32 * P * n);
-    q.o_jsc = take(32 * P * (2 * n + 2)); q.o_jout = take(144 * 2 * P); q.o_pts = take(64 * P * q.npt);
-  }
+  p.in_bytes = take.o;
+  for (RppmClass &q : p.cls) rpp_take_scratch(q, take, q, (size_t)q.count, q);
   p.o_out = take((size_t)p.total_out + 16);
-  p.need = o;
+  p.need = take.o;
   return p;
 }

@@ -36,6 +36,60 @@ def _le32(v):
     return (int(v.x if hasattr(v, "x") else v) % Q).to_bytes(32, "little")
 
 
+def pack_scalars(xs, m=None, what="prover"):
+    """32 little-endian bytes per value, proof after proof, from bytes already packed, a flat list of ModP / int (proofs of one value),
+    or a list of rows of m per proof.  m=None: rows of any length (a commitment does not depend on its proof's size).  what: "prover"
+    or "class", for the text of the error."""
+    if isinstance(xs, (bytes, bytearray, memoryview)):
+        return bytes(xs)
+    if len(xs) and isinstance(xs[0], (list, tuple)):
+        if m is not None and any(len(row) != m for row in xs):
+            raise ValueError("every proof of this %s takes %d values" % (what, m))
+        xs = [x for row in xs for x in row]
+    elif len(xs) and m not in (None, 1):
+        raise ValueError("every proof of this %s takes %d values" % (what, m))
+    return b"".join([_le32(x) for x in xs])
+
+
+def pack_pairs(vs, gammas, m, what="prover"):
+    """(values, blinding factors, proofs) of proofs of m values: pack_scalars of both, of the same whole number of proofs."""
+    vb, gb = pack_scalars(vs, m, what), pack_scalars(gammas, m, what)
+    count = len(vb) // (32 * m)
+    if len(vb) != 32 * count * m or len(gb) != len(vb):
+        raise ValueError("values and blinding factors must have the same length")
+    return vb, gb, count
+
+
+def seed_offsets(seeds, count):
+    """(joined bytes, c_uint64 array of count + 1 offsets) from a list of count seeds, or from (joined bytes, offsets) -- offsets a list
+    or a ctypes c_uint64 array (taken as it is)."""
+    if isinstance(seeds, tuple):
+        sb, offs = seeds
+        if len(offs) != count + 1:
+            raise ValueError("values, blinding factors and seeds must have the same length")
+        return bytes(sb), offs if isinstance(offs, ctypes.Array) else (ctypes.c_uint64 * (count + 1))(*offs)
+    if len(seeds) != count:
+        raise ValueError("values, blinding factors and seeds must have the same length")
+    off = (ctypes.c_uint64 * (count + 1))()
+    pos = 0
+    for i, sd in enumerate(seeds):
+        off[i] = pos
+        pos += len(sd)
+    off[count] = pos
+    return b"".join(seeds), off
+
+
+def grown_output(eng, buf, cap):
+    """The page-locked output buffer of a prover, kept between batches: `buf` if it holds cap bytes, else a new one with an eighth to
+    spare.  The library copies the proofs there straight from the device, and ONE host copy makes the bytes object (a fresh 18 MB ctypes
+    buffer per batch cost three: zero-fill, staging copy, string_at)."""
+    if buf is None or len(buf) < cap:
+        if buf is not None:
+            buf.free()
+        buf = eng.host_alloc(cap + cap // 8)
+    return buf
+
+
 class BatchRangeProver:
     def __init__(self, n, g, h, gs, hs, u, engine=None, m=1, wire_format=2):
         """n: bits per value (at most 128), m: values per proof (powers of two, 2 <= n m <= 1024; m = 1: single-value proofs); g, h, u:
@@ -59,34 +113,12 @@ class BatchRangeProver:
         self._handle = handle.value
         self._out = None
 
-    def _packed_scalars(self, vs, gammas):
-        """(values, blinding factors, count) as packed bytes, 32 little-endian per value, from lists of ModP / int (aggregated provers:
-        a list of m per proof) or from bytes already packed."""
-        vm = self.m
-
-        def flat(xs):
-            if vm == 1 and not (len(xs) and isinstance(xs[0], (list, tuple))):
-                return xs
-            for row in xs:
-                if len(row) != vm:
-                    raise ValueError("every proof of this prover takes %d values" % vm)
-            return [x for row in xs for x in row]
-        if isinstance(vs, (bytes, bytearray, memoryview)):
-            vb, count = bytes(vs), len(vs) // (32 * vm)
-        else:
-            count = len(vs)
-            vb = b"".join([_le32(v) for v in flat(vs)])
-        gb = bytes(gammas) if isinstance(gammas, (bytes, bytearray, memoryview)) else b"".join([_le32(x) for x in flat(gammas)])
-        if len(vb) != 32 * count * vm or len(gb) != 32 * count * vm:
-            raise ValueError("values and blinding factors must have the same length")
-        return vb, gb, count
-
     def commit_packed(self, vs, gammas):
         """The commitments V = v g + gamma h of every value, 64 bytes each (x, y little-endian; the identity is 64 zero bytes), proof
         after proof: what BatchRangeVerifier.verify_wire / partial_wire / locate_wire take as Vs.  One launch over the prover's tables
         (bpmi_rp_prover_commit_batch) instead of a loop of commitment(g, h, v, gamma).  The WHOLE value enters, not only its low n bits:
         the proof of an out-of-range value fails against its commitment.  vs, gammas: as for prove_wire_packed."""
-        vb, gb, count = self._packed_scalars(vs, gammas)
+        vb, gb, count = pack_pairs(vs, gammas, self.m)
         total = count * self.m
         out = ctypes.create_string_buffer(64 * total)
         eng = self._engine
@@ -111,31 +143,12 @@ class BatchRangeProver:
         copy=False: `packed` is a memoryview of the prover's page-locked output buffer and `offsets` the ctypes array the library
         filled -- valid until the next call on this prover or its close(); a service that forwards the bytes (a socket, the batch verifier's
         receive buffer) saves the one host copy of the batch (18 MB at 2^14 proofs) and the list of 2^14 Python integers."""
-        vb, gb, m = self._packed_scalars(vs, gammas)
-        if isinstance(seeds, tuple):
-            sb, offs = seeds
-            if len(offs) != m + 1:
-                raise ValueError("values, blinding factors and seeds must have the same length")
-            off = offs if isinstance(offs, ctypes.Array) else (ctypes.c_uint64 * (m + 1))(*offs)
-        else:
-            if len(seeds) != m:
-                raise ValueError("values, blinding factors and seeds must have the same length")
-            off = (ctypes.c_uint64 * (m + 1))()
-            pos = 0
-            for i, sd in enumerate(seeds):
-                off[i] = pos
-                pos += len(sd)
-            off[m] = pos
-            sb = b"".join(seeds)
+        vb, gb, m = pack_pairs(vs, gammas, self.m)
+        sb, off = seed_offsets(seeds, m)
         eng = self._engine
         eng.set_option("prover_wire_format", self.wire_format)           # (an engine option: set per call, provers may share the engine)
         cap = m * eng.lib.bpmi_rp_prove_batch_proof_bytes(self._handle, 0) + (off[m] - off[0]) + 16      # a proof is a fixed part + its seed
-        # the proofs land in a page-locked buffer of the prover (kept between batches): the library copies them there straight from the
-        # device, and ONE host copy makes the bytes object (a fresh 18 MB ctypes buffer per batch cost three: zero-fill, staging copy, string_at)
-        if self._out is None or len(self._out) < cap:
-            if self._out is not None:
-                self._out.free()
-            self._out = eng.host_alloc(cap + cap // 8)
+        self._out = grown_output(eng, self._out, cap)
         out_off = (ctypes.c_uint64 * (m + 1))()
         eng._ck(eng.lib.bpmi_rp_prove_batch(self._handle, m, vb, gb, sb, off, ctypes.c_void_p(self._out.ptr), cap, out_off))
         if not copy:

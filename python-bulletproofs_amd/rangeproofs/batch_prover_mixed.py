@@ -21,7 +21,7 @@ import ctypes
 
 from .. import _native
 from .. import engine as _engine
-from .batch_prover import BatchRangeProver, _le32
+from .batch_prover import BatchRangeProver, grown_output, pack_pairs, pack_scalars, seed_offsets
 
 
 class MixedBatchRangeProver:
@@ -40,30 +40,10 @@ class MixedBatchRangeProver:
         if m < 1 or m & (m - 1) or m > self.M or self.n * m < 2:
             raise ValueError("a class has a power of two of values per proof, at most %d, with bits x values >= 2" % self.M)
 
-    @staticmethod
-    def _packed(xs, m):
-        """32 little-endian bytes per value from a list of ModP / int (m > 1, or rows given: a list of m per proof) or packed bytes."""
-        if isinstance(xs, (bytes, bytearray, memoryview)):
-            return bytes(xs)
-        if len(xs) and isinstance(xs[0], (list, tuple)):
-            for row in xs:
-                if len(row) != m:
-                    raise ValueError("every proof of this class takes %d values" % m)
-            xs = [x for row in xs for x in row]
-        elif m != 1:
-            raise ValueError("every proof of this class takes %d values" % m)
-        return b"".join([_le32(x) for x in xs])
-
     def commit_packed(self, vs, gammas):
         """The commitments V = v g + gamma h, 64 bytes per value, in the order given (the tables of g and h do not depend on the class):
         vs, gammas as packed bytes, flat lists, or lists of rows."""
-        def flat(xs):
-            if isinstance(xs, (bytes, bytearray, memoryview)):
-                return bytes(xs)
-            if len(xs) and isinstance(xs[0], (list, tuple)):
-                xs = [x for row in xs for x in row]
-            return b"".join([_le32(x) for x in xs])
-        vb, gb = flat(vs), flat(gammas)
+        vb, gb = pack_scalars(vs), pack_scalars(gammas)
         if len(vb) != len(gb) or len(vb) % 32:
             raise ValueError("values and blinding factors must have the same length")
         out = ctypes.create_string_buffer(max(2 * len(vb), 1))
@@ -96,26 +76,8 @@ class MixedBatchRangeProver:
         eng.set_option("prover_wire_format", self.wire_format)
         for c, (m, vs, gammas, seeds) in enumerate(classes):
             self._check_m(m)
-            vb, gb = self._packed(vs, m), self._packed(gammas, m)
-            cnt = len(vb) // (32 * m)
-            if len(vb) != 32 * cnt * m or len(gb) != len(vb):
-                raise ValueError("values and blinding factors must have the same length")
-            if isinstance(seeds, tuple):
-                sb, offs = seeds
-                if len(offs) != cnt + 1:
-                    raise ValueError("values, blinding factors and seeds must have the same length")
-                off = offs if isinstance(offs, ctypes.Array) else (ctypes.c_uint64 * (cnt + 1))(*offs)
-                sb = bytes(sb)
-            else:
-                if len(seeds) != cnt:
-                    raise ValueError("values, blinding factors and seeds must have the same length")
-                off = (ctypes.c_uint64 * (cnt + 1))()
-                pos = 0
-                for i, sd in enumerate(seeds):
-                    off[i] = pos
-                    pos += len(sd)
-                off[cnt] = pos
-                sb = b"".join(seeds)
+            vb, gb, cnt = pack_pairs(vs, gammas, m, "class")
+            sb, off = seed_offsets(seeds, cnt)
             keep += [vb, gb, sb, off]
             arr[c].m, arr[c].n_proofs = m, cnt
             arr[c].values, arr[c].gammas = ctypes.cast(ctypes.c_char_p(vb), ctypes.c_void_p), ctypes.cast(ctypes.c_char_p(gb), ctypes.c_void_p)
@@ -123,10 +85,7 @@ class MixedBatchRangeProver:
             cap += cnt * eng.lib.bpmi_rp_prove_batch_proof_bytes_class(self._bp._handle, m, 0) + (off[cnt] - off[0])
             counts.append(cnt)
             total += cnt
-        if self._out is None or len(self._out) < cap:
-            if self._out is not None:
-                self._out.free()
-            self._out = eng.host_alloc(cap + cap // 8)
+        self._out = grown_output(eng, self._out, cap)
         out_off = (ctypes.c_uint64 * (total + 1))()
         eng._ck(eng.lib.bpmi_rp_prove_batch_mixed(self._bp._handle, len(classes), ctypes.cast(arr, ctypes.c_void_p), ctypes.c_void_p(self._out.ptr), cap,
                                                   ctypes.cast(out_off, ctypes.c_void_p)))

@@ -224,6 +224,72 @@ def test_a_single_class_of_the_capacity_equals_the_single_class_call(gp):
     assert _split(got) == [first] and second == first and nothing == []
 
 
+def test_calls_of_every_kind_share_one_prover(gp):
+    """One prover of capacity (8 bits, M = 4), at most 70 proofs per call (per_block 32 .. 8, a chain block is crossed at 65), takes in
+    turn: bpmi_rp_prove_batch of 3 proofs with seeds of 0, 1 and 100 bytes; a mixed call of m = 1 x 65 and m = 4 x 2;
+    bpmi_rp_prover_commit_batch of 5 pairs; bpmi_rp_prove_batch of 70 proofs, for which both of its buffers grow; the first call again.
+    Every result is what a fresh prover gives for that call alone, the first and the last are identical, a pageable `out` gives the
+    bytes of the page-locked one, and after each proving call last_ms holds seven finite non-negative values whose last is at least each
+    other.  Under option prover_split a single-class call of 4 proofs gives the same bytes: 1 (halves of at least 2 048: not split),
+    and 2 (split into 2 + 2)."""
+    import math
+    from bulletproofs_amd.rangeproofs.batch_prover import pack_pairs, seed_offsets
+    gens = tuple(x[:32] if isinstance(x, list) else x for x in _gens(gp, 1024))
+    eng = gp.engine()
+    v3, g3, _, _ = _rows(8, 4, 3, 0)
+    s3 = [b"", b"\x07", bytes(range(100))]
+    v65, g65, s65, _ = _rows(8, 1, 65, 1)
+    v2, g2, s2, _ = _rows(8, 4, 2, 2)
+    v70, g70, s70, _ = _rows(8, 4, 70, 3)
+    cv, cg, _, _ = _rows(8, 1, 5, 4)
+    calls = [lambda p: p._bp.prove_wire(v3, g3, s3),
+             lambda p: _split(p.prove_classes_packed([(1, v65, g65, s65), (4, v2, g2, s2)])),
+             lambda p: p.commit_packed(cv, cg),
+             lambda p: p._bp.prove_wire(v70, g70, s70),
+             lambda p: p._bp.prove_wire(v3, g3, s3)]
+
+    def timed(p):
+        ms = list(p.last_ms().values())
+        assert len(ms) == 7 and all(math.isfinite(v) and v >= 0 for v in ms) and ms[6] == max(ms) and ms[6] > 0, ms
+
+    want = []
+    for call in calls[:4]:
+        fresh = _mixed(gp, 8, gens)
+        try:
+            want.append(call(fresh))
+        finally:
+            fresh.close()
+    want.append(want[0])
+    mp = _mixed(gp, 8, gens)
+    try:
+        got = []
+        for i, call in enumerate(calls):
+            got.append(call(mp))
+            if i != 2:
+                timed(mp)
+        # the first call once more, into ordinary memory
+        vb, gb, count = pack_pairs(v3, g3, 4)
+        sb, off = seed_offsets(s3, count)
+        cap = sum(len(b) for b in want[0])
+        out, out_off = ctypes.create_string_buffer(cap), (ctypes.c_uint64 * (count + 1))()
+        eng._ck(eng.lib.bpmi_rp_prove_batch(mp._bp._handle, count, vb, gb, sb, off, ctypes.cast(out, ctypes.c_void_p), cap, out_off))
+        timed(mp)
+        pageable = [out.raw[out_off[i]: out_off[i + 1]] for i in range(count)]
+        split = {}
+        for opt in (1, 2):
+            eng.set_option("prover_split", opt)
+            split[opt] = mp._bp.prove_wire(v70[:4], g70[:4], s70[:4])
+            timed(mp)
+    finally:
+        eng.set_option("prover_split", 0)
+        mp.close()
+    assert len(got[0]) == 3 and [len(c) for c in got[1]] == [65, 2] and len(got[2]) == 64 * 5 and len(got[3]) == 70
+    for i in range(5):
+        assert got[i] == want[i], i
+    assert got[4] == got[0] and pageable == got[0]
+    assert split[1] == want[3][:4] and split[2] == want[3][:4]
+
+
 def test_degenerate_generators_inside_the_shortest_prefix(gp):
     """A capacity list with an identity (gs_1) and a coinciding pair (hs_0 = gs_0) inside the shortest prefix, and hs_5 = -gs_5 in the next:
     every class still equals the prover over its prefix, which tests/test_gpu_rp_degenerate.py pins to the integer model."""

@@ -23,11 +23,19 @@ def table_bytes(elems, w):
 BOUND = table_bytes(128, 16)                 # the largest default table of a proof of up to 128 elements: 8.7 GB
 
 
-@pytest.fixture(scope="module")
-def plans(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("rp_prove_plan") / "rp_prove_plan_main")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", INC, SRC, "-o", exe])
+def _build(tmp, src):
+    exe = str(tmp / os.path.basename(src)[:-4])
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", INC, src, "-o", exe])
+    return exe
 
+
+@pytest.fixture(scope="module")
+def exe(tmp_path_factory):
+    return _build(tmp_path_factory.mktemp("rp_prove_plan"), SRC)
+
+
+@pytest.fixture(scope="module")
+def plans(exe):
     def run(shapes):
         args = [str(x) for shape in shapes for x in shape]
         r = subprocess.run([exe] + args, capture_output=True, text=True, timeout=300)
@@ -146,3 +154,56 @@ def test_base_lists(defaults):
                 hit[g_list].add(rank)
                 hit[h_list].add(n // 2 + rank)
             assert hit["L"] == set(range(n)) and hit["R"] == set(range(n))
+
+
+# every array of rpp::Batch, inputs first: tests/test_rp_prove_mixed_plan_cpu.py ARRAYS
+ARRAYS = ("dig0", "dlen", "val", "gam", "tr", "trlen", "slr", "alpha", "chal", "tau", "tsc", "res", "xs", "xr", "a", "b", "cg", "hf", "jsc", "jout", "pts")
+INPUTS = ARRAYS[:4]
+LAYOUT_PROOFS = (1, 3, 64, 65)
+LAYOUT_SEEDS = ((0, 0), (7, 3), (65535, 65535))                  # total, longest
+
+
+def test_single_class_layout(exe, tmp_path_factory):
+    """rpp_layout, the device buffer of bpmi_rp_prove_batch, for every legal shape: aligned, disjoint, inside `need`, the upload inside
+    in_bytes, every array of the stated size -- and region for region the one-class mixed plan without its three device tables."""
+    mixed = _build(tmp_path_factory.mktemp("rp_prove_mixed_plan_for_layout"), os.path.join(os.path.dirname(SRC), "rp_prove_mixed_plan_main.cpp"))
+    cases = [(nb, m, P, st, sm) for nb, m in SHAPES for P in LAYOUT_PROOFS for st, sm in LAYOUT_SEEDS]
+    r = subprocess.run([exe, "layout"] + [str(x) for c in cases for x in c], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-4000:]
+    layouts = [json.loads(line) for line in r.stdout.splitlines()]
+    assert len(layouts) == len(cases)
+    up = lambda x: (x + 255) // 256 * 256
+    for (nb, m, P, st, sm), L in zip(cases, layouts):
+        n = nb * m
+        k = n.bit_length() - 1
+        assert list(L["regions"]) == list(ARRAYS)
+        sizes = {"dig0": P * L["dig0_stride"], "dlen": 4 * P, "val": 32 * P * m, "gam": 32 * P * m, "tr": P * L["tr_stride"], "trlen": 4 * P, "slr": 32 * P * (2 * n + 1), "alpha": 32 * P,
+                 "chal": 128 * P, "tau": 64 * P, "tsc": 128 * P, "res": 160 * P, "xs": 32 * P * k, "xr": 64 * P, "a": 32 * P * n, "b": 32 * P * n, "cg": 32 * P * n, "hf": 32 * P * n,
+                 "jsc": 32 * P * (2 * n + 2), "jout": 288 * P, "pts": 64 * P * (6 + 2 * k)}
+        assert {name: size for name, (_, size) in L["regions"].items()} == sizes
+        assert {name: size for name, (_, size) in L["call_regions"].items()} == {"seeds": st + 16, "soff": 8 * (P + 1), "ooff": 8 * (P + 1), "out": L["total_out"] + 16}
+        spans = []
+        for name, (off, size) in list(L["regions"].items()) + list(L["call_regions"].items()):
+            assert off % 256 == 0
+            assert (off + size <= L["in_bytes"]) if name in INPUTS + ("seeds", "soff", "ooff") else (off >= L["in_bytes"]), name
+            spans.append((off, off + size, name))
+        spans.sort()
+        for (a0, a1, an), (b0, b1, bn) in zip(spans, spans[1:]):
+            assert a1 <= b0, (an, bn)
+        assert spans[0][0] == 0 and spans[-1][1] <= L["need"]
+        assert [name for _, _, name in spans] == list(INPUTS) + ["seeds", "soff", "ooff"] + list(ARRAYS[4:]) + ["out"]          # the order in the buffer
+        # the one-class mixed plan of the same shape (capacity = the class)
+        mr = subprocess.run([mixed, "plan", str(nb), str(m), "2", "0", "%d:%d:%d:%d" % (m, P, st, sm)], capture_output=True, text=True, timeout=300)
+        assert mr.returncode == 0, mr.stderr[-4000:]
+        mp = json.loads(mr.stdout)
+        assert mp["err"] == 0 and len(mp["classes"]) == 1 and mp["total_out"] == L["total_out"]
+        q = mp["classes"][0]
+        assert (q["dig0_stride"], q["tr_stride"]) == (L["dig0_stride"], L["tr_stride"])
+        assert sorted(q["regions"], key=lambda name: q["regions"][name][0]) == list(ARRAYS)          # (the same order)
+        tables = sum(up(mp["call_regions"][t][1]) for t in ("batch", "jobs", "units"))
+        assert tables > 0 and mp["in_bytes"] == L["in_bytes"] + tables and mp["need"] == L["need"] + tables
+        for name in ARRAYS:
+            assert q["regions"][name] == [L["regions"][name][0] + (0 if name in INPUTS else tables), L["regions"][name][1]], name
+        for name in ("seeds", "soff", "ooff"):
+            assert mp["call_regions"][name] == L["call_regions"][name]
+        assert mp["call_regions"]["out"] == [L["call_regions"]["out"][0] + tables, L["call_regions"]["out"][1]]
