@@ -787,6 +787,58 @@ int bpmi_ipa_batch_prover_last_ms(const bpmi_ipa_batch_prover *pv, double ms[4])
 int bpmi_ipa_batch_prover_commit_batch(bpmi_ipa_batch_prover *pv, uint64_t count, const uint8_t *a, const uint8_t *b, int u_mode, const uint8_t *t,
                                        uint8_t *out);
 int bpmi_ipa_batch_prover_commit_last_ms(const bpmi_ipa_batch_prover *pv, double ms[2]);
+/* Arguments of DIFFERENT lengths from one prover, one table and one call (csrc/ipa_prove_mixed_plan_host.hpp,
+ * ipa_prove_mixed_kernels.hpp, ipa_prove_mixed_host.hpp).  A bpmi_ipa_batch_prover created for n = N is a CAPACITY: a class of
+ * n_c = 2^k_c elements, 1 <= n_c <= N, runs over g[:n_c], h[:n_c], the one u, and h_scale[:n_c] where the prover has one -- the
+ * generators a loop of `NIProver(g[:n_c], h[:n_c], u, P_p, c_p, a_p, b_p, group, seed_p).prove()`
+ * (src/innerproduct/inner_product_prover.py:11-45) or of `FastNIProver2(g[:n_c], h[:n_c], u, P_p, a_p, b_p, group, transcript_p).prove()`
+ * (:48-110) would be given: proof p of class c is byte for byte what bpmi_ipa_prove_batch writes on a prover created over that prefix.
+ * The rounds never fold a generator (:94-110 read g and h through the fold coefficients), so the table of the longest list serves
+ * every class; every protocol step is one launch per kernel over ALL classes, k_max + 1 steps where a loop over lengths runs the sum
+ * of the k_c + 1.
+ *   bpmi_ipa_prove_class    one class: n, n_proofs and the inputs a, b, c, P, seeds, seed_off as bpmi_ipa_prove_batch takes them
+ *                           (n_proofs x n x 32 B etc.; c may be NULL per class), and the class's OWN outputs ab, xs, LR, head,
+ *                           transcripts (cap bytes), tr_off (n_proofs + 1 entries): with the class's statements they are the fields of
+ *                           one bpmi_ipa_packed_class of bpmi_ipa_verify_batch_packed_mixed_dev, untouched.
+ *   bpmi_ipa_prove_batch_transcript_bytes_class   bpmi_ipa_prove_batch_transcript_bytes of a class of n elements (0: n is no class of
+ *                           the prover, or the protocol is neither 1 nor 2)
+ *   bpmi_ipa_prove_batch_mixed   proves classes[0 .. n_classes) in the caller's order, one protocol per call.  The NULL / non-NULL rules of
+ *                           bpmi_ipa_prove_batch hold per class with the class's own k_c (a class of n = 1 may pass NULL xs and LR).
+ *                           Two classes may have the same n.  BPMI_E_ARG, the message naming the class where there is one: more
+ *                           than 64 classes, an n that is no class, a class of 0 proofs, more than 2^20 proofs or 2^27 elements (sum
+ *                           of n_proofs x n) per call, a seed above 65 535 bytes, decreasing seed offsets, a class's cap below n_proofs
+ *                           x bpmi_ipa_prove_batch_transcript_bytes_class of its longest seed, a scalar of a, b, c not below q (the
+ *                           message names the class, the array and the first index), and under protocol 1 and "validate_points" >= 1
+ *                           a P that is no point of the curve (the class and the index).  The shape errors come before anything is
+ *                           read or allocated; no output of any class is written on any error.  n_classes = 0 is BPMI_OK (the
+ *                           protocol is still checked) and touches nothing.  Option "prover_job_lanes" covers the whole call (a
+ *                           class's lanes per job by the jobs of the whole launch).  bpmi_ipa_batch_prover_last_ms reports the same
+ *                           four phases.  One window width serves every class: the capacity's.
+ *   bpmi_ipa_commit_class, bpmi_ipa_batch_prover_commit_batch_mixed   the statements of such a block from the same tables:
+ *                           out_c[p] = sum_j a_p[j] g_j + sum_j b_p[j] (c_j h_j) + t_p u over the class's prefix -- per class a loop of
+ *                           `vector_commitment(g[:n_c], h[:n_c], a_p, b_p)` (src/utils/commitments.py:13) plus `inner_product(a, b) * u`.
+ *                           u_mode is one value per call; the NULL rules of bpmi_ipa_batch_prover_commit_batch hold per class; the
+ *                           caps and the class errors are those of the prove call; nothing is written on an error.
+ *                           bpmi_ipa_batch_prover_commit_last_ms reports this call like the single-class one. */
+typedef struct {
+  uint32_t n;                    /* elements per vector: a power of two, 1 <= n <= the prover's */
+  uint64_t n_proofs;
+  const uint8_t *a, *b, *c, *P;
+  const uint8_t *seeds;
+  const uint64_t *seed_off;
+  uint8_t *ab, *xs, *LR, *head, *transcripts;
+  uint64_t cap;
+  uint64_t *tr_off;
+} bpmi_ipa_prove_class;
+uint64_t bpmi_ipa_prove_batch_transcript_bytes_class(const bpmi_ipa_batch_prover *pv, uint32_t n, int protocol, uint64_t seed_len);
+int bpmi_ipa_prove_batch_mixed(bpmi_ipa_batch_prover *pv, int protocol, uint32_t n_classes, const bpmi_ipa_prove_class *classes);
+typedef struct {
+  uint32_t n;
+  uint64_t count;
+  const uint8_t *a, *b, *t;
+  uint8_t *out;
+} bpmi_ipa_commit_class;
+int bpmi_ipa_batch_prover_commit_batch_mixed(bpmi_ipa_batch_prover *pv, int u_mode, uint32_t n_classes, const bpmi_ipa_commit_class *classes);
 
 /* ---- batch verifier of PACKED inner-product proofs ---------------------------------------- */
 /* What bpmi_ipa_prove_batch writes, verified without leaving native code: the Fiat-Shamir re-hash, the byte-level checks and the

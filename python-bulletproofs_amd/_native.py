@@ -101,6 +101,10 @@ SIGNATURES = {
     "bpmi_ipa_batch_prover_last_ms": (_i, [_vp, ctypes.POINTER(ctypes.c_double)]),
     "bpmi_ipa_batch_prover_commit_batch": (_i, [_vp, _u64, _cp, _cp, _i, _cp, _vp]),
     "bpmi_ipa_batch_prover_commit_last_ms": (_i, [_vp, ctypes.POINTER(ctypes.c_double)]),
+    "bpmi_ipa_prove_batch_transcript_bytes_class": (_u64, [_vp, ctypes.c_uint32, _i, _u64]),
+    # pv, protocol | u_mode, n_classes, classes (IpaProveClass / IpaCommitClass array)
+    "bpmi_ipa_prove_batch_mixed": (_i, [_vp, _i, ctypes.c_uint32, _vp]),
+    "bpmi_ipa_batch_prover_commit_batch_mixed": (_i, [_vp, _i, ctypes.c_uint32, _vp]),
     # (k | ctx, k | ctx, g, h, hscale, n), protocol, n_proofs, ab, xs, LR, transcripts, tr_off, start, u, P, c, head, weights, seed, ...
     "bpmi_ipa_batch_prepare": (_i, [ctypes.c_uint32, _i, _u64, _cp, _cp, _cp, _cp, _vp, _vp, _cp, _cp, _cp, _cp, _cp, _cp, _i, _vp, _vp, _vp, _vp]),
     "bpmi_ipa_batch_prepare_dev": (_i, [_vp, ctypes.c_uint32, _i, _u64, _cp, _cp, _cp, _cp, _vp, _vp, _cp, _cp, _cp, _cp, _cp, _cp, _vp, _vp, _vp, _vp]),
@@ -140,6 +144,18 @@ class RpProveClass(ctypes.Structure):
     """bpmi_rp_prove_class (include/bpmi.h): one class of bpmi_rp_prove_batch_mixed.  Plain addresses, as RpClass."""
     _fields_ = [("m", ctypes.c_uint32), ("n_proofs", ctypes.c_uint64), ("values", ctypes.c_void_p), ("gammas", ctypes.c_void_p), ("seeds", ctypes.c_void_p),
                 ("seed_off", ctypes.c_void_p)]
+
+
+class IpaProveClass(ctypes.Structure):
+    """bpmi_ipa_prove_class (include/bpmi.h): one class of bpmi_ipa_prove_batch_mixed, its inputs and its own outputs.  Plain addresses, as RpClass."""
+    _fields_ = ([("n", ctypes.c_uint32), ("n_proofs", ctypes.c_uint64)] +
+                [(name, ctypes.c_void_p) for name in ("a", "b", "c", "P", "seeds", "seed_off", "ab", "xs", "LR", "head", "transcripts")] +
+                [("cap", ctypes.c_uint64), ("tr_off", ctypes.c_void_p)])
+
+
+class IpaCommitClass(ctypes.Structure):
+    """bpmi_ipa_commit_class (include/bpmi.h): one class of bpmi_ipa_batch_prover_commit_batch_mixed.  Plain addresses, as RpClass."""
+    _fields_ = [("n", ctypes.c_uint32), ("count", ctypes.c_uint64)] + [(name, ctypes.c_void_p) for name in ("a", "b", "t", "out")]
 
 
 class IpaPackedClass(ctypes.Structure):

@@ -62,6 +62,7 @@ using namespace bpmi;
 #include "rp_prove_plan_host.hpp"
 #include "rp_prove_mixed_plan_host.hpp"
 #include "ipa_prove_plan_host.hpp"
+#include "ipa_prove_mixed_plan_host.hpp"
 #include "ipa_batch_plan_host.hpp"
 #include "ipa_mixed_plan_host.hpp"
 #include "ipa_packed_plan_host.hpp"
@@ -96,6 +97,7 @@ using namespace bpmi;
 #include "rp_prove_kernels.hpp"
 #include "rp_prove_mixed_kernels.hpp"
 #include "ipa_prove_kernels.hpp"
+#include "ipa_prove_mixed_kernels.hpp"
 #include "h2c.hpp"
 #include "h2c_kernels.hpp"
 #include "h2c_host.hpp"

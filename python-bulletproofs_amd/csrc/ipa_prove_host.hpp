@@ -2,7 +2,8 @@
 // The batched inner-product prover's object and launch sequence (kernels: ipa_prove_kernels.hpp; plan: ipa_prove_plan_host.hpp):
 // bpmi_ipa_batch_prover_create builds the fixed-base tables of a generator set (u, g, h) once; bpmi_ipa_prove_batch proves any
 // number of arguments over them, every protocol step as one launch over the whole batch; bpmi_ipa_batch_prover_commit_batch makes the
-// statements P_p of a batch from the same tables.
+// statements P_p of a batch from the same tables.  ipa_prove_mixed_host.hpp (included at the end): both calls over classes of different
+// lengths on one prover.
 #pragma once
 
 struct bpmi_ipa_batch_prover {
@@ -13,6 +14,8 @@ struct bpmi_ipa_batch_prover {
   u32 tw = 16, wt = 16, bt = 32768;
   unsigned short *bases = nullptr;             // device: the base lists (ipp_plan)
   unsigned short *cbases = nullptr;            // device: the base lists of a statement's job (ipp_commit_bases_all)
+  unsigned short *mixed_bases = nullptr;       // device: the base lists of every class n_c <= n (ipp_capacity_bases), made by the first mixed call
+  unsigned short *mixed_cbases = nullptr;      // device: the statements' lists of every class (ipp_capacity_commit_bases), likewise
   u32 off_head = 0, off_round = 0;
   u32 *hscale = nullptr;                       // device: n scalars, or nullptr
   rpp_host::Buffers mem;                       // the batch's device arrays; page-locked staging of the inputs / the proofs
@@ -29,6 +32,8 @@ void bpmi_ipa_batch_prover_destroy(bpmi_ipa_batch_prover *pv) {
   if (pv->table) (void)hipFree(pv->table);
   if (pv->bases) (void)hipFree(pv->bases);
   if (pv->cbases) (void)hipFree(pv->cbases);
+  if (pv->mixed_bases) (void)hipFree(pv->mixed_bases);
+  if (pv->mixed_cbases) (void)hipFree(pv->mixed_cbases);
   if (pv->hscale) (void)hipFree(pv->hscale);
   pv->mem.release();
   for (auto e : pv->ev) if (e) (void)hipEventDestroy(e);
@@ -303,3 +308,5 @@ int bpmi_ipa_batch_prover_commit_last_ms(const bpmi_ipa_batch_prover *pv, double
 }
 
 }  // extern "C"
+
+#include "ipa_prove_mixed_host.hpp"

@@ -15,6 +15,9 @@
 //     (1 under Protocol 2) where the range prover has one constant x_ip per batch (its Protocol-1 seed is always empty);
 //   * the statement point P_p is no fixed base: P_new = P_p + (x_p c_p) u is one complete mixed addition behind a one-term job (k_ip_head);
 //   * the points of a proof are u_new, P_new (`head`) and L_0.. R_0.. (`lr`), two arrays in the order the caller receives them.
+// Every kernel's body is a __device__ function of (record, block index), ip_*_block, which the kernel calls with blockIdx.x and its
+// `_mixed` twin (ipa_prove_mixed_kernels.hpp: classes of different lengths in one launch) with the block's index inside its class.
+// Hoisting the bodies moved no kernel's registers, scratch, LDS or occupancy (profiles/r22_ipa_prove_mixed_resources.txt).
 #pragma once
 
 namespace ipp {
@@ -55,8 +58,8 @@ struct Batch {
 // ---- the transcript's start, one lane per proof (inner_product_prover.py:30-31, :58-63) ----------------------------------------------------
 // Protocol 1: the outer transcript is base64(seed) "&"; x = mod_hash of it; the inner transcript is "&" || outer || str(x) "&".
 // Protocol 2: the inner transcript is "&" || the caller's prefix, staged whole.
-__global__ void __launch_bounds__(64) k_ip_begin(Batch B) {
-  const u32 p = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void ip_begin_block(const Batch &B, const u32 blk) {
+  const u32 p = blk * blockDim.x + threadIdx.x;
   if (p >= B.P) return;
   u8 *tr = B.tr + (size_t)p * B.tr_stride;
   const u8 *dg = B.dig0 + (size_t)p * B.dig0_stride;
@@ -77,11 +80,12 @@ __global__ void __launch_bounds__(64) k_ip_begin(Batch B) {
     st_sc(B.uc + 8ull * p, sc_u32(1));
   }
 }
+__global__ void __launch_bounds__(64) k_ip_begin(Batch B) { ip_begin_block(B, blockIdx.x); }
 
 // ---- the head of a Protocol-1 proof (:32-33): job 2p = x_p u is u_new; job 2p + 1 = (x_p c_p) u, and P_new = P_p + it -- a complete
 // mixed addition: P_p may be the identity, the opposite of the job's result (P_new is the identity) or equal to it (a doubling)
-__global__ void __launch_bounds__(256) k_ip_head(Batch B) {
-  const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void ip_head_block(const Batch &B, const u32 blk) {
+  const u32 t = blk * blockDim.x + threadIdx.x;
   if (t >= 2u * B.P) return;
   xyzz acc;
   ::xyzz_load_g(acc, B.jout + 36ull * t);
@@ -96,13 +100,14 @@ __global__ void __launch_bounds__(256) k_ip_head(Batch B) {
   bpmi::affine_to_words(w, r);
   ::store_words16(B.head + 16ull * t, w);
 }
+__global__ void __launch_bounds__(256) k_ip_head(Batch B) { ip_head_block(B, blockIdx.x); }
 
 // ---- one round (:94-110) over the UNFOLDED generators: see rp_prove_kernels.hpp, "one round of Protocol 2".  Job 2p is L, job 2p + 1 is
 // R, n + 1 terms each in the base order of ipp_plan:
 //   L = sum a_(i-half) cg_j g_j + sum b_(i+half) hf_j h_j + (uc_p c_L) u,   i = j mod len
 // L, R -> transcript -> x, 1 / x (:100-106); k_pv_round_chal with this layout's points
-__global__ void __launch_bounds__(64) k_ip_round_chal(Batch B, u32 round) {
-  const u32 p = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void ip_round_chal_block(const Batch &B, const u32 round, const u32 blk) {
+  const u32 p = blk * blockDim.x + threadIdx.x;
   if (p >= B.P) return;
   u8 *tr = B.tr + (size_t)p * B.tr_stride;
   u32 tl = B.tr_len[p];
@@ -116,15 +121,16 @@ __global__ void __launch_bounds__(64) k_ip_round_chal(Batch B, u32 round) {
   st_sc(B.xr + 16ull * p, x);
   st_sc(B.xr + 16ull * p + 8, invq(x));
 }
+__global__ void __launch_bounds__(64) k_ip_round_chal(Batch B, u32 round) { ip_round_chal_block(B, round, blockIdx.x); }
 // n lanes per proof (block = NT threads = NT / n proofs; NT = 1024: 4 x 32 KB of LDS, a block per CU).  first = 1: the state is loaded
 // from the caller's vectors with cg = 1, hf = hscale_j or 1, and under Protocol 1 without c the head's scalar x_p <a_p, b_p> is summed
 // over the proof's lanes; else the state is folded with the challenge of `round` (:107-110).  Either way the scalars of the NEXT
 // round's L and R are written, as k_pv_round_wide writes them with uc_p in the place of x_ip.  After the last fold (or at once, for
 // n = 1) a[0], b[0] are the proof's scalars.
-template <u32 NT> __global__ void __launch_bounds__(NT) k_ip_round_wide(Batch B, u32 round, u32 first) {
+template <u32 NT> __device__ __forceinline__ void ip_round_wide_block(const Batch &B, const u32 round, const u32 first, const u32 blk) {
   __shared__ u32 s_a[NT * 8], s_b[NT * 8], s_l[NT * 8], s_r[NT * 8];
   const u32 n = B.n, tid = threadIdx.x;
-  const u32 p = blockIdx.x * (NT / n) + tid / n, j = tid & (n - 1u);
+  const u32 p = blk * (NT / n) + tid / n, j = tid & (n - 1u);
   const bool live = p < B.P;
   const u32 base = tid - j;                                  // first thread of this proof in the block
   u32 len = first ? n : (n >> round);                        // length BEFORE this call's fold
@@ -201,6 +207,7 @@ template <u32 NT> __global__ void __launch_bounds__(NT) k_ip_round_wide(Batch B,
   st_sc((up ? jl : jr) + 8ull * rank, mulq(ga, cgj));                       // L: a_(i-half) cg_j for i >= half; R: a_(i+half) cg_j for i < half
   st_sc((up ? jr : jl) + 8ull * ((n >> 1) + rank), mulq(hb, hfj));          // L: b_(i+half) hf_j for i < half; R: b_(i-half) hf_j for i >= half
 }
+template <u32 NT> __global__ void __launch_bounds__(NT) k_ip_round_wide(Batch B, u32 round, u32 first) { ip_round_wide_block<NT>(B, round, first, blockIdx.x); }
 
 // ---- the statements of a batch (bpmi_ipa_batch_prover_commit_batch): P_p = sum a_p[j] g_j + sum b_p[j] (c_j h_j) + t_p u, a loop of
 // vector_commitment(g, h, a_p, b_p) (src/utils/commitments.py:13) plus inner_product(a, b) * u.  This kernel only lays out the scalars:
@@ -225,10 +232,10 @@ __device__ __forceinline__ sc sc_shfl_xor(const sc &a, int mask) {
 // included, which carry zeros -- reaches every shuffle and the barrier.  The dot of u_mode 1: a butterfly of shuffles over the
 // min(n, 64) lanes a proof has in a wave; for n > 64 the n / 64 wave sums meet in LDS and the proof's first wave adds them with the
 // same butterfly.
-template <u32 NT> __global__ void __launch_bounds__(NT) k_ip_commit_scalars(Commit C) {
+template <u32 NT> __device__ __forceinline__ void ip_commit_scalars_block(const Commit &C, const u32 blk) {
   __shared__ u32 s_w[(NT / 64u) * 8u];
   const u32 n = C.n, tid = threadIdx.x;
-  const u32 p = blockIdx.x * (NT / n) + tid / n, j = tid & (n - 1u);
+  const u32 p = blk * (NT / n) + tid / n, j = tid & (n - 1u);
   const bool live = p < C.count;
   const size_t e = (size_t)p * n + j;
   u32 *row = C.jsc + 8ull * (size_t)p * C.T;
@@ -255,5 +262,6 @@ template <u32 NT> __global__ void __launch_bounds__(NT) k_ip_commit_scalars(Comm
   }
   if (live && j == 0u) st_sc(row + 8ull * off_t, acc);
 }
+template <u32 NT> __global__ void __launch_bounds__(NT) k_ip_commit_scalars(Commit C) { ip_commit_scalars_block<NT>(C, blockIdx.x); }
 
 }  // namespace ipp

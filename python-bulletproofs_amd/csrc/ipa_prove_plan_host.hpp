@@ -29,6 +29,30 @@ struct IppPlan {
 
 static inline IppPlan ipp_plan_error(const char *msg) { IppPlan p; p.err = BPMI_E_ARG; p.msg = msg; return p; }
 
+// The base lists of a proof of n elements over the first n of N generators each (n = N: a prover of its own; n < N: a class of a
+// capacity, ipa_prove_mixed_plan_host.hpp): u = 0, g_j = 1 + j, h_j = 1 + N + j -- the capacity enters in the base of h_j and nowhere
+// else.  The head's one term (u) at entry 0, then from entry 1 round r: L then R, n + 1 each, by the rule of rpp_plan: L holds the g_j
+// with (j mod len) >= half, then the h_j with (j mod len) < half, then u; R the complements (ipa_prove_kernels.hpp k_ip_round_wide)
+static inline size_t ipp_class_bases_len(u32 n) {
+  u32 k = 0;
+  while ((1u << k) < n) k++;
+  return 1 + (size_t)k * 2 * (n + 1);
+}
+static inline std::vector<unsigned short> ipp_class_bases(u32 n, u32 N) {
+  std::vector<unsigned short> bl;
+  bl.reserve(ipp_class_bases_len(n));
+  bl.push_back(0);
+  for (u32 len = n; len > 1; len >>= 1) {
+    const u32 half = len >> 1;
+    for (int side = 0; side < 2; side++) {               // 0: L, 1: R
+      for (u32 j = 0; j < n; j++) if (((j & (len - 1)) >= half) == (side == 0)) bl.push_back((unsigned short)(1 + j));
+      for (u32 j = 0; j < n; j++) if (((j & (len - 1)) < half) == (side == 0)) bl.push_back((unsigned short)(1 + N + j));
+      bl.push_back(0);
+    }
+  }
+  return bl;
+}
+
 // opt_tw: option "prover_table_bits" (0, or 4 .. 16: bpmi_set_option checks it)
 static inline IppPlan ipp_plan(uint32_t n, int opt_tw) {
   if (n < 1 || n > PROVER_ELEMS_MAX || (n & (n - 1)))
@@ -43,21 +67,9 @@ static inline IppPlan ipp_plan(uint32_t n, int opt_tw) {
   p.wt = (256u + p.tw - 1u) / p.tw; p.bt = 1u << (p.tw - 1u);
   p.table_bytes = rpp_table_bytes_of(p.nbases, p.tw);
   p.max_proofs = PROVER_BATCH_ELEMS_MAX / n < PROVER_PROOFS_MAX ? PROVER_BATCH_ELEMS_MAX / n : PROVER_PROOFS_MAX;
-  // bases: u = 0, g_j = 1 + j, h_j = 1 + n + j; round r by the rule of rpp_plan: L holds the g_j with (j mod len) >= half, then the
-  // h_j with (j mod len) < half, then u; R the complements (ipa_prove_kernels.hpp k_ip_round_wide)
-  std::vector<unsigned short> &bl = p.bases;
-  bl.reserve(1 + (size_t)p.k * 2 * (n + 1));
   p.off_head = 0;
-  bl.push_back(0);
-  p.off_round = (u32)bl.size();
-  for (u32 r = 0; r < p.k; r++) {
-    const u32 len = n >> r, half = len >> 1;
-    for (int side = 0; side < 2; side++) {               // 0: L, 1: R
-      for (u32 j = 0; j < n; j++) if (((j & (len - 1)) >= half) == (side == 0)) bl.push_back((unsigned short)(1 + j));
-      for (u32 j = 0; j < n; j++) if (((j & (len - 1)) < half) == (side == 0)) bl.push_back((unsigned short)(1 + n + j));
-      bl.push_back(0);
-    }
-  }
+  p.off_round = 1;
+  p.bases = ipp_class_bases(n, n);
   return p;
 }
 
@@ -131,19 +143,22 @@ static inline const char *ipp_commit_error(const IppCommitCall &c) {
 // the base list of a statement's job: g_0 .. g_(n-1) (bases 1 + j) when a is given, h_0 .. h_(n-1) (1 + n + j) when b is, then u (0)
 // LAST: of 2n + 1 terms it is the one that does not fill a round of the job's 16 lanes, the remainder term k_pv_msm shares out by
 // windows.  A NULL half is dropped from the list, not multiplied by zero.
-static inline std::vector<unsigned short> ipp_commit_bases(u32 n, bool have_a, bool have_b, bool have_u) {
+// N: the generators of the prover's table (h_j at base 1 + N + j); N = n unless the statements are a class of a capacity
+static inline std::vector<unsigned short> ipp_commit_class_bases(u32 n, u32 N, bool have_a, bool have_b, bool have_u) {
   std::vector<unsigned short> bl;
   bl.reserve((size_t)n * ((have_a ? 1u : 0u) + (have_b ? 1u : 0u)) + (have_u ? 1u : 0u));
   if (have_a) for (u32 j = 0; j < n; j++) bl.push_back((unsigned short)(1 + j));
-  if (have_b) for (u32 j = 0; j < n; j++) bl.push_back((unsigned short)(1 + n + j));
+  if (have_b) for (u32 j = 0; j < n; j++) bl.push_back((unsigned short)(1 + N + j));
   if (have_u) bl.push_back(0);
   return bl;
 }
+static inline std::vector<unsigned short> ipp_commit_bases(u32 n, bool have_a, bool have_b, bool have_u) { return ipp_commit_class_bases(n, n, have_a, have_b, have_u); }
 // the device copy: the lists (a, b, u), (a, u), (b, u) one after the other; a call without a u term takes its list one entry short
 static inline u32 ipp_commit_bases_offset(u32 n, bool have_a, bool have_b) { return have_a && have_b ? 0u : have_a ? 2u * n + 1u : 3u * n + 2u; }
-static inline std::vector<unsigned short> ipp_commit_bases_all(u32 n) {
-  std::vector<unsigned short> all = ipp_commit_bases(n, true, true, true);
-  const std::vector<unsigned short> a_only = ipp_commit_bases(n, true, false, true), b_only = ipp_commit_bases(n, false, true, true);
+static inline std::vector<unsigned short> ipp_commit_bases_all(u32 n, u32 N = 0) {
+  if (!N) N = n;
+  std::vector<unsigned short> all = ipp_commit_class_bases(n, N, true, true, true);
+  const std::vector<unsigned short> a_only = ipp_commit_class_bases(n, N, true, false, true), b_only = ipp_commit_class_bases(n, N, false, true, true);
   all.insert(all.end(), a_only.begin(), a_only.end());
   all.insert(all.end(), b_only.begin(), b_only.end());
   return all;
