@@ -843,7 +843,8 @@ int bpmi_ipa_batch_prover_commit_batch_mixed(bpmi_ipa_batch_prover *pv, int u_mo
 /* ---- batch verifier of PACKED inner-product proofs ---------------------------------------- */
 /* What bpmi_ipa_prove_batch writes, verified without leaving native code: the Fiat-Shamir re-hash, the byte-level checks and the
  * weighted scalars of every proof run per proof (host twin: csrc/ipa_packed_host.hpp; kernels: csrc/ipa_packed_kernels.hpp), then
- * the batch is the one MSM of bpmi_ipa_verify_batch_dev.  No new wire format: for n = 2^k the input is, per call,
+ * the batch is the one MSM of bpmi_ipa_verify_batch_dev.  The arrays are the library's own layout (the wire format of a Protocol-2
+ * proof is BPIP2, below): for n = 2^k the input is, per call,
  *   ab           n_proofs x 64 B        a || b, little-endian
  *   xs           n_proofs x k x 32 B    the challenges, little-endian                           (NULL allowed at k = 0)
  *   LR           n_proofs x 2k x 64 B   L_0 .. L_(k-1) R_0 .. R_(k-1), affine; the identity is 64 zero bytes   (NULL allowed at k = 0)
@@ -991,6 +992,62 @@ int bpmi_ipa_verify_batch_packed_mixed_dev(bpmi_ctx *ctx, const void *d_g, const
 int bpmi_ipa_group_values_packed_mixed_dev(bpmi_ctx *ctx, const void *d_g, const void *d_h, const void *d_hscale, uint64_t n_gens, int protocol,
                                            uint32_t n_classes, const bpmi_ipa_packed_class *classes, const uint64_t *group, const uint8_t *weights,
                                            const uint8_t *seed, uint8_t *values, uint64_t *value_off, uint8_t *status);
+/* ---- wire format BPIP2 of Protocol-2 inner-product proofs, verified from bytes ------------------- */
+/* The packed arrays above carry every fact two or three times (the points as LR rows and as base64 items of the transcript, the
+ * challenges as xs rows and in decimal).  BPIP2 is the same information once, self-describing, 78 + 98 k + prefix_len bytes for a
+ * proof of n = 2^k elements (0.67 KB at n = 64 against 2.04 KB packed):
+ *   "BPIP2" | k (1 B)                              k <= 22
+ *   a | b | xs[0..k)                               (2 + k) x 32 B big-endian
+ *   L_0 .. L_(k-1) R_0 .. R_(k-1)                  2k x 33 B SEC1 compressed; 33 zero bytes = the identity
+ *   start (4 B big-endian)                         Proof2.start_transcript
+ *   prefix_len (4 B big-endian) | prefix           the transcript's bytes before item `start`
+ * (scalars, identity and the points' offset as rangeproofs/codec.py).  A batch is `blobs` plus `off`: n_proofs + 1 offsets, proof p
+ * is blobs[off[p] .. off[p+1]).  A blob STANDS FOR the packed proof with ab, xs little-endian, LR the decompressed points, start, and
+ * the transcript
+ *   prefix || for each round j:  item(L_j) "&" item(R_j) "&" decimal(x_j) "&"      item = base64(SEC1(point)), "AA==" for the identity
+ * -- what FastNIProver2 writes (/root/reference/src/innerproduct/inner_product_prover.py:94-110 over src/utils/transcript.py:13-29;
+ * for its proofs the prefix is "&" plus the `transcript` argument, :62-67).  A wire proof is VALID exactly when that packed proof is
+ * valid for bpmi_ipa_verify_batch_packed_dev, with three conventions on top:
+ *   status bit 0   a malformed blob: wrong magic; a k byte that is not the call's; a length that is not 78 + 98 k + prefix_len; a, b
+ *                  or x_j >= q; an expansion above 2^17 bytes.  Nothing of it is expanded (zero ab / xs rows, start 0, no transcript)
+ *   status bit 1   a point that does not decode -- a tag other than 0, 2, 3; tag 0 with a non-zero x; x >= p; an x with no y -- at
+ *                  EVERY "validate_points" level (the decompression decides it anyway).  Its LR row is zero.  The points are decoded
+ *                  whenever the blob has the call's header and at least 78 + 98 k bytes, so both bits can be set
+ *   a flagged proof contributes nothing, as in the packed call; the status byte of a proof these two conventions flag holds their
+ *   bits alone (the packed checks saw rows that are zero).
+ * `start` is carried, not recounted: a prefix whose number of '&' does not match it expands to a proof the packed checks reject.
+ * ENCODABLE is a packed proof whose transcript IS that text: at least `start` '&', and from item `start` on exactly the canonical
+ * rounds; a, b, xs below q; every L, R the identity or on the curve.  A proof with trailing text passes Verifier2 (which never looks
+ * behind the last round, inner_product_verifier.py:104-125) but has no wire form.
+ * Protocol 2 only: Protocol 1, proofs of different lengths in one call, the group / locate calls and a format with y hints are out
+ * of scope; every entry point below takes `protocol` where the packed calls do and refuses anything but 2 with BPMI_E_ARG.
+ *   bpmi_ipa_wire_bytes        78 + 98 k + prefix_len
+ *   bpmi_ipa_wire_encode       HOST code, no ctx (message: bpmi_last_error(NULL)).  packed -> blobs back to back in blobs[0, cap) and off
+ *                              (n_proofs + 1; off[0] = 0); status[p] = 0, or 1 for a proof that is not encodable (an empty blob).
+ *                              start NULL = 1 for every proof.  cap: n_proofs x (78 + 98 k) + the transcripts' bytes always suffice;
+ *                              BPMI_E_ARG when it runs out
+ *   bpmi_ipa_wire_expand       HOST code, no ctx: blobs -> ab, xs, LR, transcripts[0, cap) with tr_off (n_proofs + 1), start, status.
+ *                              cap must hold the expansion BOUND of the call: per proof min(len - 78 - 98 k + 169 k, 2^17), 0 for a
+ *                              blob shorter than 78 + 98 k (BPMI_E_ARG otherwise).  The host twin (csrc/ipa_wire_host.hpp)
+ *   bpmi_ipa_wire_expand_dev   the same bytes (tests/test_gpu_ipa_wire.py) by the kernels of csrc/ipa_wire_kernels.hpp, downloaded: the
+ *                              comparison hook.  bpmi_debug_ipap_t_budget applies
+ *   bpmi_ipa_verify_batch_wire_dev   the blobs uploaded as they are; decompression and expansion in device memory; then the
+ *                              preparation, the s-vector sum and the one MSM of bpmi_ipa_verify_batch_packed_dev, unchanged.  u, P:
+ *                              n_proofs x 64 B; weights / seed, out, status, d_g, d_h (, d_hscale), the 0xFF rule of a refused
+ *                              generator and the caps (2^16 proofs, k <= 22, ...) as there.  n_proofs = 0 writes the identity.
+ *                              BPMI_E_ARG before anything is read beyond off, allocated or uploaded, and nothing is written:
+ *                              decreasing off, more than 4 GiB of blobs, NULL arguments, a protocol other than 2.
+ *                              bpmi_debug_ipap_t_budget applies (at least 64 proofs per launch).  One call at a time per ctx. */
+uint64_t bpmi_ipa_wire_bytes(uint32_t k, uint64_t prefix_len);
+int bpmi_ipa_wire_encode(uint32_t k, int protocol, uint64_t n_proofs, const uint8_t *ab, const uint8_t *xs, const uint8_t *LR, const uint8_t *transcripts,
+                         const uint64_t *tr_off, const uint32_t *start, uint8_t *blobs, uint64_t cap, uint64_t *off, uint8_t *status);
+int bpmi_ipa_wire_expand(uint32_t k, int protocol, uint64_t n_proofs, const uint8_t *blobs, const uint64_t *off, uint8_t *ab, uint8_t *xs, uint8_t *LR,
+                         uint8_t *transcripts, uint64_t cap, uint64_t *tr_off, uint32_t *start, uint8_t *status);
+int bpmi_ipa_wire_expand_dev(bpmi_ctx *ctx, uint32_t k, int protocol, uint64_t n_proofs, const uint8_t *blobs, const uint64_t *off, uint8_t *ab, uint8_t *xs,
+                             uint8_t *LR, uint8_t *transcripts, uint64_t cap, uint64_t *tr_off, uint32_t *start, uint8_t *status);
+int bpmi_ipa_verify_batch_wire_dev(bpmi_ctx *ctx, const void *d_g, const void *d_h, const void *d_hscale, uint64_t n, int protocol, uint64_t n_proofs,
+                                   const uint8_t *blobs, const uint64_t *off, const uint8_t *u, const uint8_t *P, const uint8_t *weights, const uint8_t *seed,
+                                   uint8_t out[64], uint8_t *status);
 /* test hook (not part of the drop-in surface): the byte budget of the transposed transcripts of ONE round of the mixed packed calls
  * on this ctx (0: the default, 2^28) -- a small value makes a few hundred proofs run as several rounds.  It also bounds one preparation
  * launch of bpmi_ipa_group_values_packed_dev (at least 64 proofs).  Not an option. */

@@ -116,6 +116,13 @@ SIGNATURES = {
     "bpmi_ipa_verify_batch_packed_mixed_dev": (_i, [_vp, _vp, _vp, _vp, _u64, _i, ctypes.c_uint32, _vp, _cp, _cp, _vp, _vp]),
     # ... classes, group (n_classes x uint64), weights, seed, values, value_off (n_classes + 1 x uint64), status
     "bpmi_ipa_group_values_packed_mixed_dev": (_i, [_vp, _vp, _vp, _vp, _u64, _i, ctypes.c_uint32, _vp, _vp, _cp, _cp, _vp, _vp, _vp]),
+    # BPIP2: (k, prefix_len); k, protocol, n_proofs, ab, xs, LR, transcripts, tr_off, start, blobs, cap, off, status; k, protocol, n_proofs, blobs, off,
+    # ab, xs, LR, transcripts, cap, tr_off, start, status (the _dev form behind ctx); ctx, g, h, hscale, n, protocol, n_proofs, blobs, off, u, P, ...
+    "bpmi_ipa_wire_bytes": (_u64, [ctypes.c_uint32, _u64]),
+    "bpmi_ipa_wire_encode": (_i, [ctypes.c_uint32, _i, _u64, _cp, _cp, _cp, _cp, _vp, _vp, _vp, _u64, _vp, _vp]),
+    "bpmi_ipa_wire_expand": (_i, [ctypes.c_uint32, _i, _u64, _cp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "bpmi_ipa_wire_expand_dev": (_i, [_vp, ctypes.c_uint32, _i, _u64, _cp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "bpmi_ipa_verify_batch_wire_dev": (_i, [_vp, _vp, _vp, _vp, _u64, _i, _u64, _cp, _vp, _cp, _cp, _cp, _cp, _vp, _vp]),
     "bpmi_debug_ipap_t_budget": (_i, [_vp, _u64]),
     "bpmi_host_alloc": (_i, [_vp, ctypes.c_size_t, ctypes.POINTER(_vp)]),
     "bpmi_host_free": (_i, [_vp, _vp]),

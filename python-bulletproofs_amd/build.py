@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbpmi.so")
 SOURCES = ["bpmi.hip"]
-HEADERS = ["field.hpp", "field_gen.hpp", "curve.hpp", "scalar.hpp", "shared_defs.hpp", "options_host.hpp", "msm_plan_host.hpp", "rp_batch_plan_host.hpp", "rp_prove_plan_host.hpp", "rp_prove_mixed_plan_host.hpp", "ipa_batch_plan_host.hpp", "msm_batch_plan_host.hpp", "msm_batch_host.hpp", "msm_fixed_plan_host.hpp", "msm_fixed_kernels.hpp", "msm_fixed_host.hpp", "svector_batch.hpp", "ipa_batch_host.hpp", "ipa_mixed_plan_host.hpp", "svector_mixed.hpp", "ipa_mixed_kernels.hpp", "ipa_mixed_host.hpp", "ipa_packed_plan_host.hpp", "ipa_packed_host.hpp", "ipa_packed_kernels.hpp", "ipa_packed_dev_host.hpp", "ipa_packed_mixed_plan_host.hpp", "ipa_packed_mixed_dev_host.hpp", "ipa_group_plan_host.hpp", "ipa_group_dev_host.hpp", "ipa_group_mixed_plan_host.hpp", "ipa_group_mixed_dev_host.hpp", "rp_batch_dev_host.hpp", "rp_mixed_plan_host.hpp", "rp_mixed_dev_host.hpp", "rp_group_mixed_plan_host.hpp", "rp_group_mixed_dev_host.hpp", "context.hpp", "device_util.hpp", "msm_kernels.hpp",
+HEADERS = ["field.hpp", "field_gen.hpp", "curve.hpp", "scalar.hpp", "shared_defs.hpp", "options_host.hpp", "msm_plan_host.hpp", "rp_batch_plan_host.hpp", "rp_prove_plan_host.hpp", "rp_prove_mixed_plan_host.hpp", "ipa_batch_plan_host.hpp", "msm_batch_plan_host.hpp", "msm_batch_host.hpp", "msm_fixed_plan_host.hpp", "msm_fixed_kernels.hpp", "msm_fixed_host.hpp", "svector_batch.hpp", "ipa_batch_host.hpp", "ipa_mixed_plan_host.hpp", "svector_mixed.hpp", "ipa_mixed_kernels.hpp", "ipa_mixed_host.hpp", "ipa_packed_plan_host.hpp", "ipa_packed_host.hpp", "ipa_packed_kernels.hpp", "ipa_packed_dev_host.hpp", "ipa_packed_mixed_plan_host.hpp", "ipa_packed_mixed_dev_host.hpp", "ipa_wire_plan_host.hpp", "ipa_wire_host.hpp", "ipa_wire_kernels.hpp", "ipa_wire_dev_host.hpp", "ipa_group_plan_host.hpp", "ipa_group_dev_host.hpp", "ipa_group_mixed_plan_host.hpp", "ipa_group_mixed_dev_host.hpp", "rp_batch_dev_host.hpp", "rp_mixed_plan_host.hpp", "rp_mixed_dev_host.hpp", "rp_group_mixed_plan_host.hpp", "rp_group_mixed_dev_host.hpp", "context.hpp", "device_util.hpp", "msm_kernels.hpp",
            "point_kernels.hpp", "point_check_host.hpp", "fold_ops_host.hpp", "scalar_kernels.hpp", "msm_host.hpp", "ipa_verify_msm_host.hpp", "host_tail.hpp", "rp_batch_host.hpp", "host_pool.hpp", "rp_algebra_host.hpp", "transcript_host.hpp", "rp_wire_v2_host.hpp", "rp_batch_kernels.hpp", "rp_prove_kernels.hpp", "rp_prove_mixed_kernels.hpp", "prove_shared_host.hpp", "rp_prove_host.hpp", "rp_prove_mixed_host.hpp", "ipa_prove_plan_host.hpp", "ipa_prove_mixed_plan_host.hpp", "ipa_prove_kernels.hpp", "ipa_prove_mixed_kernels.hpp", "ipa_prove_host.hpp", "ipa_prove_mixed_host.hpp", "ipa_host.hpp", "scalar_gen.hpp", "h2c.hpp", "h2c_kernels.hpp", "h2c_host.hpp", os.path.join("..", "..", "include", "bpmi.h")]
 
 

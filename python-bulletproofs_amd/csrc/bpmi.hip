@@ -67,6 +67,7 @@ using namespace bpmi;
 #include "ipa_mixed_plan_host.hpp"
 #include "ipa_packed_plan_host.hpp"
 #include "ipa_packed_mixed_plan_host.hpp"
+#include "ipa_wire_plan_host.hpp"
 #include "ipa_group_plan_host.hpp"
 #include "ipa_group_mixed_plan_host.hpp"
 #include "msm_batch_plan_host.hpp"
@@ -88,12 +89,14 @@ using namespace bpmi;
 #include "msm_fixed_host.hpp"
 #include "rp_batch_host.hpp"
 #include "ipa_packed_host.hpp"
+#include "ipa_wire_host.hpp"
 #include "host_pool.hpp"
 #include "rp_algebra_host.hpp"
 #include "transcript_host.hpp"
 #include "rp_wire_v2_host.hpp"
 #include "rp_batch_kernels.hpp"
 #include "ipa_packed_kernels.hpp"
+#include "ipa_wire_kernels.hpp"
 #include "rp_prove_kernels.hpp"
 #include "rp_prove_mixed_kernels.hpp"
 #include "ipa_prove_kernels.hpp"
@@ -895,6 +898,7 @@ int bpmi_ipa_verify_dev(bpmi_ctx *ctx, const void *d_g, const void *d_h, const v
 #include "ipa_mixed_host.hpp"
 #include "ipa_packed_dev_host.hpp"
 #include "ipa_packed_mixed_dev_host.hpp"
+#include "ipa_wire_dev_host.hpp"
 #include "ipa_group_dev_host.hpp"
 #include "ipa_group_mixed_dev_host.hpp"
 #include "msm_batch_host.hpp"

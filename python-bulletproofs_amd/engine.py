@@ -350,6 +350,31 @@ class Engine:
                                                            ctypes.cast(out, ctypes.c_void_p), ctypes.cast(status, ctypes.c_void_p)))
         return out.raw, status.raw[:count]
 
+    # ---- inner-product proofs in the wire format BPIP2 (innerproduct/codec.py) ----
+    def ipa_wire_expand_dev(self, k, blobs, off, protocol=2):
+        """(ab, xs, lr, transcripts, starts, status) of bpmi_ipa_wire_expand_dev: the packed arrays a batch of blobs (joined bytes and
+        len(off) - 1 proofs) stands for, rebuilt by the device kernels and downloaded; the bytes of codec.packed_from_wire."""
+        count = len(off) - 1
+        if count <= 0:
+            return b"", b"", b"", [], [], b""
+        offs = (ctypes.c_uint64 * (count + 1))(*off)
+        cap = max(sum(max(off[i + 1] - off[i] - (78 + 98 * k), 0) for i in range(count)) + 169 * k * count, 1)
+        ab, xs, lr = ctypes.create_string_buffer(64 * count), ctypes.create_string_buffer(max(32 * k * count, 1)), ctypes.create_string_buffer(max(128 * k * count, 1))
+        tr, tr_off, start, status = ctypes.create_string_buffer(cap), (ctypes.c_uint64 * (count + 1))(), (ctypes.c_uint32 * count)(), ctypes.create_string_buffer(count)
+        self._ck(self.lib.bpmi_ipa_wire_expand_dev(self.ctx, k, protocol, count, bytes(blobs), offs, ab, xs, lr, tr, cap, tr_off, start, status))
+        raw = tr.raw
+        return (ab.raw, xs.raw[: 32 * k * count], lr.raw[: 128 * k * count], [raw[tr_off[i]: tr_off[i + 1]] for i in range(count)], list(start),
+                status.raw[:count])
+
+    def ipa_verify_batch_wire_dev(self, d_g, d_h, n, count, blobs, off, u, P, weights=None, seed=None, d_hscale=None, protocol=2):
+        """(out, status) of bpmi_ipa_verify_batch_wire_dev: ipa_verify_batch_packed_dev over the proofs the blobs stand for, expanded in
+        device memory.  blobs: joined bytes; off: count + 1 offsets (a list or a ctypes array of uint64); u, P: 64 bytes per proof."""
+        out, status = ctypes.create_string_buffer(64), ctypes.create_string_buffer(max(count, 1))
+        offs = off if isinstance(off, ctypes.Array) else (ctypes.c_uint64 * (count + 1))(*off)
+        self._ck(self.lib.bpmi_ipa_verify_batch_wire_dev(self.ctx, _ptr(d_g), _ptr(d_h), None if d_hscale is None else _ptr(d_hscale), n, protocol, count,
+                                                         blobs if isinstance(blobs, bytes) else bytes(blobs), offs, u, P, weights, seed, ctypes.cast(out, ctypes.c_void_p), ctypes.cast(status, ctypes.c_void_p)))
+        return out.raw, status.raw[:count]
+
     def ipa_group_values_packed_dev(self, d_g, d_h, n, protocol, count, ab, xs, lr, transcripts, starts, u, P, c=None, head=None, weights=None, seed=None,
                                     d_hscale=None, group=1):
         """(values, status) of bpmi_ipa_group_values_packed_dev: values[t] = the 64-byte value of the weighted combination over the

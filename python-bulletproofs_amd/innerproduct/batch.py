@@ -12,6 +12,7 @@ Two ways in.  Proof OBJECTS: `add` / `add_proof1` re-derive each transcript in P
 the arrays BatchInnerProductProver.prove2_packed / prove1_packed return: `verify_packed2` / `verify_packed1` hand them to ONE native
 call (bpmi_ipa_verify_batch_packed_dev) that re-hashes, compares, inverts and weights every proof on the device, one lane per proof,
 and runs the same MSM; the weights come from a fresh 32-byte seed per call, and the note above applies unchanged."""
+import ctypes
 import math
 import secrets
 
@@ -19,6 +20,7 @@ from .. import engine as _engine
 from ..ec import PackedPoints, pack_points, pack_scalars, secp256k1
 from ..locate import locate_by_bisection, locate_plan        # noqa: F401  (locate_by_bisection: also this module's old export)
 from ..utils.utils import mod_hash
+from .codec import _split as split_blobs
 from .inner_product_verifier import Verifier2
 
 Q = secp256k1.q
@@ -328,6 +330,31 @@ class BatchInnerProductVerifier:
         calls."""
         rows, sizes, count = self._packed_rows(2, us, Ps, None, ab, xs, lr, None, transcripts, starts)
         return self._verify_packed(2, rows, sizes, count, weights)
+
+    def verify_wire2(self, us, Ps, blobs, off=None, weights=None):
+        """True iff every Protocol-2 proof of a batch in the wire format BPIP2 (innerproduct/codec.py) is valid for its statement
+        (us[i], Ps[i]) -- points or packed bytes, 64 per proof.  blobs: a list of blobs, or the joined bytes with `off`, count + 1
+        offsets (a list or a ctypes array of uint64: what prove2_wire and codec.wire_from_packed return).  ONE native call
+        (bpmi_ipa_verify_batch_wire_dev): the bytes are uploaded as they are -- a third of the packed arrays -- and decompressed and
+        expanded in device memory; then the work of verify_packed2, unchanged.  A malformed blob or a point that does not decode makes
+        the batch invalid.  Weights as verify_packed2; a batch above 2^16 proofs runs as consecutive calls."""
+        to_bytes = lambda v: bytes(v) if isinstance(v, (bytes, bytearray, memoryview)) else pack_points(v)
+        if off is None:
+            blobs, off = split_blobs(blobs)
+        count = len(off) - 1
+        ub, Pb = to_bytes(us), to_bytes(Ps)
+        if count < 0 or len(ub) != 64 * count or len(Pb) != 64 * count:
+            raise ValueError("us and Ps: 64 bytes per proof, one per blob")
+        wb = self._weights_bytes(2, weights, count)
+        for lo in range(0, count, CALL_MAX):               # consecutive calls of at most 2^16 proofs; valid iff every call is
+            hi = min(lo + CALL_MAX, count)
+            offs = off if hi - lo == count and isinstance(off, ctypes.Array) else (ctypes.c_uint64 * (hi - lo + 1))(*off[lo: hi + 1])
+            seed = None if wb is not None else secrets.token_bytes(32)
+            out, status = self.engine.ipa_verify_batch_wire_dev(self._d[0], self._d[1], self.n, hi - lo, blobs, offs, ub[64 * lo: 64 * hi], Pb[64 * lo: 64 * hi],
+                                                                None if wb is None else wb[32 * lo: 32 * hi], seed, self._d_scale)
+            if out != bytes(64) or status != bytes(hi - lo):
+                return False
+        return True
 
     def verify_packed1(self, u, Ps, cs, ab, xs, lr, head, transcripts, weights=None):
         """True iff every Protocol-1 proof of the packed batch (ab, xs, lr, head, transcripts: what prove1_packed returns) is valid

@@ -122,6 +122,18 @@ class BatchInnerProductProver:
         out = self._run(2, ab, bb, None, None, transcripts, count)
         return out[0], out[1], out[2], out[4]
 
+    def prove2_wire(self, as_, bs, transcripts=None):
+        """Protocol 2 straight to the wire format BPIP2 (innerproduct/codec.py): (blobs, off) -- the proofs of prove2_packed as blobs
+        back to back and count + 1 offsets, the arguments of BatchInnerProductVerifier.verify_wire2.  prove2_packed plus the native
+        host encoder (bpmi_ipa_wire_encode); start_transcript as prove2 computes it (the items of the prefix, 1 without one)."""
+        from .codec import wire_from_packed
+        ab, xs, lr, trs = self.prove2_packed(as_, bs, transcripts)
+        if isinstance(transcripts, tuple):
+            sb, offs = transcripts
+            transcripts = [sb[offs[i]: offs[i + 1]] for i in range(len(trs))]
+        starts = [len(t.split(b"&")) if t else 1 for t in (transcripts or [None] * len(trs))]
+        return wire_from_packed(ab, xs, lr, trs, starts)
+
     # ---- Proof objects -------------------------------------------------------------------------------------------------------
     def _proof2(self, i, ab, xs, lr, transcript, start):
         k = self.k
