@@ -5,7 +5,10 @@
 // the 9 x 29-bit device formulation compiled for x86).  Inputs are the device's XYZZ
 // records (4 x 9 u32 limbs, weakly reduced); the result is the canonical 64-byte affine
 // point.  tests/test_gpu_msm.py runs every multi-level case under both tail = 1 (the
-// device kernel built from curve.hpp) and tail = 2 (this file) and requires equal bytes.
+// device kernel built from curve.hpp) and tail = 2 (this file) and requires equal bytes;
+// tests/test_gpu_msm_reduce_degenerate.py does the same on colliding window sums (the
+// accumulator meeting its addend and its negative), and tests/test_msm_dlog_ref_cpu.py
+// runs this file alone on those sums.
 #pragma once
 #include <stdint.h>
 #include <string.h>
